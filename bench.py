@@ -19,6 +19,7 @@ N > 1 (one process per GPU): the SAME native prover, iopx_aurora_prove_dist, wit
 contiguous cosets (libiop_amd/cpp/dist.hpp) and an RCCL communicator created through the C ABI; "strong" scaling: one proof.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR   (also writes DIR/transcript.npy: the last timed proof's bytes)
     python bench.py --gpus N ...                      (starts torch.distributed.run itself, as a child process, when RANK is unset)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
@@ -196,6 +197,17 @@ def reference_own_digest_equal(log_n, transcript):
     return None
 
 
+def dump_outputs(out_dir, outputs):
+    """Write each output of the timed path as out_dir/<name>.npy in float32 (a transcript's bytes are exact in it)."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, value in outputs.items():
+        a = np.frombuffer(value, dtype=np.uint8).astype(np.float32) if isinstance(value, (bytes, bytearray)) else np.asarray(value, dtype=np.float32)
+        total += a.nbytes
+        assert total <= 64 << 20, "outputs over 64 MB: dump a seeded sample instead"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def rank_replay(lib, torch, native, params, world, rank, steps=5, warmup=2):
     """One rank's compute path of the N-rank prover, measured on ONE GPU: iopx_aurora_prove_dist over a replay communicator
     (iopx_comm_create_replay: rank `rank` of `world` alone, every collective completed locally on the stream — all-gathers filled from this rank's
@@ -250,7 +262,14 @@ def main():
     ap.add_argument("--no-warm", action="store_true", help="do not call iopx_aurora_instance_warm: config.first_proof_ms is then the cold first proof")
     ap.add_argument("--no-rank-replay", action="store_true", help="skip config.rank_replay (ranks 0 and N-1 of 2, 4, 8 played alone on this GPU)")
     ap.add_argument("--cpu-all-cores", action="store_true", help="also time one independent oracle proof per host core at once (not in the reference, which is single-threaded)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the proof's transcript bytes, as float32) to DIR/transcript.npy; the seeded "
+                         "instance is the same on every run, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.replay_rank is not None:
+        ap.error("--dump-outputs: a replayed rank's proof is meaningless (collectives completed locally); run without --replay-rank")
 
     # RCCL prints a version banner on STDOUT at NCCL_DEBUG=VERSION/INFO (seen on the GPU box: five lines ahead of the JSON line);
     # stdout carries the one JSON line only, so the debug level is pinned to WARN unless IOPX_NCCL_DEBUG says otherwise
@@ -375,6 +394,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     prover_s = dt / args.steps
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"transcript": transcript.serialize()})
 
     # the second, independently written prover (libiop_amd/aurora.py; over libiop_amd/dist.py's operators under --force-sharded) on the same
     # instance; with N > 1 ranks rank 0 proves the instance once more on its own GPU alone instead (no collective involved): the distributed

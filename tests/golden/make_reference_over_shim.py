@@ -14,7 +14,7 @@ import harness  # noqa: E402
 
 
 def main():
-    why = harness.available()
+    why = harness.buildable()
     if why:
         sys.exit(why)
     harness.build(stubbed=False)
@@ -40,8 +40,8 @@ def main():
 def functions():
     """tests/golden/reference_functions.json: tests/harness/reference_vectors.cpp's lines (the reference's own functions on seeded inputs)."""
     import subprocess
-    harness._make(["_build/reference_vectors"])
-    out = subprocess.run([os.path.join(harness.HERE, "_build", "reference_vectors")], capture_output=True, text=True, check=True).stdout
+    harness._make(["reference_vectors"])
+    out = subprocess.run([os.path.join(harness.BUILD, "reference_vectors")], capture_output=True, text=True, check=True).stdout
     entries = [json.loads(line) for line in out.splitlines() if line.startswith("{")]
     with open(os.path.join(ROOT, "tests", "golden", "reference_functions.json"), "w") as f:
         f.write('{"generated_by": "tests/golden/make_reference_over_shim.py", "program": "tests/harness/reference_vectors.cpp over tests/harness/shim",\n "entries": [\n')

@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE ONLY: run the reference's own test programs built by `make reftests_plain` / `reftests_stubbed`; one summary line per program."""
 import glob, os, subprocess, sys, time, json
 HERE = os.path.dirname(os.path.abspath(__file__))
-variant = sys.argv[1]                   # plain | stubbed (tests/harness/_build/reftests/...) | hip (tests/harness/_hip/reftests/...: on the GPU box)
-base = os.path.join(HERE, "_hip", "reftests") if variant == "hip" else os.path.join(HERE, "_build", "reftests", variant)
+REF_OUT = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref")
+variant = sys.argv[1]                   # plain | stubbed (oracle/_ref/build/reftests/...) | hip (oracle/_ref/hip/reftests/...: on the GPU box)
+base = os.path.join(REF_OUT, "hip", "reftests") if variant == "hip" else os.path.join(REF_OUT, "build", "reftests", variant)
 # Tests that feed raw random bytes as libff::edwards_Fr elements (random_vector<FieldT>: "invalid elements for libff prime fields", the reference's own words,
 # algebra/polynomials/polynomial.tcc:233-234) and expect acceptance: libff-style reduction tolerates unreduced representatives, the kernels take canonical ones —
 # with the stubs in force these two tests pass or fail by the draw (about one run in four fails).  Left out by name; everything else of the two programs runs.
@@ -39,7 +40,7 @@ for exe in sorted(glob.glob(os.path.join(base, "*", "*"))):
     except subprocess.TimeoutExpired:
         out[name] = {"rc": "timeout", "seconds": round(time.time() - t, 1)}
     print(name, out[name], flush=True)
-dst = os.path.join(HERE, "_build") if variant != "hip" else os.environ.get("REFTEST_OUT", "/tmp")
+dst = os.path.join(REF_OUT, "build") if variant != "hip" else os.environ.get("REFTEST_OUT", "/tmp")
 os.makedirs(dst, exist_ok=True)
 json.dump(out, open(os.path.join(dst, "reftests_%s.json" % variant), "w"), indent=1)
 print("programs", len(out), "tests", sum(v.get("tests", 0) for v in out.values()), "passed", sum(v.get("passed", 0) for v in out.values()))

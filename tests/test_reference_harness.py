@@ -2,7 +2,8 @@
 field arithmetic is this repository's host code and (2) with the stubs of INTEGRATION.md compiled in verbatim, forwarding to the CPU build of the
 kernel sources through the C ABI.  Both must produce the oracle's transcript byte for byte, and the reference's own verifier must accept it.
 
-Container-only (skipped where /root/reference, libsodium or GMP are absent — the GPU box); tests/golden/reference_over_shim.json carries the digests there.
+The programs are what build() compiled into oracle/_ref/build (oracle/reference.mk); nothing here reads the reference tree.  Skipped where build() could not
+compile them (no reference tree, libsodium or GMP — the GPU box); tests/golden/reference_over_shim.json carries the digests there.
 What this shows: libiop's protocol code calls the kernels UNCHANGED through the documented stubs, and the oracle follows libiop's logic as libiop's own code
 executes it.  What it does not: anything about libff's bytes — the shim is a stand-in."""
 import os
@@ -23,9 +24,7 @@ SMALL = [c for c in harness.CASES if c[2] <= 10]
 
 @pytest.fixture(scope="module")
 def built():
-    from emu_lib import emu
-    emu()                       # tests/emu/libiopx_emu.so: the stubbed program links it
-    harness.build()
+    assert harness.available() is None, harness.available()
     return True
 
 
@@ -91,7 +90,7 @@ def test_ligero_calls_the_kernels_unchanged_too(field, log_n, built):
 def test_the_compiled_stub_text_is_integration_md(built):
     with open(os.path.join(harness.ROOT, "INTEGRATION.md")) as f:
         md = f.read()
-    with open(os.path.join(harness.HERE, "_build", "stubs.inc")) as f:
+    with open(os.path.join(harness.BUILD, "stubs.inc")) as f:
         inc = f.read()
     for needle in ("additive_FFT<libff::gf192>", "multiplicative_IFFT<libff::edwards_Fr>", "construct_with_leaves_serialized_by_cosets", "solve_pow_internal",
                    "combined_LDT_virtual_oracle<libff::edwards_Fr>::evaluated_contents"):
@@ -115,8 +114,7 @@ def test_the_committed_function_vectors_are_what_the_references_functions_produc
     """tests/golden/reference_functions.json == the lines tests/harness/reference_vectors.cpp prints today (libiop's own FFTs, folds, trees, ... on the seeds)."""
     import json
     import subprocess
-    harness._make(["_build/reference_vectors"])
-    out = subprocess.run([os.path.join(harness.HERE, "_build", "reference_vectors")], capture_output=True, text=True, check=True).stdout
+    out = subprocess.run([os.path.join(harness.BUILD, "reference_vectors")], capture_output=True, text=True, check=True).stdout
     now = [json.loads(line) for line in out.splitlines() if line.startswith("{")]
     with open(os.path.join(harness.ROOT, "tests", "golden", "reference_functions.json")) as f:
         committed = json.load(f)["entries"]
@@ -127,7 +125,7 @@ def test_the_committed_function_vectors_are_what_the_references_functions_produc
 def test_the_references_own_test_files_pass_with_the_kernels_underneath(name, built):
     """libiop's own test files (libiop/tests/*/test_*.cpp), unmodified, compiled as programs with the stubs of INTEGRATION.md in force (googletest replaced by
     tests/harness/shim/gtest/gtest.h, tests_prelude.hpp force-included ahead of the test's text): every TEST passes, and the multiplicative ones ran their
-    transforms in the kernel library.  Default: three programs; IOPX_REFTESTS=all: the 34 of tests/harness/Makefile (143 tests with the stubs, 145 without, recorded in
+    transforms in the kernel library.  Default: three programs; IOPX_REFTESTS=all: the 34 of oracle/reference.mk (143 tests with the stubs, 145 without, recorded in
     profiles/r06_reference_own_tests_{plain,stubbed}.json)."""
     harness.build_reftest(name)
     ran, ok, kernels, tail = harness.run_reftest(name)

@@ -1,22 +1,22 @@
-"""Container-only check of the drop-in boundary's declarations against the reference's own header TEXT.
+"""The drop-in boundary's declarations against the reference's own header TEXT.
 
 The reference's domain classes cannot be compiled here (every libiop header includes libff, an empty submodule, and writing stand-in
 headers for it is not allowed), so what CAN be checked is checked: for every accessor and free function the forwarding bodies of
 libiop_amd/cpp/reference_binding.hpp go through, the declaration in the reference header (return type, value category, constness,
 parameter types) is extracted and compared with the mirror's declaration in libiop_amd/cpp/libiop_amd.hpp.  This is the test that would
 have caught round 5's `const FieldT &shift()` (the reference returns BY VALUE: subspace.hpp:61, field_subset.hpp:67, subgroup.hpp:102).
-It reads /root/reference, which exists only in the build container: skipped elsewhere."""
+The reference's side is data: tests/golden/reference_declarations.json holds the declarations as this file's parser extracts them from the reference
+headers (tests/golden/make_reference_declarations.py, run where the reference tree is present), so nothing here reads the reference tree."""
+import json
 import os
 import re
 
 import pytest
 
-REF = "/root/reference/libiop"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIRROR = os.path.join(ROOT, "libiop_amd", "cpp", "libiop_amd.hpp")
 BINDING = os.path.join(ROOT, "libiop_amd", "cpp", "reference_binding.hpp")
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_declarations.json")
 
 
 def _strip_comments(text):
@@ -78,9 +78,21 @@ def _declaration(body, name):
     return _norm_type(ret), _param_types(m.group(2)), bool(m.group(3))
 
 
-def _ref(path):
-    with open(os.path.join(REF, path)) as f:
+def _ref_text(ref_root, path):
+    """Comment-free text of a reference header (the fixture generator's input)."""
+    with open(os.path.join(ref_root, path)) as f:
         return _strip_comments(f.read())
+
+
+def _fixture():
+    with open(FIXTURE) as f:
+        return json.load(f)
+
+
+def _ref(key):
+    """The reference's declaration recorded under `key`: (return type, [parameter types], const?) or, for a constructor, [parameter types]."""
+    d = _fixture()["declarations"][key]
+    return (d[0], d[1], d[2]) if isinstance(d, list) and len(d) == 3 and isinstance(d[1], list) else d
 
 
 def _mirror():
@@ -116,7 +128,7 @@ ACCESSORS = [
 
 @pytest.mark.parametrize("header,ref_class,mirror_class,member", ACCESSORS, ids=lambda v: os.path.basename(v) if "/" in v else v)
 def test_member_declarations_match_the_reference(header, ref_class, mirror_class, member):
-    ref = _declaration(_class_body(_ref(header), ref_class), member)
+    ref = _ref("%s:%s::%s" % (header, ref_class, member))
     mine = _declaration(_class_body(_mirror(), mirror_class), member)
     assert ref == mine, "%s::%s: reference %s, mirror %s" % (ref_class, member, ref, mine)
 
@@ -134,7 +146,7 @@ FUNCTIONS = [
 
 @pytest.mark.parametrize("header,name", FUNCTIONS, ids=lambda v: os.path.basename(v) if "/" in v else v)
 def test_free_function_signatures_match_the_reference(header, name):
-    ref = _declaration(_ref(header), name)
+    ref = _ref("%s:%s" % (header, name))
     mine = _declaration(_mirror(), name)
     assert ref == mine, "%s: reference %s, mirror %s" % (name, ref, mine)
 
@@ -142,7 +154,7 @@ def test_free_function_signatures_match_the_reference(header, name):
 def test_construct_with_leaves_serialized_by_cosets_takes_the_references_arguments():
     """The mirror adds one defaulted trailing argument (the position map, for trees over the other domain kind); the reference's
     two arguments come first with the reference's types (merkle_tree.hpp:88-90)."""
-    ref = _declaration(_class_body(_ref("bcs/merkle_tree.hpp"), "merkle_tree"), "construct_with_leaves_serialized_by_cosets")
+    ref = _ref("bcs/merkle_tree.hpp:merkle_tree::construct_with_leaves_serialized_by_cosets")
     mine = _declaration(_class_body(_mirror(), "merkle_tree"), "construct_with_leaves_serialized_by_cosets")
     assert ref[0] == mine[0] == "void" and mine[1][:2] == ref[1] and mine[1][2:] == ["int"] and ref[2] == mine[2]
 
@@ -155,7 +167,7 @@ def _first_constructor(body, name):
 
 def test_merkle_constructor_takes_the_references_arguments():
     """merkle_tree.hpp:67-72: (num_leaves, leaf_hasher, node_hasher, digest_len_bytes, make_zk, security_parameter)."""
-    ref = _first_constructor(_class_body(_ref("bcs/merkle_tree.hpp"), "merkle_tree"), "merkle_tree")
+    ref = _ref("bcs/merkle_tree.hpp:merkle_tree::merkle_tree()")
     mine = _first_constructor(_class_body(_mirror(), "merkle_tree"), "merkle_tree")
     assert len(ref) == 6 and ref == mine, (ref, mine)
 
@@ -179,6 +191,18 @@ def test_binding_header_uses_only_accessors_the_reference_declares():
         body = _strip_comments(f.read())
     used = set(re.findall(r"\b(?:domain|f_i_domain|codeword_domain)\.(\w+)\(", body))
     assert used == {"shift", "basis", "dimension", "num_elements", "generator"}, used
-    fs = _class_body(_ref("algebra/field_subset/field_subset.hpp"), "field_subset")
     for member in used:
-        _declaration(fs, member)                                     # field_subset declares all five (field_subset.hpp:47-68)
+        assert "algebra/field_subset/field_subset.hpp:field_subset::" + member in _fixture()["declarations"]   # field_subset declares all five (field_subset.hpp:47-68)
+
+
+def reference_declarations(ref_root):
+    """What the fixture holds, extracted from the reference headers under ref_root (the reference's libiop/ directory)."""
+    out = {}
+    for header, ref_class, _, member in ACCESSORS:
+        out["%s:%s::%s" % (header, ref_class, member)] = _declaration(_class_body(_ref_text(ref_root, header), ref_class), member)
+    for header, name in FUNCTIONS:
+        out["%s:%s" % (header, name)] = _declaration(_ref_text(ref_root, header), name)
+    merkle = _class_body(_ref_text(ref_root, "bcs/merkle_tree.hpp"), "merkle_tree")
+    out["bcs/merkle_tree.hpp:merkle_tree::construct_with_leaves_serialized_by_cosets"] = _declaration(merkle, "construct_with_leaves_serialized_by_cosets")
+    out["bcs/merkle_tree.hpp:merkle_tree::merkle_tree()"] = _first_constructor(merkle, "merkle_tree")
+    return out

@@ -1,6 +1,6 @@
 """Manual run (gpurun): the REFERENCE'S OWN provers — libiop's sources compiled unmodified in the build container by tests/harness, with the stubs of
-INTEGRATION.md compiled in — linked against the HIP build of the library and run on the MI355X (`make -C tests/harness hip` builds
-tests/harness/_hip/reference_stubbed_hip before the snapshot is sent).  Prints, per case, the reference verifier's decision, whether the transcript's digest equals
+INTEGRATION.md compiled in — linked against the HIP build of the library and run on the MI355X (build(), through `make -f oracle/reference.mk hip`,
+builds oracle/_ref/hip/reference_stubbed_hip before the tree is sent).  Prints, per case, the reference verifier's decision, whether the transcript's digest equals
 the committed one (tests/golden/reference_over_shim.json, oracle_*_transcript_digests_large.json), the kernels the reference's prover launched and the
 wall-clock of the whole program (generator, prover, verifier: the reference's host code around the stubs is unchanged and single-threaded)."""
 import hashlib
@@ -12,7 +12,7 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "harness", "_hip", "reference_stubbed_hip")
+EXE = os.path.join(ROOT, "oracle", "_ref", "hip", "reference_stubbed_hip")
 
 
 def expected():

@@ -172,6 +172,7 @@ class Library:
         c.iopx_fri_fold_add_gf192.argtypes = [_u64p, _u64p, _sz, _u64p, _sz, _u64p, _u64p]
         c.iopx_mul_fft_fp3_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp]
         c.iopx_mul_fft_fp3.argtypes = [_u64p, _sz, _sz, _u64p, _u64p, _u64p]
+        c.iopx_mul_fft_fp3_windows_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp, _sz, ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_vp)]
         c.iopx_mul_ifft_fp3_dev.argtypes = [_vp, _sz, _u64p, _u64p, _vp]
         c.iopx_mul_ifft_fp3.argtypes = [_u64p, _sz, _u64p, _u64p, _u64p]
         c.iopx_mul_ifft_known_degree_fp3_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp]
@@ -345,6 +346,45 @@ class Library:
         self._check(self.c.iopx_mul_fft_fp3(coeffs.ctypes.data_as(_u64p), coeffs.shape[0], log_n, gen.ctypes.data_as(_u64p),
                                             shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
         return out
+
+    def multiplicative_FFT_windows_dev(self, d_coeffs, n_coeffs, log_n, shift, d_out, windows, gen=None):
+        """multiplicative_FFT into d_out that also writes up to two strided windows of its output: windows = [(first, log_stride, d_window), ...],
+        window w receives out[first + k 2^log_stride] for k < 2^(log_n - log_stride)."""
+        shift = _as_u64(shift)
+        gen = _as_u64(edwards_subgroup_generator(log_n) if gen is None else gen)
+        k = len(windows)
+        first = (_sz * max(k, 1))(*[int(w[0]) for w in windows])
+        log_stride = (_sz * max(k, 1))(*[int(w[1]) for w in windows])
+        dst = (_vp * max(k, 1))(*[w[2] for w in windows])
+        self._check(self.c.iopx_mul_fft_fp3_windows_dev(_vp(d_coeffs), int(n_coeffs), int(log_n), gen.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p),
+                                                        _vp(d_out), k, first, log_stride, dst))
+
+    def multiplicative_FFT_windows(self, poly_coeffs, log_n, shift, windows, in_place=False):
+        """multiplicative_FFT with windows = [(first, log_stride), ...] of its output written beside it: returns (out, [window, ...]).
+        in_place: the coefficients are uploaded into the output buffer itself (d_coeffs == d_out)."""
+        coeffs = _as_u64(poly_coeffs)
+        n = 1 << log_n
+        d_out = self.malloc(24 * n)
+        d_coeffs = d_out if in_place else (self.malloc(max(coeffs.nbytes, 8)))
+        d_wins = [self.malloc(24 * (n >> int(ls))) for _, ls in windows]
+        try:
+            if coeffs.shape[0]:
+                self.h2d(d_coeffs, coeffs)
+            self.multiplicative_FFT_windows_dev(d_coeffs, coeffs.shape[0], log_n, shift, d_out,
+                                                [(f, ls, d) for (f, ls), d in zip(windows, d_wins)])
+            out = np.empty((n, 3), dtype=np.uint64)
+            self.d2h(out, d_out)
+            wins = []
+            for (_, ls), d in zip(windows, d_wins):
+                wins.append(np.empty((n >> int(ls), 3), dtype=np.uint64))
+                self.d2h(wins[-1], d)
+        finally:
+            for d in d_wins:
+                self.free(d)
+            if not in_place:
+                self.free(d_coeffs)
+            self.free(d_out)
+        return out, wins
 
     def multiplicative_IFFT(self, evals, shift, gen=None):
         """multiplicative_IFFT(evals, coset) — fft.tcc:343-361 over libfqfft iFFT / icosetFFT."""

@@ -214,3 +214,12 @@ def check_lincheck(lib, n, k, seed, prime_field=False):
     assert np.array_equal(got, oracle.lincheck_combine(fz, mz, r, p1, p2, prime_field))
     with pytest.raises(ValueError):         # basic_lincheck_aux.tcc:32-34
         lib.lincheck(fz, mz, r[:k - 1] if k > 1 else np.zeros((2, 3), dtype=np.uint64), p1, p2, prime_field)
+
+
+# GPU only: the many-gap rows of ADDITIVE at 2^14 points, where the combine runs on many workgroups (the no-slots kernel's grid-stride loop and
+# the uniform high index bits of ldt_subset_sum), with both bases; and twenty oracles of distinct degrees over a 2^14-point coset
+ADDITIVE_LARGE = [(14, [12000] + [12000 - 3 * k - 1 for k in range(20)], 17, kind) for kind in ("standard", "random")] + \
+                 [(14, [12000] + [12000 - (1 << k) for k in range(8)] + [12000 - 3, 12000 - 5, 12000 - 9, 12000 - 17, 12000 - 33], 19, kind)
+                  for kind in ("standard", "random")] + \
+                 [(14, [12000] + [12000 - 3 * k - 1 for k in range(15)], 20, kind) for kind in ("standard", "random")]
+MULTIPLICATIVE_LARGE = [(14, [(1 << 14) - 1 - 397 * k for k in range(20)], 21, True)]

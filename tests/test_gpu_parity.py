@@ -144,7 +144,8 @@ def test_fri_chain_cfg3_shape_small(gpu):
 
 
 @pytest.mark.parametrize("additive", [True, False])
-@pytest.mark.parametrize("r,cs,L", [(1, 1, 2), (1, 2, 16), (4, 2, 64), (1, 4, 32), (12, 2, 8), (2, 8, 4), (4, 2, 1 << 15), (1, 2, 1 << 17), (2, 2, 128), (2, 4, 1 << 12), (3, 4, 32), (4, 4, 256), (3, 2, 1 << 14), (5, 2, 16)])
+@pytest.mark.parametrize("r,cs,L", [(1, 1, 2), (1, 2, 16), (4, 2, 64), (1, 4, 32), (12, 2, 8), (2, 8, 4), (4, 2, 1 << 15), (1, 2, 1 << 17), (2, 2, 128), (2, 4, 1 << 12), (3, 4, 32), (4, 4, 256), (3, 2, 1 << 14), (5, 2, 16),
+                                   (1, 16, 64), (3, 16, 128), (2, 32, 32)])
 def test_merkle(gpu, additive, r, cs, L):
     n = L * cs
     oracles = [rand_elems(700 + k, n, W) for k in range(r)]
@@ -409,14 +410,18 @@ import fri_cases as fc
 
 @pytest.mark.parametrize("field_name,dim,rs_extra,loc_param,interactions,queries", [
     ("gf192", 10, 3, 2, 1, 10), ("gf192", 16, 2, 2, 1, 10), ("gf192", 13, 2, 2, 2, 6),
-    ("edwards_Fr", 10, 3, 2, 1, 10), ("edwards_Fr", 16, 2, 2, 1, 10)])
+    ("edwards_Fr", 10, 3, 2, 1, 10), ("edwards_Fr", 16, 2, 2, 1, 10),
+    # localization 4 and 5 (rounds [1, 4, 4] and [1, 5, 5, 5]): unfused folds, leaves over cosets of 16 / 32, queries of large cosets
+    ("gf192", 13, 2, 4, 1, 8), ("gf192", 16, 2, 5, 1, 10), ("edwards_Fr", 13, 2, 4, 1, 8), ("edwards_Fr", 16, 2, 5, 1, 10)])
 def test_fri_snark(gpu, field_name, dim, rs_extra, loc_param, interactions, queries):
     import torch
     gpu.set_stream(torch.cuda.current_stream().cuda_stream)
     assert fc.prove_and_verify(gpu, torch, torch.device("cuda:0"), field_name, dim, rs_extra, loc_param, interactions, queries, 0x2203)
 
 
-@pytest.mark.parametrize("field_name,dim,rs_extra,loc_param,interactions,queries", [("gf192", 16, 2, 2, 1, 10), ("gf192", 13, 2, 2, 2, 6), ("edwards_Fr", 16, 2, 2, 1, 10)])
+@pytest.mark.parametrize("field_name,dim,rs_extra,loc_param,interactions,queries", [("gf192", 16, 2, 2, 1, 10), ("gf192", 13, 2, 2, 2, 6), ("edwards_Fr", 16, 2, 2, 1, 10),
+                                                                                  ("gf192", 13, 2, 4, 1, 8), ("gf192", 16, 2, 5, 1, 10), ("edwards_Fr", 13, 2, 4, 1, 8),
+                                                                                  ("edwards_Fr", 16, 2, 5, 1, 10)])
 def test_native_fri_snark(gpu, field_name, dim, rs_extra, loc_param, interactions, queries):
     """FRI_snark_prover through the C ABI (libiop_amd/cpp/fri.hpp inside the library) == the oracle prover's transcript."""
     import torch

@@ -2,12 +2,14 @@
 MI355X, through the C ABI: what the stage timings and bench.py run is checked here at the size they run it — sampled values
 against the oracle's point formulas (Horner evaluation, single-coset fold, hashlib digests, the LDT combination at a point),
 whole-vector identities computed on the device (interpolate o evaluate, re-extension of a folded codeword), and the complete
-2^20 Aurora proof accepted by the oracle's independent verifier."""
+2^20 Aurora proof accepted by the oracle's independent verifier.  Configs 2 and 3 (the 2^22-point additive FFT, the FRI SNARK of dimension 22)
+are pinned whole against digests of the oracle's outputs (tests/fullsize_cases.py)."""
 import hashlib
 
 import numpy as np
 import pytest
 
+import fullsize_cases as fc
 import oracle
 from helpers import rand_elems
 
@@ -245,7 +247,8 @@ def test_fri_snark_cfg3_full_size_accepted_by_the_oracle_verifier(env):
     assert len(transcript.MT_roots) == 10
     args = (oracle.FIELD_GF192, dim, rs_extra, loc, interactions, queries)
     assert oracle.fri_snark_verify(*args, transcript.serialize())
-    # the native prover (libiop_amd/cpp/fri.hpp behind iopx_fri_snark_prove) at the same size: the same bytes
+    # the native prover (libiop_amd/cpp/fri.hpp behind iopx_fri_snark_prove) at the same size: the same bytes.  Both provers call the same
+    # kernels, so this pins nothing against the oracle: test_fri_snark_2p22_equals_the_oracle_prover does (the oracle prover's transcript digest)
     assert lib.fri_snark_prove(0, d_coeffs.data_ptr(), params.poly_degree_bound, dim, rs_extra, loc, interactions, queries) == transcript.serialize()
     t = copy.deepcopy(transcript)
     t.query_responses[1] = t.query_responses[1].copy(); t.query_responses[1][0, 0, 1] ^= np.uint64(1)
@@ -369,3 +372,48 @@ def test_fractal_transcript_equals_the_oracle_provers_at_large_sizes(env, log_n)
     assert [r.hex() for r in roots] == want["index_roots"]
     assert len(t) == want["argument_bytes"]
     assert hashlib.blake2b(t, digest_size=32).hexdigest() == want["transcript_blake2b"], "native device transcript differs from the oracle prover's"
+
+
+# ---- whole-output pins for configs 2 and 3 (tests/fullsize_cases.py; digests of the oracle's outputs in tests/golden/oracle_function_digests_large.json) ----
+def _large(key):
+    return fc.load()["large"]["entries"][key]
+
+
+@pytest.mark.parametrize("key", [k.format(m=fc.LARGE_M) for k in fc.TRANSFORMS])
+def test_additive_transform_2p22_equals_the_oracle(env, key):
+    """Config 2 and its neighbours at 2^22: every output of the device FFT / IFFT (Library.additive_FFT / additive_IFFT, as in
+    test_cfg2_full_size_properties) hashes to the oracle's, chunk by chunk."""
+    lib = env[0]
+    err = fc.mismatch(fc.device_transform(lib, key, fc.LARGE_M), _large(key), fc.LARGE_LOG_CHUNK)
+    assert err is None, err
+
+
+@pytest.mark.parametrize("key", sorted(fc.FOLD_CHAINS))
+def test_fri_fold_chain_2p22_equals_the_oracle(env, key):
+    """Config 3's codeword (the device LDE of 2^20 coefficients onto 2^22 points), then every FRI round's fold over the derived domains
+    (localization 2: fused folds [1, 2 x 9]; localization 4: unfused folds over cosets of 16): every word hashes to the oracle's."""
+    lib, torch, dev, ops, _ = env
+    want = _large(key)
+    steps = [want] + want["folds"]
+    seen = []
+
+    def check(i, d_word):
+        err = fc.mismatch(ops.download(d_word), steps[i], fc.LARGE_LOG_CHUNK)
+        assert err is None, "step %d: %s" % (i, err)
+        seen.append(i)
+
+    fc.device_fold_chain(ops, key, fc.LARGE_M, check)
+    assert seen == list(range(len(steps)))
+
+
+@pytest.mark.parametrize("key", [k.format(m=fc.LARGE_M) for k in fc.SNARKS])
+def test_fri_snark_2p22_equals_the_oracle_prover(env, key):
+    """The FRI SNARK at config 3's size, both fields and localization 4: the Python device prover's and the native prover's transcripts
+    both hash to the oracle prover's."""
+    lib, torch, dev, _, _ = env
+    mine, native = fc.device_snarks(lib, torch, dev, key)
+    want = _large(key)
+    err = fc.snark_mismatch(mine, want)
+    assert err is None, "Python device prover: " + err
+    err = fc.snark_mismatch(native, want)
+    assert err is None, "native prover: " + err

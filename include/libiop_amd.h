@@ -191,6 +191,43 @@ int iopx_fp3_multiplicative_generator(uint64_t *gen);
 int iopx_fp3_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 int iopx_fp3_host_pow(const uint64_t *a, uint64_t exponent, uint64_t *out);
 
+/* ---- multiplicative-coset FFT / IFFT / FRI fold / LDT combination over alt_bn128 Fr ------------------ */
+/* The same entries as the edwards_Fr ones above, argument for argument, for libff alt_bn128_Fr (254 bits, 2-adicity 28,
+ * multiplicative generator 5): elements are Fp_model<4> Montgomery words (4 x uint64, R = 2^256), canonical in and out;
+ * log_n <= 28.  `gen` is the generator of the order-2^log_n subgroup, 5^((r - 1) / 2^log_n) (iopx_bn128_subgroup_generator).
+ *   iopx_mul_fft_bn128                  multiplicative_FFT_degree_aware, fft.tcc:236-317
+ *   iopx_mul_ifft_bn128                 multiplicative_IFFT_internal, fft.tcc:343-361
+ *   iopx_mul_ifft_known_degree_bn128_dev IFFT_of_known_degree_over_field_subset, fft.tcc:435-456
+ *   iopx_fri_fold_mul_bn128             multiplicative_evaluate_next_f_i_over_entire_domain, fri_aux.tcc:106-249
+ *   iopx_ldt_combine_bn128_dev          combined_LDT_virtual_oracle::evaluated_contents, multiplicative arm
+ *                                       (ldt_reducer_aux.tcc:104-128); arguments as iopx_ldt_combine_fp3_dev */
+int iopx_mul_fft_bn128_dev(const uint64_t *d_coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen,
+                           const uint64_t *shift, uint64_t *d_out);
+int iopx_mul_fft_bn128(const uint64_t *coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen,
+                       const uint64_t *shift, uint64_t *out);
+int iopx_mul_ifft_bn128_dev(const uint64_t *d_evals, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                            uint64_t *d_out);
+int iopx_mul_ifft_bn128(const uint64_t *evals, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                        uint64_t *out);
+int iopx_mul_ifft_known_degree_bn128_dev(const uint64_t *d_evals, size_t degree, size_t log_n, const uint64_t *gen,
+                                         const uint64_t *shift, uint64_t *d_out);
+int iopx_fri_fold_mul_bn128_dev(const uint64_t *d_f_i, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                                size_t coset_size, const uint64_t *x_i, uint64_t *d_next);
+int iopx_fri_fold_mul_bn128(const uint64_t *f_i, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                            size_t coset_size, const uint64_t *x_i, uint64_t *next);
+int iopx_ldt_combine_bn128_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees,
+                               const uint64_t *random_coefficients, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                               uint64_t *d_out);
+
+/* Host-side scalars of alt_bn128 Fr (no device needed), as the iopx_fp3_* ones; iopx_bn128_from_uint(v) is FieldT(v);
+ * iopx_bn128_host_inverse fails on zero. */
+int iopx_bn128_subgroup_generator(size_t log_order, uint64_t *gen);
+int iopx_bn128_multiplicative_generator(uint64_t *gen);
+int iopx_bn128_from_uint(uint64_t v, uint64_t *out);
+int iopx_bn128_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
+int iopx_bn128_host_pow(const uint64_t *a, uint64_t exponent, uint64_t *out);
+int iopx_bn128_host_inverse(const uint64_t *a, uint64_t *out);
+
 /* ---- FRI fold over GF(2^192) -------------------------------------------------------------------- */
 /* evaluate_next_f_i_over_entire_domain for affine subspaces:
  * libiop/protocols/ldt/fri/fri_aux.tcc:5-34 -> :36-103.  f_i has 2^m evaluations over (basis, shift);

@@ -62,6 +62,9 @@ EXPORTED_SYMBOLS = [
     "iopx_memcpy_d2h_deferrable", "iopx_comm_rccl_unique_id", "iopx_comm_create_rccl", "iopx_comm_create_callbacks", "iopx_comm_create_replay", "iopx_comm_is_replay", "iopx_cold_stats", "iopx_cold_add", "iopx_gf192_mul_halves_dev", "iopx_mul_fft_fp3_windows_dev", "iopx_set_option", "iopx_clear_option", "iopx_get_option", "iopx_comm_destroy", "iopx_comm_rank",
     "iopx_comm_all_gather_dev", "iopx_comm_all_reduce_u64_dev", "iopx_comm_broadcast_dev", "iopx_comm_all_to_all_dev", "iopx_comm_sendrecv_dev", "iopx_comm_stats", "iopx_comm_bind_transforms", "iopx_add_taylor_inv_gf192_dev", "iopx_add_combine_inv_gf192_dev",
     "iopx_interleave_dev", "iopx_gather_rows_dev", "iopx_fri_snark_prove", "iopx_fri_snark_prove_dist", "iopx_add_fft_gf192_dist_dev", "iopx_add_ifft_gf192_dist_dev", "iopx_aurora_prove_dist", "iopx_fractal_index_dist", "iopx_fractal_prove_dist",
+    "iopx_mul_fft_bn128_dev", "iopx_mul_fft_bn128", "iopx_mul_ifft_bn128_dev", "iopx_mul_ifft_bn128", "iopx_mul_ifft_known_degree_bn128_dev",
+    "iopx_fri_fold_mul_bn128_dev", "iopx_fri_fold_mul_bn128", "iopx_ldt_combine_bn128_dev",
+    "iopx_bn128_subgroup_generator", "iopx_bn128_multiplicative_generator", "iopx_bn128_host_mul", "iopx_bn128_host_pow", "iopx_bn128_host_inverse", "iopx_bn128_from_uint",
 ]
 
 
@@ -178,6 +181,20 @@ class Library:
         c.iopx_mul_ifft_known_degree_fp3_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp]
         c.iopx_fri_fold_mul_fp3_dev.argtypes = [_vp, _sz, _u64p, _u64p, _sz, _u64p, _vp]
         c.iopx_fri_fold_mul_fp3.argtypes = [_u64p, _sz, _u64p, _u64p, _sz, _u64p, _u64p]
+        c.iopx_mul_fft_bn128_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp]
+        c.iopx_mul_fft_bn128.argtypes = [_u64p, _sz, _sz, _u64p, _u64p, _u64p]
+        c.iopx_mul_ifft_bn128_dev.argtypes = [_vp, _sz, _u64p, _u64p, _vp]
+        c.iopx_mul_ifft_bn128.argtypes = [_u64p, _sz, _u64p, _u64p, _u64p]
+        c.iopx_mul_ifft_known_degree_bn128_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp]
+        c.iopx_fri_fold_mul_bn128_dev.argtypes = [_vp, _sz, _u64p, _u64p, _sz, _u64p, _vp]
+        c.iopx_fri_fold_mul_bn128.argtypes = [_u64p, _sz, _u64p, _u64p, _sz, _u64p, _u64p]
+        c.iopx_ldt_combine_bn128_dev.argtypes = [ctypes.POINTER(_vp), _sz, ctypes.POINTER(_sz), _u64p, _sz, _u64p, _u64p, _vp]
+        c.iopx_bn128_subgroup_generator.argtypes = [_sz, _u64p]
+        c.iopx_bn128_multiplicative_generator.argtypes = [_u64p]
+        c.iopx_bn128_host_mul.argtypes = [_u64p, _u64p, _u64p]
+        c.iopx_bn128_host_pow.argtypes = [_u64p, ctypes.c_uint64, _u64p]
+        c.iopx_bn128_host_inverse.argtypes = [_u64p, _u64p]
+        c.iopx_bn128_from_uint.argtypes = [ctypes.c_uint64, _u64p]
         c.iopx_merkle_blake2b_dev.argtypes = [ctypes.POINTER(_vp), _sz, _sz, _sz, _sz, ctypes.c_int, _vp, _sz, _vp]
         c.iopx_merkle_blake2b.argtypes = [ctypes.POINTER(_vp), _sz, _sz, _sz, _sz, ctypes.c_int, _vp, _sz, _vp]
         c.iopx_merkle_leaves_blake2b_dev.argtypes = [ctypes.POINTER(_vp), _sz, _sz, _sz, _sz, ctypes.c_int, _vp, _sz, _vp]
@@ -433,6 +450,89 @@ class Library:
                                                  int(coset_size), x.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
         return out
 
+    # ---- multiplicative cosets over alt_bn128 Fr: elements are (count, 4) uint64 Montgomery words (x * 2^256 mod r) ----
+    def bn128_subgroup_generator(self, log_n):
+        """5^((r - 1) / 2^log_n), the generator of the order-2^log_n subgroup (subgroup.tcc:55-59), as (4,) words."""
+        out = np.empty(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_subgroup_generator(int(log_n), out.ctypes.data_as(_u64p)))
+        return out
+
+    def bn128_multiplicative_generator(self):
+        out = np.empty(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_multiplicative_generator(out.ctypes.data_as(_u64p)))
+        return out
+
+    def bn128_host_mul(self, a, b):
+        a, b = _as_u64(a, 4), _as_u64(b, 4)
+        out = np.empty(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_host_mul(a.ctypes.data_as(_u64p), b.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def bn128_host_pow(self, a, exponent):
+        a = _as_u64(a, 4)
+        out = np.empty(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_host_pow(a.ctypes.data_as(_u64p), int(exponent), out.ctypes.data_as(_u64p)))
+        return out
+
+    def bn128_host_inverse(self, a):
+        a = _as_u64(a, 4)
+        out = np.empty(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_host_inverse(a.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def _bn128_log_n(self, n, what):
+        log_n = n.bit_length() - 1
+        if n != 1 << log_n:
+            raise ValueError("%s: %d evaluations is not a power of two" % (what, n))
+        return log_n
+
+    def multiplicative_FFT_bn128(self, poly_coeffs, log_n, shift, gen=None):
+        """multiplicative_FFT(poly_coeffs, multiplicative_coset(2^log_n, shift)) over alt_bn128 Fr — fft.tcc:236-317."""
+        coeffs, shift = _as_u64(poly_coeffs, 4), _as_u64(shift, 4)
+        gen = _as_u64(self.bn128_subgroup_generator(log_n) if gen is None else gen, 4)
+        out = np.empty((1 << log_n, 4), dtype=np.uint64)
+        self._check(self.c.iopx_mul_fft_bn128(coeffs.ctypes.data_as(_u64p), coeffs.shape[0], log_n, gen.ctypes.data_as(_u64p),
+                                              shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def multiplicative_IFFT_bn128(self, evals, shift, gen=None):
+        """multiplicative_IFFT(evals, coset) over alt_bn128 Fr — fft.tcc:343-361."""
+        evals, shift = _as_u64(evals, 4), _as_u64(shift, 4)
+        log_n = self._bn128_log_n(evals.shape[0], "multiplicative IFFT")
+        gen = _as_u64(self.bn128_subgroup_generator(log_n) if gen is None else gen, 4)
+        out = np.empty_like(evals)
+        self._check(self.c.iopx_mul_ifft_bn128(evals.ctypes.data_as(_u64p), log_n, gen.ctypes.data_as(_u64p),
+                                               shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def multiplicative_IFFT_of_known_degree_bn128(self, evals, degree, shift):
+        """IFFT_of_known_degree_over_field_subset, multiplicative overload, over alt_bn128 Fr — fft.tcc:435-456."""
+        evals, shift = _as_u64(evals, 4), _as_u64(shift, 4)
+        log_n = self._bn128_log_n(evals.shape[0], "multiplicative IFFT of known degree")
+        k = max(int(degree) - 1, 0).bit_length()
+        gen = _as_u64(self.bn128_subgroup_generator(log_n), 4)
+        d_in, d_out = self.malloc(evals.nbytes), self.malloc(32 << k)
+        try:
+            self.h2d(d_in, evals)
+            self._check(self.c.iopx_mul_ifft_known_degree_bn128_dev(_vp(d_in), int(degree), log_n, gen.ctypes.data_as(_u64p),
+                                                                    shift.ctypes.data_as(_u64p), _vp(d_out)))
+            out = np.empty((1 << k, 4), dtype=np.uint64)
+            self.d2h(out, d_out)
+        finally:
+            self.free(d_in)
+            self.free(d_out)
+        return out
+
+    def multiplicative_evaluate_next_f_i_bn128(self, f_i_evals, shift, coset_size, x_i, gen=None):
+        """multiplicative_evaluate_next_f_i_over_entire_domain over alt_bn128 Fr — fri_aux.tcc:106-249."""
+        f, shift, x = _as_u64(f_i_evals, 4), _as_u64(shift, 4), _as_u64(x_i, 4)
+        log_n = self._bn128_log_n(f.shape[0], "multiplicative fold")
+        gen = _as_u64(self.bn128_subgroup_generator(log_n) if gen is None else gen, 4)
+        out = np.empty((f.shape[0] // max(int(coset_size), 1), 4), dtype=np.uint64)
+        self._check(self.c.iopx_fri_fold_mul_bn128(f.ctypes.data_as(_u64p), log_n, gen.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p),
+                                                   int(coset_size), x.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
     def merkle_tree(self, oracles, coset_size, domain_type=DOMAIN_ADDITIVE, salts=None):
         """construct_with_leaves_serialized_by_cosets + compute_inner_nodes (merkle_tree.tcc:92-229).
         Returns the (2L-1, 32) uint8 node array in heap order; row 0 is get_root()."""
@@ -660,6 +760,37 @@ class Library:
 
     def ldt_combine_multiplicative(self, evals, degrees, random_coefficients, log_n, gen, shift):
         return self._ldt_combine_host(evals, lambda d, o: self.ldt_combine_multiplicative_dev(d, degrees, random_coefficients, log_n, gen, shift, o))
+
+    def ldt_combine_bn128_dev(self, d_oracles, degrees, random_coefficients, log_n, shift, d_out, gen=None):
+        """combined_LDT_virtual_oracle::evaluated_contents over the alt_bn128 coset shift * <g>, |<g>| = 2^log_n; device pointers."""
+        shift, rc = _as_u64(shift, 4), _as_u64(random_coefficients, 4)
+        gen = _as_u64(self.bn128_subgroup_generator(log_n) if gen is None else gen, 4)
+        if rc.shape[0] != 2 * len(d_oracles):
+            raise ValueError("Expected the nunmber of random coefficients to be twice the number of oracles.")
+        ptrs = (_vp * max(len(d_oracles), 1))(*d_oracles)
+        deg = (_sz * max(len(degrees), 1))(*[int(d) for d in degrees])
+        self._check(self.c.iopx_ldt_combine_bn128_dev(ptrs, len(d_oracles), deg, rc.ctypes.data_as(_u64p), int(log_n),
+                                                      gen.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p), _vp(d_out)))
+
+    def ldt_combine_bn128(self, evals, degrees, random_coefficients, shift, gen=None):
+        """Host-array form of ldt_combine_bn128_dev: evals is a list of (2^log_n, 4) arrays."""
+        evals = [_as_u64(e, 4) for e in evals]
+        n = evals[0].shape[0]
+        for e in evals:
+            if e.shape[0] != n:
+                raise ValueError("Vectors of mismatched size.")
+        log_n = self._bn128_log_n(n, "LDT combination")
+        bufs = [self.malloc(e.nbytes) for e in evals] + [self.malloc(evals[0].nbytes)]
+        try:
+            for b, e in zip(bufs, evals):
+                self.h2d(b, e)
+            self.ldt_combine_bn128_dev(bufs[:-1], degrees, random_coefficients, log_n, shift, bufs[-1], gen)
+            out = np.empty_like(evals[0])
+            self.d2h(out, bufs[-1])
+        finally:
+            for b in bufs:
+                self.free(b)
+        return out
 
     # ---- proof of work (pow.tcc) ----
     def solve_pow(self, challenge, pow_bitlen, poseidon_params=None):

@@ -1,7 +1,7 @@
 // Plain field-element types for C++ callers that do not link libff: 24 raw bytes with the layout of libff::gf192 (three
-// little-endian words, polynomial basis) / libff::edwards_Fr (three Montgomery limbs).  They provide exactly what the mirror asks of
-// a FieldT — construction from an integer, ==, + — through the library's host helpers; a libiop integration uses libff's own types
-// instead.
+// little-endian words, polynomial basis) / libff::edwards_Fr (three Montgomery limbs), 32 with that of libff::alt_bn128_Fr (four).
+// They provide what the mirror asks of a FieldT — construction from an integer, ==, + — through the library's host helpers; a libiop
+// integration uses libff's own types instead.
 #pragma once
 #include "iop.hpp"
 
@@ -27,5 +27,15 @@ struct edwards_Fr_element {
     edwards_Fr_element operator+(const edwards_Fr_element &o) const { edwards_Fr_element r; check(iopx_fp3_host_add(w, o.w, r.w)); return r; }
 };
 template<> struct field_kind<edwards_Fr_element> { static const field_subset_type type = multiplicative_coset_type; };
+
+// 32 raw bytes with the layout of libff::alt_bn128_Fr (four Montgomery limbs, R = 2^256)
+struct alt_bn128_Fr_element {
+    uint64_t w[4];
+    alt_bn128_Fr_element() : w{ 0, 0, 0, 0 } {}
+    explicit alt_bn128_Fr_element(uint64_t v) { check(iopx_bn128_from_uint(v, w)); }
+    bool operator==(const alt_bn128_Fr_element &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
+    bool operator!=(const alt_bn128_Fr_element &o) const { return !(*this == o); }
+};
+template<> struct field_kind<alt_bn128_Fr_element> { static const field_subset_type type = multiplicative_coset_type; };
 
 } // namespace libiop_amd

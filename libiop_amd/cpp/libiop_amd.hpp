@@ -99,13 +99,22 @@ public:
 };
 
 // libiop/algebra/field_subset/subgroup.hpp — multiplicative_coset: order 2^k, generator g, shift; index i <-> shift * g^i.
-// FieldT has libff::edwards_Fr's layout (three uint64 Montgomery words); the subgroup generator multiplicative_generator^
-// ((p-1)/order) (subgroup.tcc:55-59) and the few scalar products of the metadata come from the library's host-side helpers, so
-// the mirror asks nothing of FieldT beyond its bytes.
+// FieldT has libff::edwards_Fr's layout (three uint64 Montgomery words) or alt_bn128_Fr's (four); the subgroup generator
+// multiplicative_generator^((p-1)/order) (subgroup.tcc:55-59) and the few scalar products of the metadata come from the library's
+// host-side helpers for that field, so the mirror asks nothing of FieldT beyond its bytes.
 template<typename FieldT>
 class multiplicative_coset {
     std::size_t order_;
     FieldT g_, shift_;
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32, "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
+    static constexpr bool bn128 = sizeof(FieldT) == 32;
+    static FieldT host_mul(const FieldT &a, const FieldT &b)
+    {
+        FieldT r;
+        check(bn128 ? iopx_bn128_host_mul(detail::words(&a), detail::words(&b), detail::words(&r))
+                    : iopx_fp3_host_mul(detail::words(&a), detail::words(&b), detail::words(&r)));
+        return r;
+    }
 public:
     multiplicative_coset() : order_(1) {}
     multiplicative_coset(std::size_t order, const FieldT &generator, const FieldT &shift) : order_(order), g_(generator), shift_(shift)
@@ -114,9 +123,9 @@ public:
     }
     multiplicative_coset(std::size_t order, const FieldT &shift) : order_(order), shift_(shift)        // subgroup.tcc:33-75, 199-215
     {
-        static_assert(sizeof(FieldT) == 24, "libiop_amd accelerates prime fields with libff::edwards_Fr's layout");
         if (order == 0 || (order & (order - 1))) throw std::invalid_argument("The order of the subgroup must be a power of two.");
-        check(iopx_fp3_subgroup_generator(detail::log2_ceil(order), detail::words(&g_)));
+        check(bn128 ? iopx_bn128_subgroup_generator(detail::log2_ceil(order), detail::words(&g_))
+                    : iopx_fp3_subgroup_generator(detail::log2_ceil(order), detail::words(&g_)));
     }
     std::size_t num_elements() const { return order_; }
     std::size_t dimension() const { return detail::log2_ceil(order_); }
@@ -125,17 +134,15 @@ public:
     FieldT element_by_index(std::size_t index) const                                       // shift * g^index
     {
         if (index >= order_) throw std::invalid_argument("element index out of bounds");
-        FieldT p, r;
-        check(iopx_fp3_host_pow(detail::words(&g_), index, detail::words(&p)));
-        check(iopx_fp3_host_mul(detail::words(&shift_), detail::words(&p), detail::words(&r)));
-        return r;
+        FieldT p;
+        check(bn128 ? iopx_bn128_host_pow(detail::words(&g_), index, detail::words(&p)) : iopx_fp3_host_pow(detail::words(&g_), index, detail::words(&p)));
+        return host_mul(shift_, p);
     }
     FieldT element_outside_of_subset() const                                               // subgroup.tcc:311-315
     {
-        FieldT gen, r;
-        check(iopx_fp3_multiplicative_generator(detail::words(&gen)));
-        check(iopx_fp3_host_mul(detail::words(&shift_), detail::words(&gen), detail::words(&r)));
-        return r;
+        FieldT gen;
+        check(bn128 ? iopx_bn128_multiplicative_generator(detail::words(&gen)) : iopx_fp3_multiplicative_generator(detail::words(&gen)));
+        return host_mul(shift_, gen);
     }
     // subgroup.tcc:149-173
     std::size_t reindex_by_subgroup(std::size_t reindex_subgroup_dim, std::size_t index) const
@@ -273,15 +280,21 @@ std::vector<FieldT> multiplicative_IFFT(const std::vector<FieldT> &evals, const 
 template<typename FieldT>
 std::vector<FieldT> FFT_over_field_subset(const std::vector<FieldT> coeffs, field_subset<FieldT> domain)
 {
-    if (domain.type() == multiplicative_coset_type) return multiplicative_FFT<FieldT>(coeffs, domain.coset());
-    return additive_FFT<FieldT>(coeffs, domain.subspace());
+    if constexpr (sizeof(FieldT) == 32) return multiplicative_FFT<FieldT>(coeffs, domain.coset());     // alt_bn128_Fr: cosets only
+    else {
+        if (domain.type() == multiplicative_coset_type) return multiplicative_FFT<FieldT>(coeffs, domain.coset());
+        return additive_FFT<FieldT>(coeffs, domain.subspace());
+    }
 }
 
 template<typename FieldT>
 std::vector<FieldT> IFFT_over_field_subset(const std::vector<FieldT> evals, field_subset<FieldT> domain)
 {
-    if (domain.type() == multiplicative_coset_type) return multiplicative_IFFT<FieldT>(evals, domain.coset());
-    return additive_IFFT<FieldT>(evals, domain.subspace());
+    if constexpr (sizeof(FieldT) == 32) return multiplicative_IFFT<FieldT>(evals, domain.coset());
+    else {
+        if (domain.type() == multiplicative_coset_type) return multiplicative_IFFT<FieldT>(evals, domain.coset());
+        return additive_IFFT<FieldT>(evals, domain.subspace());
+    }
 }
 
 // fft.tcc:435-475: the multiplicative arm interpolates every (n / 2^ceil(log2 degree))-th evaluation over the sub-coset of
@@ -297,8 +310,11 @@ std::vector<FieldT> IFFT_of_known_degree_over_field_subset(const std::vector<Fie
         for (std::size_t i = 0; i < domain.num_elements(); i += freq) sub.emplace_back(evals[i]);
         return multiplicative_IFFT<FieldT>(sub, minimal.coset());
     }
-    const std::vector<FieldT> head(evals.begin(), evals.begin() + pow2);
-    return additive_IFFT<FieldT>(head, minimal.subspace());
+    if constexpr (sizeof(FieldT) == 32) throw std::invalid_argument("alt_bn128_Fr: multiplicative cosets only");
+    else {
+        const std::vector<FieldT> head(evals.begin(), evals.begin() + pow2);
+        return additive_IFFT<FieldT>(head, minimal.subspace());
+    }
 }
 
 // ---- FRI fold (libiop/protocols/ldt/fri/fri_aux.hpp:23-28; dispatch fri_aux.tcc:5-34) -------------------
@@ -324,7 +340,9 @@ std::shared_ptr<std::vector<FieldT>> evaluate_next_f_i_over_entire_domain(
     const std::shared_ptr<std::vector<FieldT>> &f_i_evals, const field_subset<FieldT> &f_i_domain,
     const std::size_t coset_size, const FieldT x_i)
 {
-    if (f_i_domain.type() == affine_subspace_type) return additive_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
+    if constexpr (sizeof(FieldT) != 32) {
+        if (f_i_domain.type() == affine_subspace_type) return additive_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
+    }
     if (f_i_domain.type() == multiplicative_coset_type) return multiplicative_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
     throw std::invalid_argument("f_i_domain is of unsupported domain type");               // fri_aux.tcc:33
 }

@@ -77,11 +77,16 @@ std::vector<FieldT> additive_IFFT(const std::vector<FieldT> &evals, const Subspa
 template<typename FieldT, typename Coset>
 std::vector<FieldT> multiplicative_FFT(const std::vector<FieldT> &poly_coeffs, const Coset &domain)
 {
-    static_assert(sizeof(FieldT) == 24, "libiop_amd accelerates prime fields with libff::edwards_Fr's layout (three Montgomery words)");
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32,
+                  "libiop_amd accelerates prime fields with libff::edwards_Fr's (three) or alt_bn128_Fr's (four Montgomery words) layout");
     const FieldT g = domain.generator(), shift = domain.shift();
     std::vector<FieldT> out(domain.num_elements());
-    check(iopx_mul_fft_fp3(detail::words(poly_coeffs.data()), poly_coeffs.size(), domain.dimension(), detail::words(&g),
-                           detail::words(&shift), detail::words(out.data())));
+    if constexpr (sizeof(FieldT) == 24)
+        check(iopx_mul_fft_fp3(detail::words(poly_coeffs.data()), poly_coeffs.size(), domain.dimension(), detail::words(&g),
+                               detail::words(&shift), detail::words(out.data())));
+    else
+        check(iopx_mul_fft_bn128(detail::words(poly_coeffs.data()), poly_coeffs.size(), domain.dimension(), detail::words(&g),
+                                 detail::words(&shift), detail::words(out.data())));
     return out;
 }
 
@@ -89,12 +94,17 @@ std::vector<FieldT> multiplicative_FFT(const std::vector<FieldT> &poly_coeffs, c
 template<typename FieldT, typename Coset>
 std::vector<FieldT> multiplicative_IFFT(const std::vector<FieldT> &evals, const Coset &domain)
 {
-    static_assert(sizeof(FieldT) == 24, "libiop_amd accelerates prime fields with libff::edwards_Fr's layout (three Montgomery words)");
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32,
+                  "libiop_amd accelerates prime fields with libff::edwards_Fr's (three) or alt_bn128_Fr's (four Montgomery words) layout");
     if (evals.size() != domain.num_elements()) throw std::invalid_argument("multiplicative_IFFT: evaluation count != domain size");
     const FieldT g = domain.generator(), shift = domain.shift();
     std::vector<FieldT> out(domain.num_elements());
-    check(iopx_mul_ifft_fp3(detail::words(evals.data()), domain.dimension(), detail::words(&g), detail::words(&shift),
-                            detail::words(out.data())));
+    if constexpr (sizeof(FieldT) == 24)
+        check(iopx_mul_ifft_fp3(detail::words(evals.data()), domain.dimension(), detail::words(&g), detail::words(&shift),
+                                detail::words(out.data())));
+    else
+        check(iopx_mul_ifft_bn128(detail::words(evals.data()), domain.dimension(), detail::words(&g), detail::words(&shift),
+                                  detail::words(out.data())));
     return out;
 }
 
@@ -118,12 +128,17 @@ template<typename FieldT, typename Domain>
 std::shared_ptr<std::vector<FieldT>> multiplicative_evaluate_next_f_i_over_entire_domain(
     const std::shared_ptr<std::vector<FieldT>> &f_i_evals, const Domain &f_i_domain, const std::size_t coset_size, const FieldT x_i)
 {
-    static_assert(sizeof(FieldT) == 24, "libiop_amd accelerates prime fields with libff::edwards_Fr's layout (three Montgomery words)");
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32,
+                  "libiop_amd accelerates prime fields with libff::edwards_Fr's (three) or alt_bn128_Fr's (four Montgomery words) layout");
     if (f_i_evals->size() != f_i_domain.num_elements()) throw std::invalid_argument("f_i size != domain size");
     const FieldT g = f_i_domain.generator(), shift = f_i_domain.shift();
     auto next = std::make_shared<std::vector<FieldT>>(f_i_domain.num_elements() / coset_size);
-    check(iopx_fri_fold_mul_fp3(detail::words(f_i_evals->data()), f_i_domain.dimension(), detail::words(&g), detail::words(&shift),
-                                coset_size, detail::words(&x_i), detail::words(next->data())));
+    if constexpr (sizeof(FieldT) == 24)
+        check(iopx_fri_fold_mul_fp3(detail::words(f_i_evals->data()), f_i_domain.dimension(), detail::words(&g), detail::words(&shift),
+                                    coset_size, detail::words(&x_i), detail::words(next->data())));
+    else
+        check(iopx_fri_fold_mul_bn128(detail::words(f_i_evals->data()), f_i_domain.dimension(), detail::words(&g), detail::words(&shift),
+                                      coset_size, detail::words(&x_i), detail::words(next->data())));
     return next;
 }
 
@@ -151,7 +166,11 @@ std::shared_ptr<std::vector<FieldT>> ldt_combine(const std::vector<std::shared_p
                                                  const std::vector<std::size_t> &input_oracle_degrees, const std::vector<FieldT> &coefficients,
                                                  const Domain &codeword_domain, bool multiplicative)
 {
-    static_assert(sizeof(FieldT) == 24, "FieldT must have a 24-byte layout (libff::gf192 / libff::edwards_Fr)");
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32,
+                  "FieldT must have a 24-byte (libff::gf192 / libff::edwards_Fr) or, multiplicative only, a 32-byte (alt_bn128_Fr) layout");
+    if constexpr (sizeof(FieldT) == 32) {
+        if (!multiplicative) throw std::invalid_argument("ldt_combine: a 32-byte field has multiplicative domains only");
+    }
     const std::size_t n = codeword_domain.num_elements();
     std::vector<void *> bufs(constituents.size() + 1, nullptr);
     auto result = std::make_shared<std::vector<FieldT>>(n);
@@ -161,12 +180,17 @@ std::shared_ptr<std::vector<FieldT>> ldt_combine(const std::vector<std::shared_p
     for (std::size_t k = 0; k + 1 < bufs.size() && rc == IOPX_OK; ++k) rc = iopx_memcpy_h2d(bufs[k], constituents[k]->data(), n * sizeof(FieldT));
     if (rc == IOPX_OK && multiplicative) {                                                  // ldt_reducer_aux.tcc:104-128
         const FieldT g = codeword_domain.generator();
-        rc = iopx_ldt_combine_fp3_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
-                                      codeword_domain.dimension(), detail::words(&g), detail::words(&shift), (uint64_t *)bufs.back());
+        if constexpr (sizeof(FieldT) == 24)
+            rc = iopx_ldt_combine_fp3_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
+                                          codeword_domain.dimension(), detail::words(&g), detail::words(&shift), (uint64_t *)bufs.back());
+        else
+            rc = iopx_ldt_combine_bn128_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
+                                            codeword_domain.dimension(), detail::words(&g), detail::words(&shift), (uint64_t *)bufs.back());
     } else if (rc == IOPX_OK) {                                                             // :78-103
-        rc = iopx_ldt_combine_gf192_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
-                                        detail::words(codeword_domain.basis().data()), codeword_domain.dimension(), detail::words(&shift),
-                                        (uint64_t *)bufs.back());
+        if constexpr (sizeof(FieldT) == 24)
+            rc = iopx_ldt_combine_gf192_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
+                                            detail::words(codeword_domain.basis().data()), codeword_domain.dimension(), detail::words(&shift),
+                                            (uint64_t *)bufs.back());
     }
     if (rc == IOPX_OK) rc = iopx_memcpy_d2h(result->data(), bufs.back(), n * sizeof(FieldT));
     for (void *b : bufs) if (b) iopx_free(b);

@@ -22,226 +22,9 @@
 #include <vector>
 #include "runtime.h"
 #include "poseidon_tables.h"
+#include "bn254_dev.h"
 
 namespace iopx {
-
-// ---- alt_bn128 Fr in radix 2^29 ----------------------------------------------------------------------------------
-// gfx950's widest integer multiply is v_mad_u64_u32 (32 x 32 + 64 -> 64, no carry-in).  Nine 29-bit limbs leave enough
-// headroom in that 64-bit accumulator for a whole column of a Montgomery product (nine a_i * b_j and nine m_i * p_j
-// terms), so a product is 162 multiply-adds and no carry chains; additions are limb-wise with no carries at all.
-// Internally an element x is any representative of x * 2^261 mod p below 2^257.5 ("R261 form"); the library's
-// boundary stays libff's 4 x 64-bit Montgomery words (x * 2^256 mod p, canonical), converted on load / store.
-struct bn9 {
-    uint32_t l[9];
-};
-
-#define BN9_MASK 0x1fffffffu
-__device__ static const uint32_t BN9_P[9] = { 0x10000001u, 0x1f0fac9fu, 0x0e5c2450u, 0x07d090f3u, 0x1585d283u, 0x02db40c0u, 0x00a6e141u, 0x0e5c2634u, 0x0030644eu };
-#define BN9_INV 0x0fffffffu                  // -p^-1 mod 2^29
-// 2^e mod p as plain 29-bit limbs: multiplying by them (one Montgomery product, / 2^261) moves between the forms
-__device__ static const uint32_t BN9_C256[9] = { 0x0ffffffbu, 0x04b1a0e2u, 0x18334a6bu, 0x18ed2b3eu, 0x1462e36fu, 0x11b7bc3cu, 0x1cbd99bau, 0x183340fbu, 0x000e0a77u };
-__device__ static const uint32_t BN9_C266[9] = { 0x0fffead7u, 0x1d5444f4u, 0x04438aa5u, 0x03b4d096u, 0x134c84dau, 0x0e92d304u, 0x14cb95b3u, 0x041b9d3du, 0x00058003u };
-__device__ static const uint32_t BN9_C517[9] = { 0x142db4dfu, 0x19d6990eu, 0x1472f48cu, 0x06dbe7e3u, 0x0b84d579u, 0x10f9faf7u, 0x121f4380u, 0x17a112deu, 0x001275c7u };
-__device__ static const uint32_t BN9_C522[9] = { 0x05b69bd4u, 0x06170a5au, 0x020cddceu, 0x1db6310bu, 0x0e54d0ffu, 0x1cf855e3u, 0x1c15e103u, 0x07d09161u, 0x000a054au };
-__device__ static const uint32_t BN_P32[8] = { 0xf0000001u, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u };
-
-__device__ __forceinline__ bn9 bn9_const(const uint32_t (&c)[9])
-{
-    bn9 r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.l[i] = c[i];
-    return r;
-}
-
-__device__ __forceinline__ bn9 bn9_zero()
-{
-    bn9 r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.l[i] = 0;
-    return r;
-}
-
-// 256-bit integer (4 little-endian 64-bit words) -> nine 29-bit limbs
-__device__ __forceinline__ bn9 bn9_unpack(const uint64_t *q)
-{
-    uint32_t w[9];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { const uint64_t v = q[i]; w[2 * i] = (uint32_t)v; w[2 * i + 1] = (uint32_t)(v >> 32); }
-    w[8] = 0;
-    bn9 r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const int bit = 29 * i, wi = bit >> 5, sh = bit & 31;
-        const uint64_t two = (uint64_t)w[wi] | ((uint64_t)w[wi + 1 > 8 ? 8 : wi + 1] << 32);
-        r.l[i] = (uint32_t)(two >> sh) & BN9_MASK;
-    }
-    return r;
-}
-
-// limb-wise sum; no carries (see the headroom rules at bn9_mul)
-__device__ __forceinline__ bn9 bn9_add(const bn9 &a, const bn9 &b)
-{
-    bn9 r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] + b.l[i];
-    return r;
-}
-
-// carry propagation: same value, limbs 0..7 back below 2^29
-__device__ __forceinline__ bn9 bn9_norm(const bn9 &a)
-{
-    bn9 r;
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t v = a.l[i] + c;
-        r.l[i] = v & BN9_MASK;
-        c = v >> 29;
-    }
-    r.l[8] = a.l[8] + c;
-    return r;
-}
-
-// 2^254 - p, plain limbs: v = q * 2^254 + rem is congruent to q * (2^254 - p) + rem
-__device__ static const uint32_t BN9_C254[9] = { 0x0fffffffu, 0x00f05360u, 0x11a3dbafu, 0x182f6f0cu, 0x0a7a2d7cu, 0x1d24bf3fu, 0x1f591ebeu, 0x11a3d9cbu, 0x000f9bb1u };
-
-// Weak reduction of any limb vector (limbs up to 2^32 - 1): same residue, value below 2^254 + (v >> 254) * 0.25 * 2^254 and
-// normalised limbs.  Used where elements are only ever added (the near-MDS layers), so that they stay below 2^256.
-__device__ __forceinline__ bn9 bn9_reduce(const bn9 &a)
-{
-    bn9 n = bn9_norm(a);
-    const uint32_t q = n.l[8] >> 22;
-    n.l[8] &= 0x3fffffu;
-    bn9 r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        acc += (uint64_t)q * BN9_C254[i] + n.l[i];
-        r.l[i] = (uint32_t)acc & BN9_MASK;
-        acc >>= 29;
-    }
-    r.l[8] = (uint32_t)acc + q * BN9_C254[8] + n.l[8];
-    return r;
-}
-
-// Montgomery reduction interleaved with the column sums (product scanning).  On entry to column k `acc` holds the
-// carry of column k - 1; COLUMN(k) adds the operand products, then the m_i * p_j terms.
-#define BN9_REDUCE_LOW(k)                                                                 \
-    {                                                                                     \
-        _Pragma("unroll") for (int i = 0; i < (k); ++i) acc += (uint64_t)m[i] * BN9_P[(k) - i]; \
-        m[k] = ((uint32_t)acc * BN9_INV) & BN9_MASK;                                      \
-        acc += (uint64_t)m[k] * BN9_P[0];                                                 \
-        acc >>= 29;                                                                       \
-    }
-#define BN9_REDUCE_HIGH(k)                                                                \
-    {                                                                                     \
-        _Pragma("unroll") for (int i = (k) - 8; i < 9; ++i) acc += (uint64_t)m[i] * BN9_P[(k) - i]; \
-        r.l[(k) - 9] = (uint32_t)acc & BN9_MASK;                                          \
-        acc >>= 29;                                                                       \
-    }
-
-// sum_n a[n] * b[n] * 2^-261 mod p for N operand pairs reduced together.
-// Headroom: every column must stay below 2^64, i.e. N * 9 * max(a limb) * max(b limb) + 9 * 2^58 < 2^64:
-//   N = 1: both operands may have limbs up to 2^30 (one carry-less addition each), or one up to 2^31 against a normalised one;
-//   N = 3: one side normalised (< 2^29), the other up to 2^30;   N = 4: both normalised.
-// Values: inputs below 2^257.5 give a result below 2^255 with normalised limbs.
-template<int N>
-__device__ __forceinline__ bn9 bn9_dot(const bn9 (&a)[N], const bn9 (&b)[N])
-{
-    uint32_t m[9];
-    bn9 r;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-#pragma unroll
-            for (int i = 0; i <= k; ++i) acc += (uint64_t)a[n].l[i] * b[n].l[k - i];
-        }
-        BN9_REDUCE_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; ++k) {
-#pragma unroll
-        for (int n = 0; n < N; ++n) {
-#pragma unroll
-            for (int i = k - 8; i < 9; ++i) acc += (uint64_t)a[n].l[i] * b[n].l[k - i];
-        }
-        BN9_REDUCE_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-}
-
-__device__ __forceinline__ bn9 bn9_mul(const bn9 &a, const bn9 &b)
-{
-    const bn9 aa[1] = { a }, bb[1] = { b };
-    return bn9_dot<1>(aa, bb);
-}
-
-// a * a * 2^-261: the cross terms once, against the doubled operand (45 products instead of 81); limbs of a up to 2^30
-__device__ __forceinline__ bn9 bn9_sqr(const bn9 &a)
-{
-    uint32_t m[9], d[9];
-    bn9 r;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) d[i] = a.l[i] << 1;
-    uint64_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-#pragma unroll
-        for (int i = 0; 2 * i < k; ++i) acc += (uint64_t)a.l[i] * d[k - i];
-        if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
-        BN9_REDUCE_LOW(k)
-    }
-#pragma unroll
-    for (int k = 9; k < 17; ++k) {
-#pragma unroll
-        for (int i = k - 8; 2 * i < k; ++i) acc += (uint64_t)a.l[i] * d[k - i];
-        if ((k & 1) == 0) acc += (uint64_t)a.l[k / 2] * a.l[k / 2];
-        BN9_REDUCE_HIGH(k)
-    }
-    r.l[8] = (uint32_t)acc;
-    return r;
-}
-
-// libff words (x * 2^256, canonical) -> R261 form
-__device__ __forceinline__ bn9 bn9_load_mont(const uint64_t *p, size_t idx)
-{
-    return bn9_mul(bn9_unpack(p + 4 * idx), bn9_const(BN9_C266));
-}
-
-// value below 2^255 with normalised limbs -> canonical 4 x 64-bit words
-__device__ __forceinline__ void bn9_store_canonical(uint64_t *q, const bn9 &y)
-{
-    uint32_t w[8], d[8];
-    uint64_t acc = 0;
-    int bits = 0, wi = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        acc |= (uint64_t)y.l[i] << bits;
-        bits += 29;
-        if (bits >= 32 && wi < 8) { w[wi++] = (uint32_t)acc; acc >>= 32; bits -= 32; }
-    }
-    uint64_t borrow = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint64_t t = (uint64_t)w[i] - BN_P32[i] - borrow;
-        d[i] = (uint32_t)t;
-        borrow = (t >> 32) & 1;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = borrow ? w[2 * i] : d[2 * i], hi = borrow ? w[2 * i + 1] : d[2 * i + 1];
-        q[i] = (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-}
-
-// R261 form (any representative) -> libff words
-__device__ __forceinline__ void bn9_store_mont(uint64_t *p, size_t idx, const bn9 &x)
-{
-    bn9_store_canonical(p + 4 * idx, bn9_mul(x, bn9_const(BN9_C256)));
-}
 
 // device copy of a parameter set: ark[(R_F + R_P) * t] then mds[t * t], nine 29-bit limbs each, R261 form
 struct PoseidonDev {

@@ -177,6 +177,7 @@ int side_stream_select(int k);      // -1: back to the main stream
 int side_stream_join(int k);
 int side_stream_current();
 void clear_mul_plans();
+void clear_bn128_plans();         // fft_bn128.hip: the alt_bn128 twiddle caches
 void clear_dist_plans();           // fft_add_dist.hip: the sharded transforms' per-rank twist tables
 void clear_poseidon_sets();
 

@@ -1,6 +1,6 @@
 // alt_bn128 Fr (r = 21888242871839275222246405745257275088548364400416034343698204186575808495617) in radix 2^29 for
-// gfx950: shared by the Poseidon kernels (poseidon_bn128.hip) and the multiplicative FFT / FRI fold / LDT combination
-// (fft_bn128.hip).
+// gfx950: shared by the Poseidon kernels (poseidon_bn128.hip) and the multiplicative FFT / FRI fold (fft_mul.hip) and LDT
+// combination (ldt_reducer.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -223,6 +223,60 @@ __device__ __forceinline__ void bn9_store_canonical(uint64_t *q, const bn9 &y)
 __device__ __forceinline__ void bn9_store_mont(uint64_t *p, size_t idx, const bn9 &x)
 {
     bn9_store_canonical(p + 4 * idx, bn9_mul(x, bn9_const(BN9_C256)));
+}
+
+// ---- weak values in the library's x * 2^256 form: the multiplicative-coset kernels (fft_mul.hip, ldt_reducer.hip) ------
+// Elements are libff Fp_model<4> Montgomery words (x * 2^256 mod r, four little-endian uint64, canonical at the boundary).
+// Those kernels keep data in that form throughout and every multiplier (twiddles, shift powers, n^-1, 1/2, fold and LDT
+// constants) in "table form" t * 2^261 (hbn::table_form), so x 2^256 * t 2^261 / 2^261 = x t 2^256 and no conversion is ever
+// needed.  Between operations a value is any representative below 2^256 with normalised limbs ("weak"); sums and differences
+// are brought back below 2^256 by bn9_reduce, products of weak values are below 2r.  Kernels store canonical words.
+
+// 2^261 mod r, plain limbs: a product with it maps a weak x * 2^256 value to a representative below 2r of the same residue
+__device__ static const uint32_t BN9_C261[9] = { 0x0fffff57u, 0x1ea70ab4u, 0x052c068bu, 0x17504f49u, 0x0aa8075bu, 0x1d4240ceu, 0x11d54c07u, 0x052ac7a8u, 0x000dc836u };
+// 8r with a 2^29 borrowed into limbs 0..7 from the limb above: limbs 0..7 in [2^29, 2^30), limb 8 above 2^24, so that
+// 8r - b is limb-wise non-negative for any weak b (normalised limbs, value below 2^256)
+__device__ static const uint32_t BN9_8R[9] = { 0x20000008u, 0x387d64fbu, 0x32e12286u, 0x3e84879au, 0x2c2e9418u, 0x36da0604u, 0x25370a07u, 0x32e1319fu, 0x01832272u };
+
+__device__ __forceinline__ bn9 bnw_load(const uint64_t *__restrict__ p, size_t idx) { return bn9_unpack(p + 4 * idx); }
+
+// weak value (normalised limbs, below 2^256) -> four words, no reduction
+__device__ __forceinline__ void bnw_pack(uint64_t *q, const bn9 &y)
+{
+    uint32_t w[8];
+    uint64_t acc = 0;
+    int bits = 0, wi = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        acc |= (uint64_t)y.l[i] << bits;
+        bits += 29;
+        if (bits >= 32 && wi < 8) { w[wi++] = (uint32_t)acc; acc >>= 32; bits -= 32; }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] = (uint64_t)w[2 * i] | ((uint64_t)w[2 * i + 1] << 32);
+}
+
+// weak -> canonical words
+__device__ __forceinline__ void bnw_store(uint64_t *p, size_t idx, const bn9 &v) { bn9_store_canonical(p + 4 * idx, bn9_mul(v, bn9_const(BN9_C261))); }
+// a product (below 2r) -> canonical words
+__device__ __forceinline__ void bnw_store_product(uint64_t *p, size_t idx, const bn9 &v) { bn9_store_canonical(p + 4 * idx, v); }
+
+__device__ __forceinline__ bn9 bnw_add(const bn9 &a, const bn9 &b) { return bn9_reduce(bn9_add(a, b)); }
+
+__device__ __forceinline__ bn9 bnw_sub(const bn9 &a, const bn9 &b)
+{
+    bn9 r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.l[i] = a.l[i] + BN9_8R[i] - b.l[i];
+    return bn9_reduce(r);
+}
+
+// (a, b) <- (a + w b, a - w b)   (fft.tcc:303-309); w in table form
+__device__ __forceinline__ void bnw_bfly(bn9 &a, bn9 &b, const bn9 &w)
+{
+    const bn9 t = bn9_mul(b, w);
+    b = bnw_sub(a, t);
+    a = bnw_add(a, t);
 }
 
 } // namespace iopx

@@ -10,17 +10,20 @@
 //     (exponentiation.tcc:3-19); x_j^e is the product over the set bits of e.  The power table is (m + 1) elements per
 //     exponent bit; bits of j above the workgroup's 256 positions are wave-uniform.
 //   * multiplicative coset: c * shift^e * (g^e)^j from a two-level power table (one product), as the reference's running
-//     product (:104-128) yields.
+//     product (:104-128) yields; one host implementation for both prime fields (edwards_Fr, alt_bn128 Fr), one kernel per field.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
 #include <vector>
+#include "bn254_dev.h"
+#include "bn254_host.h"
 #include "gf192_dev.h"
 #include "gf192_host.h"
 #include "fp3_dev.h"
 #include "fp3_host.h"
+#include "mul_field.h"
 #include "runtime.h"
 
 namespace iopx {
@@ -144,12 +147,13 @@ __global__ void __launch_bounds__(256) k_ldt_combine_add_slots(LdtSlotParams q)
     }
 }
 
+// the multiplicative arm, both prime fields: out[j] = sum_o (c_o + c'_o shift^e_o (g^e_o)^j) f_o[j]   (ldt_reducer_aux.tcc:104-128)
 struct LdtFpParams {
     const uint64_t *const *oracles; // device array of num_oracles device pointers
     const uint64_t *const *hi;      // per oracle: hi table (nullptr = maximal)
     const uint64_t *const *lo;
     uint64_t *out;
-    const uint64_t *coef;           // per oracle: c[k]
+    const uint64_t *coef;           // per oracle: c[k], table form
     size_t n;
     int num_oracles;
 };
@@ -171,6 +175,21 @@ __global__ void __launch_bounds__(256) k_ldt_combine_fp(LdtFpParams p)
             acc = fp_add(acc, fp_redc(w));
         }
         fp_store(p.out, j, acc);
+    }
+}
+
+// the same over alt_bn128 Fr (bn254_dev.h): weak values, one product at a time
+__global__ void __launch_bounds__(256) k_bn_ldt_combine(LdtFpParams p)
+{
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.n; j += (size_t)gridDim.x * blockDim.x) {
+        bn9 acc = bn9_zero();
+        for (int o = 0; o < p.num_oracles; ++o) {
+            bn9 c = bnw_load(p.coef, o);
+            const uint64_t *hi = p.hi[o];
+            if (hi) c = bnw_add(c, bn9_mul(bnw_load(hi, j >> 12), bnw_load(p.lo[o], j & 4095)));
+            acc = bnw_add(acc, bn9_mul(c, bnw_load(p.oracles[o], j)));
+        }
+        bnw_store(p.out, j, acc);
     }
 }
 
@@ -200,6 +219,61 @@ static int ldt_plan(const size_t *degrees, size_t num, LdtPlan *pl)
         else pl->shifted.push_back(0);
         pl->expo.push_back(pl->max_degree - degrees[k]);
     }
+    return IOPX_OK;
+}
+
+// the multiplicative arm, both prime fields (mul_field.h)
+template<class Field>
+static int ldt_combine_mul_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees, const uint64_t *random_coefficients,
+                               size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out,
+                               void (*kernel)(LdtFpParams), const char *label)
+{
+    typedef typename Field::H H;
+    const size_t words = Field::WORDS;
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!d_oracles || !random_coefficients || !d_out || !gen || !shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (log_n > (size_t)Field::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, Field::NAME);
+    LdtPlan pl;
+    if ((rc = ldt_plan(degrees, num_oracles, &pl)) != IOPX_OK) return rc;
+    auto coef = [&](size_t t) { return t ? H::from_words(random_coefficients + words * (t - 1)) : H::one(); };
+    const H g = H::from_words(gen), s = H::from_words(shift);
+    std::vector<uint64_t> hcoef;
+    std::vector<std::unique_ptr<TmpBuf>> tabs;
+    std::vector<const uint64_t *> hhi(num_oracles, nullptr), hlo(num_oracles, nullptr);
+    for (size_t k = 0; k < num_oracles; ++k) {
+        const H a = coef(pl.own[k]).table_form();          // multipliers are uploaded in the device's table form
+        hcoef.insert(hcoef.end(), a.w, a.w + words);
+        if (!pl.shifted[k]) continue;
+        // cur_bump_factor = c[num + i] * shift^e, multiplied by g^e per position (ldt_reducer_aux.tcc:112-126)
+        tabs.emplace_back(new TmpBuf());
+        tabs.emplace_back(new TmpBuf());
+        TmpBuf &hi = *tabs[tabs.size() - 2], &lo = *tabs[tabs.size() - 1];
+        // the random coefficient rides on the hi half (rebuilt per call); the lo half depends on the degree gap and the domain only
+        if ((rc = build_two_level(g.pow(pl.expo[k]), coef(pl.shifted[k]) * s.pow(pl.expo[k]), (int)log_n, hi, lo, false)) != IOPX_OK) return rc;
+        hhi[k] = hi.u64();
+        hlo[k] = lo.u64();
+    }
+    // one block for the four per-call tables (one constant-carrying launch): oracle pointers, the two table-pointer lists, the coefficients
+    std::vector<uint64_t> meta(3 * num_oracles + hcoef.size());
+    for (size_t k = 0; k < num_oracles; ++k) {
+        meta[k] = (uint64_t)(uintptr_t)d_oracles[k];
+        meta[num_oracles + k] = (uint64_t)(uintptr_t)hhi[k];
+        meta[2 * num_oracles + k] = (uint64_t)(uintptr_t)hlo[k];
+    }
+    std::memcpy(&meta[3 * num_oracles], hcoef.data(), hcoef.size() * 8);
+    TmpBuf dmeta;
+    if ((rc = dmeta.alloc(meta.size() * 8)) != IOPX_OK) return rc;
+    if ((rc = upload(dmeta.p, meta.data(), meta.size() * 8)) != IOPX_OK) return rc;
+    LdtFpParams p;
+    p.oracles = (const uint64_t *const *)dmeta.u64();
+    p.hi = (const uint64_t *const *)(dmeta.u64() + num_oracles);
+    p.lo = (const uint64_t *const *)(dmeta.u64() + 2 * num_oracles);
+    p.out = d_out;
+    p.coef = dmeta.u64() + 3 * num_oracles;
+    p.n = (size_t)1 << log_n; p.num_oracles = (int)num_oracles;
+    { ProfScope ps_(label, (num_oracles + 1) * p.n * Field::BYTES); hipLaunchKernelGGL(kernel, dim3(ldt_grid(p.n)), dim3(256), 0, stream(), p); }
+    IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
@@ -337,57 +411,11 @@ int iopx_ldt_combine_gf192_dev(const void *const *d_oracles, size_t num_oracles,
     return IOPX_OK;
 }
 
-int iopx_ldt_combine_fp3_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees,
-                             const uint64_t *random_coefficients, size_t log_n, const uint64_t *gen, const uint64_t *shift,
-                             uint64_t *d_out)
-{
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (!d_oracles || !random_coefficients || !d_out || !gen || !shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (log_n > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension %zu too large", log_n);
-    LdtPlan pl;
-    if ((rc = ldt_plan(degrees, num_oracles, &pl)) != IOPX_OK) return rc;
-    auto coef = [&](size_t t) { hfp3 r = hfp3::one(); if (t) memcpy(r.w, random_coefficients + 3 * (t - 1), 24); return r; };
-    hfp3 g, s;
-    memcpy(g.w, gen, 24);
-    memcpy(s.w, shift, 24);
-    std::vector<uint64_t> hcoef;
-    std::vector<std::unique_ptr<TmpBuf>> tabs;
-    std::vector<const uint64_t *> hhi(num_oracles, nullptr), hlo(num_oracles, nullptr);
-    for (size_t k = 0; k < num_oracles; ++k) {
-        const hfp3 a = coef(pl.own[k]).table_form();       // multipliers are uploaded in the device's table form (fp3_dev.h)
-        hcoef.insert(hcoef.end(), a.w, a.w + 3);
-        if (!pl.shifted[k]) continue;
-        // cur_bump_factor = c[num + i] * shift^e, multiplied by g^e per position (ldt_reducer_aux.tcc:112-126)
-        tabs.emplace_back(new TmpBuf());
-        tabs.emplace_back(new TmpBuf());
-        TmpBuf &hi = *tabs[tabs.size() - 2], &lo = *tabs[tabs.size() - 1];
-        // the random coefficient rides on the hi half (rebuilt per call); the lo half depends on the degree gap and the domain only
-        if ((rc = build_two_level(g.pow(pl.expo[k]), coef(pl.shifted[k]) * s.pow(pl.expo[k]), (int)log_n, hi, lo, false)) != IOPX_OK) return rc;
-        hhi[k] = hi.u64();
-        hlo[k] = lo.u64();
-    }
-    // one block for the four per-call tables (one constant-carrying launch): oracle pointers, the two table-pointer lists, the coefficients
-    std::vector<uint64_t> meta(3 * num_oracles + hcoef.size());
-    for (size_t k = 0; k < num_oracles; ++k) {
-        meta[k] = (uint64_t)(uintptr_t)d_oracles[k];
-        meta[num_oracles + k] = (uint64_t)(uintptr_t)hhi[k];
-        meta[2 * num_oracles + k] = (uint64_t)(uintptr_t)hlo[k];
-    }
-    std::memcpy(&meta[3 * num_oracles], hcoef.data(), hcoef.size() * 8);
-    TmpBuf dmeta;
-    if ((rc = dmeta.alloc(meta.size() * 8)) != IOPX_OK) return rc;
-    if ((rc = upload(dmeta.p, meta.data(), meta.size() * 8)) != IOPX_OK) return rc;
-    LdtFpParams p;
-    p.oracles = (const uint64_t *const *)dmeta.u64();
-    p.hi = (const uint64_t *const *)(dmeta.u64() + num_oracles);
-    p.lo = (const uint64_t *const *)(dmeta.u64() + 2 * num_oracles);
-    p.out = d_out;
-    p.coef = dmeta.u64() + 3 * num_oracles;
-    p.n = (size_t)1 << log_n; p.num_oracles = (int)num_oracles;
-    { ProfScope ps_("k_ldt_combine_fp", (num_oracles + 1) * p.n * 24); hipLaunchKernelGGL(k_ldt_combine_fp, dim3(ldt_grid(p.n)), dim3(256), 0, stream(), p); }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
-}
+int iopx_ldt_combine_fp3_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees, const uint64_t *random_coefficients,
+                             size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out)
+{ return ldt_combine_mul_dev<FpField>(d_oracles, num_oracles, degrees, random_coefficients, log_n, gen, shift, d_out, k_ldt_combine_fp, "k_ldt_combine_fp"); }
+int iopx_ldt_combine_bn128_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees, const uint64_t *random_coefficients,
+                               size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out)
+{ return ldt_combine_mul_dev<BnField>(d_oracles, num_oracles, degrees, random_coefficients, log_n, gen, shift, d_out, k_bn_ldt_combine, "k_bn_ldt_combine"); }
 
 } // extern "C"

@@ -141,12 +141,15 @@ struct ProfScope {
     ~ProfScope();
 };
 
-// fft_mul.hip: two-level power tables of the 181-bit prime field on the device,
+// fft_mul.hip: two-level power tables of a prime field on the device (edwards_Fr, alt_bn128 Fr),
 // hi[q] = init * base^(4096 q) (q < 2^max(logc-12,0)), lo[r] = base^r (r < 4096), so init * base^j = hi[j >> 12] * lo[j & 4095]
 struct hfp3;
-// Tables are kept by (base, init, logc) — most of them depend on the domain only and recur in every proof; cache_hi = false for a
-// table whose init carries a per-proof value (the LDT coefficients): its lo half is still shared by base.
+struct hbn;
+// edwards_Fr tables are kept by (base, init, logc) — most of them depend on the domain only and recur in every proof; cache_hi = false
+// for a table whose init carries a per-proof value (the LDT coefficients): its lo half is still shared by base.  alt_bn128 Fr tables
+// are built per call.
 int build_two_level(const hfp3 &base, const hfp3 &init, int logc, TmpBuf &hi, TmpBuf &lo, bool cache_hi = true);
+int build_two_level(const hbn &base, const hbn &init, int logc, TmpBuf &hi, TmpBuf &lo, bool cache_hi = true);   // cache_hi: no effect (never cached)
 
 // Per-module plan caches dropped by iopx_clear_plans() (the caller has synchronised the device).
 // Options: named integers that select a schedule or a tile geometry.  One table for the whole library: a name's value is whatever
@@ -176,8 +179,7 @@ int side_stream_fork(int k);
 int side_stream_select(int k);      // -1: back to the main stream
 int side_stream_join(int k);
 int side_stream_current();
-void clear_mul_plans();
-void clear_bn128_plans();         // fft_bn128.hip: the alt_bn128 twiddle caches
+void clear_mul_plans();           // fft_mul.hip: both prime fields' twiddle caches and power tables
 void clear_dist_plans();           // fft_add_dist.hip: the sharded transforms' per-rank twist tables
 void clear_poseidon_sets();
 

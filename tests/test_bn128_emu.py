@@ -1,4 +1,4 @@
-"""The alt_bn128 Fr multiplicative-coset kernels (libiop_amd/csrc/fft_bn128.hip) compiled for the CPU (tests/emu) against values computed with
+"""The alt_bn128 Fr multiplicative-coset kernels (libiop_amd/csrc/fft_mul.hip, ldt_reducer.hip) compiled for the CPU (tests/emu) against values computed with
 Python integers only: every case of tests/golden/bn128_tiny.json, the full-size digest recipes at m = 10 and 12
 (tests/golden/bn128_function_digests_large.json), the host scalars, the argument checks and the in-place forms.  The GPU leg is
 tests/test_gpu_bn128.py."""
@@ -71,6 +71,14 @@ def test_argument_checks():
         lib.multiplicative_FFT_bn128(f, 4, one, gen=C.elem(C.gen(3)))
     with pytest.raises(ValueError, match="exceed"):
         lib.multiplicative_FFT_bn128(C.data_words("checks", 17), 4, one)
+    # the null-pointer checks of these entries are shared with the edwards_Fr ones (one host implementation for both fields)
+    for call in (lambda: lib.c.iopx_mul_ifft_known_degree_fp3_dev(None, 4, 3, None, None, None),
+                 lambda: lib.c.iopx_mul_ifft_known_degree_bn128_dev(None, 4, 3, None, None, None),
+                 lambda: lib.c.iopx_mul_fft_fp3(None, 4, 3, None, None, None),
+                 lambda: lib.c.iopx_mul_ifft_fp3(None, 3, None, None, None),
+                 lambda: lib.c.iopx_fri_fold_mul_fp3(None, 3, None, None, 2, None, None)):
+        with pytest.raises(ValueError, match="null"):
+            lib._check(call())
 
 
 def test_in_place():

@@ -87,7 +87,7 @@ __device__ __forceinline__ bn9 bn9_norm(const bn9 &a)
 // 2^254 - p, plain limbs: v = q * 2^254 + rem is congruent to q * (2^254 - p) + rem
 __device__ static const uint32_t BN9_C254[9] = { 0x0fffffffu, 0x00f05360u, 0x11a3dbafu, 0x182f6f0cu, 0x0a7a2d7cu, 0x1d24bf3fu, 0x1f591ebeu, 0x11a3d9cbu, 0x000f9bb1u };
 
-// Weak reduction of any limb vector (limbs up to 2^32 - 1): same residue, value below 2^254 + (v >> 254) * 0.25 * 2^254 and
+// Weak reduction of a limb vector (limbs 0..7 up to 2^32 - 8: bn9_norm adds a carry of up to 7 in 32 bits): same residue, value below 2^254 + (v >> 254) * 0.25 * 2^254 and
 // normalised limbs.  Used where elements are only ever added (the near-MDS layers), so that they stay below 2^256.
 __device__ __forceinline__ bn9 bn9_reduce(const bn9 &a)
 {
@@ -193,7 +193,7 @@ __device__ __forceinline__ bn9 bn9_load_mont(const uint64_t *p, size_t idx)
     return bn9_mul(bn9_unpack(p + 4 * idx), bn9_const(BN9_C266));
 }
 
-// value below 2^255 with normalised limbs -> canonical 4 x 64-bit words
+// value below 2r with normalised limbs (a product of a value below 2^256 and a canonical one) -> canonical 4 x 64-bit words: r is subtracted once
 __device__ __forceinline__ void bn9_store_canonical(uint64_t *q, const bn9 &y)
 {
     uint32_t w[8], d[8];

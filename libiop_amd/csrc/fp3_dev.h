@@ -142,7 +142,8 @@ __device__ __forceinline__ fp3 fp7_pack(const fp7 &y)
 }
 
 // a * b * 2^-203 mod p, result < 2p with normalised limbs.  Column sums stay below 2^64 for operand limbs up to 2^30 (both)
-// or 2^31 against a normalised operand; values up to 2^192 on both sides keep the result below 2p.
+// or any 32-bit limbs against a normalised operand; one value below 2^192 against one below p (data or a lazily reduced value times a
+// canonical table entry: every caller) keeps the result below 2p — both at 2^192 would give up to 2^181 + p = 2.97 p.
 __device__ __forceinline__ fp7 fp7_mul(const fp7 &a, const fp7 &b)
 {
     uint32_t m[7];
@@ -178,6 +179,7 @@ __device__ __forceinline__ fp7 fp7_mul(const fp7 &a, const fp7 &b)
 struct fp7w {
     uint64_t c[13];
 };
+#define FP7W_MAX_TERMS 8                // products of normalised limbs per fp7w_redc: the group size of every kernel that sums more terms
 
 __device__ __forceinline__ void fp7w_zero(fp7w &w)
 {
@@ -242,10 +244,11 @@ __device__ __forceinline__ fp3 fp_neg(const fp3 &a)
 // ---- lazily reduced butterflies ---------------------------------------------------------------------------------------
 // A radix-2 butterfly (x, y) -> (x + w y, x - w y) on limb vectors with NO carry handling: t = w y is below 2p with 29-bit
 // limbs; the difference is formed as x + (8p - t) with 8p written so that each of its lower six limbs is at least 2^29 - 1
-// (and the top one above t's), so every limb stays non-negative.  Limbs grow by at most 1.5 * 2^29 per level — below 2^32 after
+// (and the top one above t's), so every limb stays non-negative.  Limbs grow by less than 2^30 per level (8p's largest limb is 1.88 * 2^29) — below 2^32 after
 // the three levels a lane runs on its registers — and fp7_mul takes one operand with any 32-bit limbs against a normalised
 // twiddle (7 * 2^32 * 2^29 + 7 * 2^58 < 2^64).  Values grow by at most 8p per level: below 2^189 for any transform length
-// of this field (2-adicity 31), so they fit the 192-bit stored form; a transform's last pass makes them canonical.
+// of this field (2-adicity 31), so they fit the 192-bit stored form; a transform's last pass makes them canonical.  Raw (non-canonical)
+// words are carried the same way while max + 8p * levels stays below 2^192; above that fp7_pack drops bits (tests/noncanonical_cases.py).
 __device__ static const uint32_t FP7_8P_SPREAD[7] = { 0x20000008u, 0x3954c9dfu, 0x3c25983au, 0x2e493b91u, 0x272b6270u, 0x35fc9d29u, 0x00000205u };
 __device__ static const uint32_t FP7_ONE_T[7] = { 0x1f81a675u, 0x0910f06bu, 0x1f077a07u, 0x02c7785du, 0x1a4c3b6au, 0x144d5829u, 0x00000011u };  // 2^203 mod p
 

@@ -181,6 +181,7 @@ __global__ void __launch_bounds__(256) k_sumcheck_g_fp(uint64_t *out, const uint
 // p_alpha^1 and p_alpha^2 already extended to the codeword domain (two ordinary transforms, :112-118):
 //     result[x] = (sum_m r_m Mz_m(x)) * p_alpha^1(x) - fz(x) * p_alpha^2(x)
 #define LINCHECK_MAX_MATRICES 8
+static_assert(LINCHECK_MAX_MATRICES <= FP7W_MAX_TERMS, "k_lincheck_fp sums r_m Mz_m with one reduction");
 struct LincheckParams {
     const uint64_t *fz, *p1, *p2;
     const uint64_t *mz[LINCHECK_MAX_MATRICES];

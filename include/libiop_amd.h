@@ -227,6 +227,9 @@ int iopx_bn128_from_uint(uint64_t v, uint64_t *out);
 int iopx_bn128_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 int iopx_bn128_host_pow(const uint64_t *a, uint64_t exponent, uint64_t *out);
 int iopx_bn128_host_inverse(const uint64_t *a, uint64_t *out);
+int iopx_bn128_host_add(const uint64_t *a, const uint64_t *b, uint64_t *out);
+int iopx_bn128_host_sub(const uint64_t *a, const uint64_t *b, uint64_t *out);
+int iopx_bn128_modulus(uint64_t *out);          /* r as four plain little-endian words */
 
 /* ---- FRI fold over GF(2^192) -------------------------------------------------------------------- */
 /* evaluate_next_f_i_over_entire_domain for affine subspaces:
@@ -334,7 +337,12 @@ int iopx_ldt_combine_fp3_dev(const void *const *d_oracles, size_t num_oracles, c
  *   gf192: the constraint domain H is span(basis[0 .. constraint_dim)) + constraint_shift (a prefix of the codeword basis, as
  *          the reference assumes, :31-33)
  *   fp3:   H is the coset constraint_shift * <gen^(2^log_n / 2^constraint_log_order)> of order 2^constraint_log_order
- * Fails with IOPX_ERR_INVALID_ARGUMENT when the two domains intersect (Z_H vanishes on the codeword domain). */
+ * Fails with IOPX_ERR_INVALID_ARGUMENT when the two domains intersect (Z_H vanishes on the codeword domain).
+ *
+ * Every *_fp3_dev entry from here to iopx_rational_sumcheck_constraint_fp3_dev has an alt_bn128 Fr twin (*_bn128_dev, iopx_bn128_*_dev) with
+ * the same arguments, checks and return codes: elements are four little-endian 64-bit words (libff Fp_model<4>, x * 2^256 mod r), gen is
+ * iopx_bn128_subgroup_generator(log_n) and log_n / log_order <= 28 (the field's 2-adicity, where edwards_Fr allows 31).  Those twins
+ * accept any raw 256-bit word as a data element (read as its residue; a multiple of r counts as zero) and always store canonical words. */
 /* d_out[i] = d_in[i] / Z_S(x_i) over the domain span(basis[0..m)) + shift, S = span(basis[0..sub_dim)) + sub_shift: Z_S is constant on a coset
  * of S, so this is one product per element with a per-coset inverse (the table rowcheck uses).  The pointwise form of
  * polynomial_over_vanishing_polynomial (r1cs_rs_iop.tcc:563-565) on a domain that does not meet S, when the division is exact. */
@@ -344,6 +352,8 @@ int iopx_rowcheck_gf192_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const ui
                             const uint64_t *shift, size_t constraint_dim, const uint64_t *constraint_shift, uint64_t *d_out);
 int iopx_rowcheck_fp3_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, size_t log_n, const uint64_t *gen,
                           const uint64_t *shift, size_t constraint_log_order, const uint64_t *constraint_shift, uint64_t *d_out);
+int iopx_rowcheck_bn128_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, size_t log_n, const uint64_t *gen,
+                            const uint64_t *shift, size_t constraint_log_order, const uint64_t *constraint_shift, uint64_t *d_out);
 
 /* fz_virtual_oracle::evaluated_contents (libiop/protocols/encoded/r1cs_rs_iop/r1cs_rs_iop.tcc:181-222):
  * out[x] = fw(x) * Z_I(x) + f_1v(x), I = the input variable domain (gf192: span(input_basis) + input_shift; fp3: the coset
@@ -353,6 +363,8 @@ int iopx_fz_gf192_dev(const uint64_t *d_fw, const uint64_t *d_f1v, const uint64_
                       const uint64_t *input_basis, size_t input_dim, const uint64_t *input_shift, uint64_t *d_out);
 int iopx_fz_fp3_dev(const uint64_t *d_fw, const uint64_t *d_f1v, size_t log_n, const uint64_t *gen, const uint64_t *shift,
                     size_t input_log_order, const uint64_t *input_shift, uint64_t *d_out);
+int iopx_fz_bn128_dev(const uint64_t *d_fw, const uint64_t *d_f1v, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                      size_t input_log_order, const uint64_t *input_shift, uint64_t *d_out);
 
 /* sumcheck_g_oracle::evaluated_contents (libiop/protocols/encoded/sumcheck/sumcheck.tcc:58-119; sumcheck_aux.tcc:3-32), H = the
  * summation domain, mu = claimed_sum:
@@ -364,6 +376,8 @@ int iopx_sumcheck_g_gf192_dev(const uint64_t *d_f, const uint64_t *d_h, const ui
                               const uint64_t *claimed_sum, uint64_t *d_out);
 int iopx_sumcheck_g_fp3_dev(const uint64_t *d_f, const uint64_t *d_h, size_t log_n, const uint64_t *gen, const uint64_t *shift,
                             size_t summation_log_order, const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out);
+int iopx_sumcheck_g_bn128_dev(const uint64_t *d_f, const uint64_t *d_h, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                              size_t summation_log_order, const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out);
 
 /* multi_lincheck_virtual_oracle::evaluated_contents (libiop/protocols/encoded/lincheck/basic_lincheck_aux.tcc:102-144):
  * out[x] = (sum_m r_Mz[m] * Mz_m(x)) * p_alpha_prime(x) - fz(x) * p_alpha_ABC(x) over n positions; the two p_alpha codewords are the
@@ -373,6 +387,8 @@ int iopx_lincheck_gf192_dev(const uint64_t *d_fz, const void *const *d_Mz, size_
                             const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out);
 int iopx_lincheck_fp3_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz,
                           const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out);
+int iopx_lincheck_bn128_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz,
+                            const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out);
 
 /* ---- encoded Aurora prover: the vector-sized steps between the transforms ---------------------------- */
 /* Sparse matrix x vector in CSR form (row_ptr: rows + 1 offsets, col: column of each entry, coeff: its field element), all on the
@@ -385,6 +401,8 @@ int iopx_spmv_gf192_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const 
                         const uint64_t *scale, int accumulate, uint64_t *d_out);
 int iopx_spmv_fp3_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
                       const uint64_t *scale, int accumulate, uint64_t *d_out);
+int iopx_spmv_bn128_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
+                        const uint64_t *scale, int accumulate, uint64_t *d_out);
 /* polynomial_over_vanishing_polynomial(P, Z).first (libiop/algebra/polynomials/vanishing_polynomial.tcc:314-371,
  * linearized_polynomial.tcc:238-289): the quotient of the n_coeffs-coefficient polynomial by the vanishing polynomial of the affine
  * subspace (basis[dim], shift) / of the coset shift * <order 2^log_order>; writes n_coeffs - |domain| coefficients (nothing when
@@ -392,19 +410,25 @@ int iopx_spmv_fp3_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const ui
 int iopx_poly_div_vanishing_gf192_dev(const uint64_t *d_poly, size_t n_coeffs, const uint64_t *basis, size_t dim, const uint64_t *shift,
                                       uint64_t *d_quotient);
 int iopx_poly_div_vanishing_fp3_dev(const uint64_t *d_poly, size_t n_coeffs, size_t log_order, const uint64_t *shift, uint64_t *d_quotient);
+int iopx_poly_div_vanishing_bn128_dev(const uint64_t *d_poly, size_t n_coeffs, size_t log_order, const uint64_t *shift, uint64_t *d_quotient);
 /* random_linear_combination_oracle::evaluated_contents (libiop/protocols/encoded/common/random_linear_combination.tcc:27-57):
  * out[x] = sum_i coefficients[i] * oracle_i[x]; d_oracles is a host array of num_oracles (<= 16) device pointers. */
 int iopx_lincomb_gf192_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
 int iopx_lincomb_fp3_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
+int iopx_lincomb_bn128_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
 /* Elementwise helpers on device vectors (the synthetic instance of libiop/relations/examples/r1cs_examples.tcc:40-64, and
  * f_w' = z - f_1v over the variable domain, r1cs_rs_iop.tcc:406-430): sum / difference, product, inverse (zero stays zero),
  * d_out[l] = init * base^l (the alpha powers of basic_lincheck_aux.tcc:37-45). */
 int iopx_gf192_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_gf192_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
 int iopx_fp3_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
+int iopx_bn128_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_fp3_sub_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
+int iopx_bn128_sub_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_fp3_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
+int iopx_bn128_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
 int iopx_fp3_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init);
+int iopx_bn128_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init);
 
 /* ---- holographic (Fractal) prover: the vector-sized steps Aurora's entry points do not cover ---------- */
 /* sum_i coefficients[i] * oracle_i[x] + constant: single_matrix_denominator::evaluated_contents
@@ -414,6 +438,8 @@ int iopx_lincomb_affine_gf192_dev(const void *const *d_oracles, size_t num_oracl
                                   uint64_t *d_out);
 int iopx_lincomb_affine_fp3_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
                                 uint64_t *d_out);
+int iopx_lincomb_affine_bn128_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
+                                  uint64_t *d_out);
 /* Elementwise quotient d_out[l] = d_num[l] / d_den[l] by batch inversion (libiop/algebra/utils.tcc:57-118 batch_inverse /
  * batch_inverse_and_mul); d_num NULL: plain inverses; a zero denominator yields zero.  d_out must not alias an input.
  * Callers: lagrange_polynomial::evaluations_over_field_subset (algebra/polynomials/lagrange_polynomial.tcc:66-136),
@@ -421,10 +447,12 @@ int iopx_lincomb_affine_fp3_dev(const void *const *d_oracles, size_t num_oracles
  * rational_linear_combination::evaluated_contents (common/rational_linear_combination.tcc:183-209). */
 int iopx_gf192_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count);
 int iopx_fp3_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count);
+int iopx_bn128_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count);
 /* d_out[j] = point - x_j over the whole domain (affine subspace basis[m] + shift / coset shift * <gen> of order 2^log_n): the
  * denominators x - y of lagrange_polynomial.tcc:72-87 and the shifted elements of boundary_constraint.tcc:31-47 (negated). */
 int iopx_domain_offsets_gf192_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *point, uint64_t *d_out);
 int iopx_domain_offsets_fp3_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, const uint64_t *point, uint64_t *d_out);
+int iopx_domain_offsets_bn128_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, const uint64_t *point, uint64_t *d_out);
 /* d_out[j] = constant - Z_S(x_j) over the whole domain, Z_S the vanishing polynomial of the subspace vanishing_basis[vanishing_dim] +
  * vanishing_shift / of the coset vanishing_shift * <order 2^vanishing_log_order> (vanishing_polynomial::evaluations_over_field_subset,
  * libiop/algebra/polynomials/vanishing_polynomial.tcc:97-137): with constant = Z_S(alpha) the numerator of lagrange_polynomial.tcc:124-131. */
@@ -432,6 +460,8 @@ int iopx_vanishing_evals_gf192_dev(const uint64_t *basis, size_t m, const uint64
                                    const uint64_t *vanishing_shift, const uint64_t *constant, uint64_t *d_out);
 int iopx_vanishing_evals_fp3_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, size_t vanishing_log_order, const uint64_t *vanishing_shift,
                                  const uint64_t *constant, uint64_t *d_out);
+int iopx_vanishing_evals_bn128_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, size_t vanishing_log_order, const uint64_t *vanishing_shift,
+                                   const uint64_t *constant, uint64_t *d_out);
 /* combined_numerator / combined_denominator::evaluated_contents (libiop/protocols/encoded/common/rational_linear_combination.tcc:13-108):
  * N[x] = sum_i coefficients[i] N_i[x] prod_{k != i} D_k[x], D[x] = prod_k D_k[x] for num_rationals (<= 4) rationals; host arrays of
  * device pointers. */
@@ -439,6 +469,8 @@ int iopx_rational_combine_gf192_dev(const void *const *d_numerators, const void 
                                     size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out);
 int iopx_rational_combine_fp3_dev(const void *const *d_numerators, const void *const *d_denominators, size_t num_rationals, const uint64_t *coefficients,
                                   size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out);
+int iopx_rational_combine_bn128_dev(const void *const *d_numerators, const void *const *d_denominators, size_t num_rationals, const uint64_t *coefficients,
+                                    size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out);
 /* sumcheck_constraint_oracle::evaluated_contents (libiop/protocols/encoded/sumcheck/rational_sumcheck.tcc:58-112) over the whole
  * codeword domain, K the summation (index) domain:
  *   subspaces: (D (p + eps^-1 mu x^(|K| - 1)) - N) / Z_K, K = span(basis[0..summation_dim)) + summation_shift, d_xinv = 1 / x over the
@@ -450,6 +482,9 @@ int iopx_rational_sumcheck_constraint_gf192_dev(const uint64_t *d_p, const uint6
 int iopx_rational_sumcheck_constraint_fp3_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, size_t log_n, const uint64_t *gen,
                                               const uint64_t *shift, size_t summation_log_order, const uint64_t *summation_shift,
                                               const uint64_t *claimed_sum, uint64_t *d_out);
+int iopx_rational_sumcheck_constraint_bn128_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, size_t log_n, const uint64_t *gen,
+                                                const uint64_t *shift, size_t summation_log_order, const uint64_t *summation_shift,
+                                                const uint64_t *claimed_sum, uint64_t *d_out);
 /* Host helpers (no device work): Z_S(x) and Z_S's linear coefficient — its formal derivative, vanishing_polynomial.tcc:55-74 — for
  * S = span(basis[dim]) + shift (either output may be NULL); the inverse of one element. */
 int iopx_gf192_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *shift, const uint64_t *x, uint64_t *value_out,

@@ -65,6 +65,11 @@ EXPORTED_SYMBOLS = [
     "iopx_mul_fft_bn128_dev", "iopx_mul_fft_bn128", "iopx_mul_ifft_bn128_dev", "iopx_mul_ifft_bn128", "iopx_mul_ifft_known_degree_bn128_dev",
     "iopx_fri_fold_mul_bn128_dev", "iopx_fri_fold_mul_bn128", "iopx_ldt_combine_bn128_dev",
     "iopx_bn128_subgroup_generator", "iopx_bn128_multiplicative_generator", "iopx_bn128_host_mul", "iopx_bn128_host_pow", "iopx_bn128_host_inverse", "iopx_bn128_from_uint",
+    "iopx_bn128_host_add", "iopx_bn128_host_sub", "iopx_bn128_modulus",
+    "iopx_rowcheck_bn128_dev", "iopx_fz_bn128_dev", "iopx_sumcheck_g_bn128_dev", "iopx_lincheck_bn128_dev", "iopx_spmv_bn128_dev",
+    "iopx_poly_div_vanishing_bn128_dev", "iopx_lincomb_bn128_dev", "iopx_bn128_mul_dev", "iopx_bn128_sub_dev", "iopx_bn128_inv_dev",
+    "iopx_bn128_pow_table_dev", "iopx_lincomb_affine_bn128_dev", "iopx_bn128_div_dev", "iopx_domain_offsets_bn128_dev",
+    "iopx_vanishing_evals_bn128_dev", "iopx_rational_combine_bn128_dev", "iopx_rational_sumcheck_constraint_bn128_dev",
 ]
 
 
@@ -247,6 +252,21 @@ class Library:
         c.iopx_rational_sumcheck_constraint_fp3_dev.argtypes = [_vp, _vp, _vp, _sz, _u64p, _u64p, _sz, _u64p, _u64p, _vp]
         c.iopx_gf192_vanishing_host.argtypes = [_u64p, _sz, _u64p, _u64p, _u64p, _u64p]
         c.iopx_gf192_inverse_host.argtypes = [_u64p, _u64p]
+        # the alt_bn128 Fr twins of the protocol-layer entries take their edwards_Fr twin's arguments
+        for twin, name in (("iopx_rowcheck_fp3_dev", "iopx_rowcheck_bn128_dev"), ("iopx_fz_fp3_dev", "iopx_fz_bn128_dev"),
+                           ("iopx_sumcheck_g_fp3_dev", "iopx_sumcheck_g_bn128_dev"), ("iopx_lincheck_fp3_dev", "iopx_lincheck_bn128_dev"),
+                           ("iopx_spmv_fp3_dev", "iopx_spmv_bn128_dev"), ("iopx_poly_div_vanishing_fp3_dev", "iopx_poly_div_vanishing_bn128_dev"),
+                           ("iopx_lincomb_fp3_dev", "iopx_lincomb_bn128_dev"), ("iopx_fp3_mul_dev", "iopx_bn128_mul_dev"),
+                           ("iopx_fp3_sub_dev", "iopx_bn128_sub_dev"), ("iopx_fp3_inv_dev", "iopx_bn128_inv_dev"),
+                           ("iopx_fp3_pow_table_dev", "iopx_bn128_pow_table_dev"), ("iopx_lincomb_affine_fp3_dev", "iopx_lincomb_affine_bn128_dev"),
+                           ("iopx_fp3_div_dev", "iopx_bn128_div_dev"), ("iopx_domain_offsets_fp3_dev", "iopx_domain_offsets_bn128_dev"),
+                           ("iopx_vanishing_evals_fp3_dev", "iopx_vanishing_evals_bn128_dev"),
+                           ("iopx_rational_combine_fp3_dev", "iopx_rational_combine_bn128_dev"),
+                           ("iopx_rational_sumcheck_constraint_fp3_dev", "iopx_rational_sumcheck_constraint_bn128_dev")):
+            getattr(c, name).argtypes = list(getattr(c, twin).argtypes)
+        c.iopx_bn128_host_add.argtypes = [_u64p, _u64p, _u64p]
+        c.iopx_bn128_host_sub.argtypes = [_u64p, _u64p, _u64p]
+        c.iopx_bn128_modulus.argtypes = [_u64p]
 
     # ---- error translation (the exception types the reference throws) ----
     def _check(self, rc):
@@ -1286,6 +1306,86 @@ class Library:
     def fp3_pow_table_dev(self, d_out, count, base, init):
         base, init = _as_u64(base), _as_u64(init)
         self._check(self.c.iopx_fp3_pow_table_dev(_vp(d_out), int(count), base.ctypes.data_as(_u64p), init.ctypes.data_as(_u64p)))
+
+    # ---- alt_bn128 Fr: the protocol-layer entries (four-word elements; arguments as the edwards_Fr methods above) ----
+    @staticmethod
+    def _w4(a):
+        return _as_u64(a, 4).ctypes.data_as(_u64p)
+
+    def bn128_host_add(self, a, b):
+        a, b, out = _as_u64(a, 4), _as_u64(b, 4), np.zeros(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_host_add(a.ctypes.data_as(_u64p), b.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def bn128_host_sub(self, a, b):
+        a, b, out = _as_u64(a, 4), _as_u64(b, 4), np.zeros(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_host_sub(a.ctypes.data_as(_u64p), b.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def bn128_modulus(self):
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.c.iopx_bn128_modulus(out.ctypes.data_as(_u64p)))
+        return sum(int(v) << (64 * i) for i, v in enumerate(out))
+
+    def bn128_rowcheck_dev(self, d_Az, d_Bz, d_Cz, log_n, gen, shift, constraint_log_order, constraint_shift, d_out):
+        self._check(self.c.iopx_rowcheck_bn128_dev(_vp(d_Az), _vp(d_Bz), _vp(d_Cz), int(log_n), self._w4(gen), self._w4(shift), int(constraint_log_order),
+                                                   self._w4(constraint_shift), _vp(d_out)))
+
+    def bn128_fz_dev(self, d_fw, d_f1v, log_n, gen, shift, input_log_order, input_shift, d_out):
+        self._check(self.c.iopx_fz_bn128_dev(_vp(d_fw), _vp(d_f1v), int(log_n), self._w4(gen), self._w4(shift), int(input_log_order), self._w4(input_shift), _vp(d_out)))
+
+    def bn128_sumcheck_g_dev(self, d_f, d_h, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out):
+        self._check(self.c.iopx_sumcheck_g_bn128_dev(_vp(d_f), _vp(d_h), int(log_n), self._w4(gen), self._w4(shift), int(summation_log_order),
+                                                     self._w4(summation_shift), self._w4(claimed_sum), _vp(d_out)))
+
+    def bn128_lincheck_dev(self, d_fz, d_Mz, r_Mz, d_p_alpha_prime, d_p_alpha_ABC, n, d_out):
+        ptrs = (_vp * max(1, len(d_Mz)))(*d_Mz)
+        self._check(self.c.iopx_lincheck_bn128_dev(_vp(d_fz), ptrs, len(d_Mz), self._w4(r_Mz), _vp(d_p_alpha_prime), _vp(d_p_alpha_ABC), int(n), _vp(d_out)))
+
+    def bn128_spmv_dev(self, d_row_ptr, d_col, d_coeff, rows, d_vec, d_out, scale=None, accumulate=False):
+        sc = self._w4(scale) if scale is not None else None
+        self._check(self.c.iopx_spmv_bn128_dev(_vp(d_row_ptr), _vp(d_col), _vp(d_coeff), int(rows), _vp(d_vec), sc, int(bool(accumulate)), _vp(d_out)))
+
+    def bn128_poly_div_vanishing_dev(self, d_poly, n_coeffs, log_order, shift, d_quotient):
+        self._check(self.c.iopx_poly_div_vanishing_bn128_dev(_vp(d_poly), int(n_coeffs), int(log_order), self._w4(shift), _vp(d_quotient)))
+
+    def bn128_lincomb_dev(self, d_oracles, coefficients, n, d_out):
+        ptrs = (_vp * max(1, len(d_oracles)))(*d_oracles)
+        self._check(self.c.iopx_lincomb_bn128_dev(ptrs, len(d_oracles), self._w4(coefficients), int(n), _vp(d_out)))
+
+    def bn128_lincomb_affine_dev(self, d_oracles, coefficients, constant, n, d_out):
+        ptrs = (_vp * max(1, len(d_oracles)))(*d_oracles)
+        self._check(self.c.iopx_lincomb_affine_bn128_dev(ptrs, len(d_oracles), self._w4(coefficients), self._w4(constant), int(n), _vp(d_out)))
+
+    def bn128_mul_dev(self, d_a, d_b, d_out, count):
+        self._check(self.c.iopx_bn128_mul_dev(_vp(d_a), _vp(d_b), _vp(d_out), int(count)))
+
+    def bn128_sub_dev(self, d_a, d_b, d_out, count):
+        self._check(self.c.iopx_bn128_sub_dev(_vp(d_a), _vp(d_b), _vp(d_out), int(count)))
+
+    def bn128_inv_dev(self, d_a, d_out, count):
+        self._check(self.c.iopx_bn128_inv_dev(_vp(d_a), _vp(d_out), int(count)))
+
+    def bn128_pow_table_dev(self, d_out, count, base, init):
+        self._check(self.c.iopx_bn128_pow_table_dev(_vp(d_out), int(count), self._w4(base), self._w4(init)))
+
+    def bn128_div_dev(self, d_num, d_den, d_out, count):
+        self._check(self.c.iopx_bn128_div_dev(_vp(d_num) if d_num is not None else None, _vp(d_den), _vp(d_out), int(count)))
+
+    def bn128_domain_offsets_dev(self, log_n, gen, shift, point, d_out):
+        self._check(self.c.iopx_domain_offsets_bn128_dev(int(log_n), self._w4(gen), self._w4(shift), self._w4(point), _vp(d_out)))
+
+    def bn128_vanishing_evals_dev(self, log_n, gen, shift, vanishing_log_order, vanishing_shift, constant, d_out):
+        self._check(self.c.iopx_vanishing_evals_bn128_dev(int(log_n), self._w4(gen), self._w4(shift), int(vanishing_log_order), self._w4(vanishing_shift),
+                                                          self._w4(constant), _vp(d_out)))
+
+    def bn128_rational_combine_dev(self, d_numerators, d_denominators, coefficients, n, d_numerator_out, d_denominator_out):
+        pn, pd = (_vp * max(1, len(d_numerators)))(*d_numerators), (_vp * max(1, len(d_denominators)))(*d_denominators)
+        self._check(self.c.iopx_rational_combine_bn128_dev(pn, pd, len(d_numerators), self._w4(coefficients), int(n), _vp(d_numerator_out), _vp(d_denominator_out)))
+
+    def bn128_rational_sumcheck_constraint_dev(self, d_p, d_N, d_D, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out):
+        self._check(self.c.iopx_rational_sumcheck_constraint_bn128_dev(_vp(d_p), _vp(d_N), _vp(d_D), int(log_n), self._w4(gen), self._w4(shift),
+                                                                       int(summation_log_order), self._w4(summation_shift), self._w4(claimed_sum), _vp(d_out)))
 
     def fri_additive_domains(self, basis, shift, localization):
         """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338): [(basis_i, shift_i)] for L^(0), L^(1), ..."""

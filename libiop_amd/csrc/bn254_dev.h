@@ -279,4 +279,79 @@ __device__ __forceinline__ void bnw_bfly(bn9 &a, bn9 &b, const bn9 &w)
     a = bnw_add(a, t);
 }
 
+// ---- helpers of the protocol-layer kernels (virtual_oracles.hip, encoded_ops.hip, fractal_ops.hip) ----------------------
+// Those kernels are the first to multiply DATA by DATA: x 2^256 * y 2^256 / 2^261 = x y 2^251.  The other terms of the same sum are
+// brought to that scale inside one bn9_dot (times the stored 1 = 2^256, or times BN9_C261 = the table form of 1 when the sum
+// stays in the data form), and a constant the host uploads anyway carries the missing 2^5 (table_form() applied twice: t 2^266).
+
+// -b as limbs: 8r - b, limb-wise non-negative for a weak b; limbs below 2^30, value below 2^257 (an operand of bn9_dot / bn9_mul)
+__device__ __forceinline__ bn9 bn9_negw(const bn9 &b)
+{
+    bn9 r;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r.l[i] = BN9_8R[i] - b.l[i];
+    return r;
+}
+
+// whether a raw 256-bit word (normalised limbs) is a multiple of r: 0, r, ..., 5r are the ones below 2^256 (constants fold)
+__device__ __forceinline__ bool bn9_is_zero_mod(const bn9 &x)
+{
+    bool z = false;
+#pragma unroll
+    for (uint32_t k = 0; k < 6; ++k) {
+        bool eq = true;
+        uint32_t carry = 0;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) {
+            const uint32_t v = k * BN9_P[i] + carry;        // below 6 * 2^29: fits
+            eq = eq && x.l[i] == (i < 8 ? (v & BN9_MASK) : v);
+            carry = v >> 29;
+        }
+        z = z || eq;
+    }
+    return z;
+}
+
+// x^(r-2) for x in the 2^261 form (closed under bn9_mul / bn9_sqr); e: the four raw words of r - 2, whose top bit is bit 253.
+// 253 squarings and 127 products: shared by a whole batch through Montgomery's trick, never paid per element.
+__device__ __forceinline__ bn9 bn9_fermat_inverse(const bn9 &x, const uint64_t *e)
+{
+    bn9 r = x;
+#pragma unroll 1
+    for (int bit = 252; bit >= 0; --bit) {
+        r = bn9_sqr(r);
+        if ((e[bit >> 6] >> (bit & 63)) & 1) r = bn9_mul(r, x);
+    }
+    return r;
+}
+
+template<int N, class LoadA, class LoadB>
+__device__ __forceinline__ bn9 bn9_dot_loaded(LoadA la, LoadB lb, size_t g)
+{
+    bn9 a[N], b[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) { a[i] = la(g + i); b[i] = lb(g + i); }
+    return bn9_dot<N>(a, b);
+}
+
+// sum_{begin <= t < end} la(t) * lb(t) * 2^-261 as a weak value: four products per reduction (bn9_dot's headroom for normalised
+// operands), the groups added up; la / lb yield weak values.  An empty range gives zero.
+template<class LoadA, class LoadB>
+__device__ __forceinline__ bn9 bn9_sum_products(LoadA la, LoadB lb, size_t begin, size_t end)
+{
+    bn9 acc = bn9_zero();
+    bool have = false;
+    for (size_t g = begin; g < end; g += 4) {
+        const size_t k = end - g;
+        bn9 t;
+        if (k >= 4) t = bn9_dot_loaded<4>(la, lb, g);
+        else if (k == 3) t = bn9_dot_loaded<3>(la, lb, g);
+        else if (k == 2) t = bn9_dot_loaded<2>(la, lb, g);
+        else t = bn9_dot_loaded<1>(la, lb, g);
+        acc = have ? bnw_add(acc, t) : t;
+        have = true;
+    }
+    return acc;
+}
+
 } // namespace iopx

@@ -22,6 +22,8 @@
 #include "gf192_host.h"
 #include "fp3_dev.h"
 #include "fp3_host.h"
+#include "bn254_dev.h"
+#include "mul_field.h"
 #include "runtime.h"
 
 namespace iopx {
@@ -80,6 +82,55 @@ __global__ void __launch_bounds__(256) k_fp3_inv(uint64_t *out, const uint64_t *
     }
 }
 
+// alt_bn128 Fr (bn254_dev.h): data live as x 2^256 and the device product divides by 2^261, so data x data = x y 2^251; there is no
+// constant in a plain product to carry the missing 2^5, so one correcting product with the raw 2^266 is the price (consts[0]).
+__global__ void __launch_bounds__(256) k_bn_mul(uint64_t *out, const uint64_t *a, const uint64_t *b, const uint64_t *consts, size_t n)
+{
+    const bn9 k266 = bnw_load(consts, 0);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x)
+        bnw_store_product(out, j, bn9_mul(bn9_mul(bnw_load(a, j), bnw_load(b, j)), k266));
+}
+
+// (a + 8r - b) times the table form of 1: the product is what makes the stored words canonical
+__global__ void __launch_bounds__(256) k_bn_sub(uint64_t *out, const uint64_t *a, const uint64_t *b, size_t n)
+{
+    const bn9 one_t = bn9_const(BN9_C261);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x)
+        bnw_store_product(out, j, bn9_mul(bn9_add(bnw_load(a, j), bn9_negw(bnw_load(b, j))), one_t));
+}
+
+// Montgomery's trick over the BN_INV_BATCH positions a lane owns (j, j + 256, ...), all in registers: one Fermat inversion per batch.
+// run_i = 2^261 prod_{l<=i} x_l 2^(-5 (i + 1)) (each stored factor carries 2^256 against the product's 2^-261); the inverse of the total,
+// times 2^-5 once (consts[3], table form), makes before * inv = 2^261 / x_i at every step.  A multiple of r is stepped over as a stored 1
+// and gives zero.  Reads of a position precede its write: out may alias a.
+#define BN_INV_BATCH 4
+__global__ void __launch_bounds__(256) k_bn_inv(uint64_t *out, const uint64_t *a, const uint64_t *consts, size_t n)
+{
+    const bn9 k256 = bnw_load(consts, 1), unscale_t = bnw_load(consts, 3), one_t = bn9_const(BN9_C261);
+    for (size_t base = (size_t)blockIdx.x * (256 * BN_INV_BATCH); base < n; base += (size_t)gridDim.x * (256 * BN_INV_BATCH)) {
+        for (unsigned lane = threadIdx.x; lane < 256; lane += blockDim.x) {
+            bn9 x[BN_INV_BATCH], run[BN_INV_BATCH];
+            bool zero[BN_INV_BATCH];
+#pragma unroll
+            for (int i = 0; i < BN_INV_BATCH; ++i) {
+                const size_t j = base + lane + 256 * (size_t)i;
+                x[i] = j < n ? bnw_load(a, j) : k256;
+                zero[i] = bn9_is_zero_mod(x[i]);
+                if (zero[i]) x[i] = k256;
+                run[i] = bn9_mul(i ? run[i - 1] : one_t, x[i]);
+            }
+            bn9 inv = bn9_mul(bn9_fermat_inverse(run[BN_INV_BATCH - 1], consts + 8), unscale_t);
+#pragma unroll
+            for (int i = BN_INV_BATCH - 1; i >= 0; --i) {
+                const size_t j = base + lane + 256 * (size_t)i;
+                const bn9 q = bn9_mul(i ? run[i - 1] : one_t, inv);    // (1 / x_i) 2^261
+                inv = bn9_mul(inv, x[i]);
+                if (j < n) bnw_store_product(out, j, zero[i] ? bn9_zero() : bn9_mul(q, k256));
+            }
+        }
+    }
+}
+
 // ---- random linear combination ---------------------------------------------------------------------------------------------
 #define LINCOMB_MAX 16
 struct LincombParams {
@@ -113,6 +164,18 @@ __global__ void __launch_bounds__(256) k_lincomb_fp3(LincombParams p)
             acc = fp_add(acc, fp_redc(w));
         }
         fp_store(p.out, j, acc);
+    }
+}
+
+// alt_bn128 Fr: four products per reduction; when a constant or a second group of four joins, the sum goes through one product with
+// the table form of 1, which is what makes the stored words canonical (a single group of products with canonical coefficients is below 2r)
+__global__ void __launch_bounds__(256) k_bn_lincomb(LincombParams p)
+{
+    const bn9 c0 = p.has_constant ? bnw_load(p.c, p.num) : bn9_zero(), one_t = bn9_const(BN9_C261);
+    const bool direct = !p.has_constant && p.num <= 4;
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 acc = bn9_sum_products([&](size_t i) { return bnw_load(p.o[i], j); }, [&](size_t i) { return bnw_load(p.c, i); }, 0, (size_t)p.num);
+        bnw_store_product(p.out, j, direct ? acc : bn9_mul(bn9_add(acc, c0), one_t));
     }
 }
 
@@ -152,12 +215,29 @@ __global__ void __launch_bounds__(256) k_spmv_fp3(SpmvParams p)
     }
 }
 
+// alt_bn128 Fr: the row sum at scale 2^251 (four products per reduction); scale (r 2^266 raw, or 2^266) restores libff's form in the
+// same reduction that adds the previous content when accumulating
+__global__ void __launch_bounds__(256) k_bn_spmv(SpmvParams p)
+{
+    const bn9 k = bnw_load(p.scale, 0), one_t = bn9_const(BN9_C261);
+    for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < p.rows; r += (size_t)gridDim.x * blockDim.x) {
+        const bn9 acc = bn9_sum_products([&](size_t t) { return bnw_load(p.vec, p.col[t]); }, [&](size_t t) { return bnw_load(p.coeff, t); },
+                                         (size_t)p.row_ptr[r], (size_t)p.row_ptr[r + 1]);
+        if (p.accumulate) {
+            const bn9 a[2] = { acc, bnw_load(p.out, r) }, b[2] = { k, one_t };
+            bnw_store_product(p.out, r, bn9_dot<2>(a, b));
+        } else {
+            bnw_store_product(p.out, r, bn9_mul(acc, k));
+        }
+    }
+}
+
 // ---- one factor (1 + u^(2^k)) of the power-series inverse ------------------------------------------------------------------
 #define PDIV_MAX_TERMS 66
 struct PolyDivParams {
     const uint64_t *src;
     uint64_t *dst;
-    uint64_t consts[3 * PDIV_MAX_TERMS];     // nterms elements (fp3: 2^203 form), in the argument block: no upload launch per pass
+    uint64_t consts[3 * PDIV_MAX_TERMS];     // nterms elements (fp3: 2^203 form; alt_bn128: four words each, 2^261 form), in the argument block: no upload launch per pass
     size_t off[PDIV_MAX_TERMS];
     size_t M;
     int nterms;
@@ -187,29 +267,87 @@ __global__ void __launch_bounds__(256) k_polydiv_pass_fp3(PolyDivParams p)
     }
 }
 
-// raw-word constants of the F_p kernels: 2^214, 2^192, p - 2
-static void fp_consts(uint64_t (&c)[9])
+// alt_bn128 Fr: src[j] 1 + sum_t src[j + off_t] c_t, each term in the reduction that also carries the running value; a position no
+// term reaches is still multiplied by the table form of 1 (canonical words)
+__global__ void __launch_bounds__(256) k_bn_polydiv_pass(PolyDivParams p)
 {
-    const hfp3 k192 = hfp3::one(), k214 = k192.table_form().table_form();
-    memcpy(c, k214.w, 24); memcpy(c + 3, k192.w, 24);
-    c[6] = hfp3::P[0] - 2; c[7] = hfp3::P[1]; c[8] = hfp3::P[2];
+    const bn9 one_t = bn9_const(BN9_C261);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.M; j += (size_t)gridDim.x * blockDim.x) {
+        bn9 acc = bnw_load(p.src, j);
+        bool done = false;
+        for (int t = 0; t < p.nterms; ++t) {
+            const size_t s = j + p.off[t];
+            if (s >= p.M) continue;
+            const bn9 a[2] = { acc, bnw_load(p.src, s) }, b[2] = { one_t, bnw_load(p.consts, t) };
+            acc = bn9_dot<2>(a, b);
+            done = true;
+        }
+        bnw_store_product(p.dst, j, done ? acc : bn9_mul(acc, one_t));
+    }
 }
 
-struct Term { size_t off; uint64_t c[3]; };
+// The two prime fields' kernels of this file behind one host implementation (mul_field.h)
+struct EoGf : Gf192Field {
+    static constexpr auto lincomb = k_lincomb_gf192; static constexpr const char *lincomb_label = "k_lincomb_gf192";
+    static constexpr auto spmv = k_spmv_gf192; static constexpr const char *spmv_label = "k_spmv_gf192";
+};
+struct EoFp : FpField {
+    static constexpr auto lincomb = k_lincomb_fp3; static constexpr const char *lincomb_label = "k_lincomb_fp3";
+    static constexpr auto spmv = k_spmv_fp3; static constexpr const char *spmv_label = "k_spmv_fp3";
+    static constexpr auto mul = k_fp3_mul; static constexpr const char *mul_label = "k_fp3_mul";
+    static constexpr auto sub = k_fp3_sub; static constexpr const char *sub_label = "k_fp3_sub";
+    static constexpr auto inv = k_fp3_inv; static constexpr const char *inv_label = "k_fp3_inv";
+    static constexpr auto polydiv_pass = k_polydiv_pass_fp3; static constexpr const char *polydiv_pass_label = "k_polydiv_pass_fp3";
+    static int inv_grid(size_t n) { return eo_grid(n); }
+};
+struct EoBn : BnField {
+    static constexpr auto lincomb = k_bn_lincomb; static constexpr const char *lincomb_label = "k_bn_lincomb";
+    static constexpr auto spmv = k_bn_spmv; static constexpr const char *spmv_label = "k_bn_spmv";
+    static constexpr auto mul = k_bn_mul; static constexpr const char *mul_label = "k_bn_mul";
+    static constexpr auto sub = k_bn_sub; static constexpr const char *sub_label = "k_bn_sub";
+    static constexpr auto inv = k_bn_inv; static constexpr const char *inv_label = "k_bn_inv";
+    static constexpr auto polydiv_pass = k_bn_polydiv_pass; static constexpr const char *polydiv_pass_label = "k_bn_polydiv_pass";
+    static int inv_grid(size_t n) { return eo_grid((n + BN_INV_BATCH - 1) / BN_INV_BATCH); }     // a lane owns a batch
+};
 
-// runs the passes; `consts_of_pass(k)` yields the terms of the factor 1 + u^(2^k) (offsets already scaled)
-template<typename PassTerms, typename Launch>
-static int run_division(const uint64_t *d_high, size_t M, size_t min_offset, uint64_t *d_quotient, PassTerms terms_of_pass, Launch launch)
+// raw-word constants of the prime-field kernels, slots of F::WORDS: the device form of the stored 1 twice (2^214 / 2^266), the stored 1
+// (2^192 / 2^256), p - 2, the table form of 1 / TABLE_FACTOR
+template<class F>
+static void fp_consts(uint64_t (&c)[4 * F::WORDS])
 {
+    typedef typename F::H H;
+    const H k1 = H::one(), k2 = k1.table_form().table_form(), unscale_t = H::from_uint(F::TABLE_FACTOR).inverse().table_form();
+    memcpy(c, k2.w, F::BYTES); memcpy(c + F::WORDS, k1.w, F::BYTES);
+    for (int i = 0; i < F::WORDS; ++i) c[2 * F::WORDS + i] = H::P[i];
+    c[2 * F::WORDS] -= 2;
+    memcpy(c + 3 * F::WORDS, unscale_t.w, F::BYTES);
+}
+
+struct Term { size_t off; uint64_t c[4]; };
+
+// runs the passes; `consts_of_pass(k)` yields the terms of the factor 1 + u^(2^k) (offsets already scaled).  Where a factor is 1 on the
+// whole range the values are copied; with `canonical_copy` (alt_bn128 Fr, whose inputs may be raw words while every output is canonical)
+// that copy is a pass with no terms, which stores each value times one.
+template<typename PassTerms, typename Launch>
+static int run_division(const uint64_t *d_high, size_t M, size_t min_offset, uint64_t *d_quotient, PassTerms terms_of_pass, Launch launch, size_t words = 3,
+                        bool canonical_copy = false)
+{
+    const size_t elt = 8 * words;
+    auto copy = [&](uint64_t *dst, const uint64_t *src) -> int {
+        if (canonical_copy) {
+            PolyDivParams p;
+            memset(&p, 0, sizeof(p));
+            p.src = src; p.dst = dst; p.M = M;      // elementwise: in place is fine
+            return launch(p);
+        }
+        return src != dst ? iopx::copy_d2d(dst, src, M * elt) : IOPX_OK;
+    };
     int passes = 0;
     for (size_t o = min_offset; o != 0 && o < M; o <<= 1) ++passes;         // offsets stay below 2 M <= 2^41: no overflow
-    if (passes == 0) {
-        if (d_high != d_quotient) { const int crc_ = iopx::copy_d2d(d_quotient, d_high, M * 24); if (crc_ != IOPX_OK) return crc_; }
-        return IOPX_OK;
-    }
+    if (passes == 0) return copy(d_quotient, d_high);
     TmpBuf ping;
     int rc;
-    if (passes > 1 && (rc = ping.alloc(M * 24)) != IOPX_OK) return rc;
+    if (passes > 1 && (rc = ping.alloc(M * elt)) != IOPX_OK) return rc;
     const uint64_t *src = d_high;
     for (int k = 0; k < passes; ++k) {
         // the last pass writes the quotient; before that alternate between the temporary and the quotient buffer
@@ -219,11 +357,11 @@ static int run_division(const uint64_t *d_high, size_t M, size_t min_offset, uin
         memset(&p, 0, sizeof(p));
         for (const Term &t : terms) {
             if (t.off >= M) continue;
-            memcpy(p.consts + 3 * p.nterms, t.c, 24);
+            memcpy(p.consts + words * p.nterms, t.c, elt);
             p.off[p.nterms++] = t.off;
         }
         if (p.nterms == 0) {        // nothing reaches back into the quotient: the factor is 1 on this range
-            if (src != dst) { const int crc_ = iopx::copy_d2d(dst, src, M * 24); if (crc_ != IOPX_OK) return crc_; }
+            if ((rc = copy(dst, src)) != IOPX_OK) return rc;
             src = dst;
             continue;
         }
@@ -262,38 +400,48 @@ int iopx_gf192_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count)
     return IOPX_OK;
 }
 
-static int fp3_elementwise(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count)
+} // extern "C"
+
+template<class F>
+static int fp_elementwise(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count)
 {
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (count == 0) return IOPX_OK;
     if (!d_a || (op != 2 && !d_b) || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    uint64_t c[9];
-    fp_consts(c);
+    uint64_t c[4 * F::WORDS];
+    fp_consts<F>(c);
     TmpBuf dc;
     if ((rc = dc.alloc(sizeof(c))) != IOPX_OK) return rc;
     if ((rc = upload(dc.p, c, sizeof(c))) != IOPX_OK) return rc;
-    if (op == 0) { ProfScope ps_("k_fp3_mul"); hipLaunchKernelGGL(k_fp3_mul, dim3(eo_grid(count)), dim3(256), 0, stream(), d_out, d_a, d_b, (const uint64_t *)dc.u64(), count); }
-    else if (op == 1) { ProfScope ps_("k_fp3_sub"); hipLaunchKernelGGL(k_fp3_sub, dim3(eo_grid(count)), dim3(256), 0, stream(), d_out, d_a, d_b, count); }
-    else { ProfScope ps_("k_fp3_inv"); hipLaunchKernelGGL(k_fp3_inv, dim3(eo_grid(count)), dim3(256), 0, stream(), d_out, d_a, (const uint64_t *)dc.u64(), count); }
+    if (op == 0) { ProfScope ps_(F::mul_label); hipLaunchKernelGGL(F::mul, dim3(eo_grid(count)), dim3(256), 0, stream(), d_out, d_a, d_b, (const uint64_t *)dc.u64(), count); }
+    else if (op == 1) { ProfScope ps_(F::sub_label); hipLaunchKernelGGL(F::sub, dim3(eo_grid(count)), dim3(256), 0, stream(), d_out, d_a, d_b, count); }
+    else { ProfScope ps_(F::inv_label); hipLaunchKernelGGL(F::inv, dim3(F::inv_grid(count)), dim3(256), 0, stream(), d_out, d_a, (const uint64_t *)dc.u64(), count); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
-int iopx_fp3_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return fp3_elementwise(0, d_a, d_b, d_out, count); }
-int iopx_fp3_sub_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return fp3_elementwise(1, d_a, d_b, d_out, count); }
-int iopx_fp3_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count) { return fp3_elementwise(2, d_a, nullptr, d_out, count); }
+extern "C" {
 
-static int lincomb_common(const void *const *d_oracles, size_t num, const uint64_t *coeffs, const uint64_t *constant, size_t n, uint64_t *d_out,
-                          bool prime_field)
+int iopx_fp3_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return fp_elementwise<EoFp>(0, d_a, d_b, d_out, count); }
+int iopx_fp3_sub_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return fp_elementwise<EoFp>(1, d_a, d_b, d_out, count); }
+int iopx_fp3_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count) { return fp_elementwise<EoFp>(2, d_a, nullptr, d_out, count); }
+int iopx_bn128_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return fp_elementwise<EoBn>(0, d_a, d_b, d_out, count); }
+int iopx_bn128_sub_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return fp_elementwise<EoBn>(1, d_a, d_b, d_out, count); }
+int iopx_bn128_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count) { return fp_elementwise<EoBn>(2, d_a, nullptr, d_out, count); }
+
+} // extern "C"
+
+template<class F>
+static int lincomb_common(const void *const *d_oracles, size_t num, const uint64_t *coeffs, const uint64_t *constant, size_t n, uint64_t *d_out)
 {
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_oracles || !coeffs || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
     if (num == 0 || num > LINCOMB_MAX) return fail(IOPX_ERR_INVALID_ARGUMENT, "Random Linear Combination Oracle: Expected same number of evaluations as in registration.");
-    std::vector<uint64_t> hc(coeffs, coeffs + 3 * num);
-    if (prime_field) for (size_t i = 0; i < num; ++i) { const hfp3 t = hfp3::from_words(coeffs + 3 * i).table_form(); memcpy(&hc[3 * i], t.w, 24); }
-    if (constant) hc.insert(hc.end(), constant, constant + 3);
+    std::vector<uint64_t> hc(F::WORDS * num);
+    multiplier_words<F>(coeffs, num, hc.data());
+    if (constant) hc.insert(hc.end(), constant, constant + F::WORDS);
     TmpBuf dc;
     if ((rc = dc.alloc(hc.size() * 8)) != IOPX_OK) return rc;
     if ((rc = upload(dc.p, hc.data(), hc.size() * 8)) != IOPX_OK) return rc;
@@ -301,36 +449,14 @@ static int lincomb_common(const void *const *d_oracles, size_t num, const uint64
     memset(&p, 0, sizeof(p));
     for (size_t i = 0; i < num; ++i) { if (!d_oracles[i]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null oracle"); p.o[i] = (const uint64_t *)d_oracles[i]; }
     p.c = dc.u64(); p.out = d_out; p.num = (int)num; p.n = n; p.has_constant = constant ? 1 : 0;
-    if (prime_field) { ProfScope ps_("k_lincomb_fp3", (num + 1) * n * 24); hipLaunchKernelGGL(k_lincomb_fp3, dim3(eo_grid(n)), dim3(256), 0, stream(), p); }
-    else { ProfScope ps_("k_lincomb_gf192", (num + 1) * n * 24); hipLaunchKernelGGL(k_lincomb_gf192, dim3(eo_grid(n)), dim3(256), 0, stream(), p); }
+    { ProfScope ps_(F::lincomb_label, (num + 1) * n * F::BYTES); hipLaunchKernelGGL(F::lincomb, dim3(eo_grid(n)), dim3(256), 0, stream(), p); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
-int iopx_lincomb_gf192_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out)
-{
-    return lincomb_common(d_oracles, num_oracles, coefficients, nullptr, n, d_out, false);
-}
-int iopx_lincomb_fp3_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out)
-{
-    return lincomb_common(d_oracles, num_oracles, coefficients, nullptr, n, d_out, true);
-}
-// sum_i c_i o_i + constant: single_matrix_denominator::evaluated_contents (libiop/protocols/encoded/lincheck/holographic_lincheck_aux.tcc:117-143)
-int iopx_lincomb_affine_gf192_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
-                                  uint64_t *d_out)
-{
-    if (!constant) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    return lincomb_common(d_oracles, num_oracles, coefficients, constant, n, d_out, false);
-}
-int iopx_lincomb_affine_fp3_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
-                                uint64_t *d_out)
-{
-    if (!constant) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    return lincomb_common(d_oracles, num_oracles, coefficients, constant, n, d_out, true);
-}
-
+template<class F>
 static int spmv_common(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
-                       const uint64_t *scale, int accumulate, uint64_t *d_out, bool prime_field)
+                       const uint64_t *scale, int accumulate, uint64_t *d_out)
 {
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
@@ -339,33 +465,73 @@ static int spmv_common(const uint64_t *d_row_ptr, const uint32_t *d_col, const u
     SpmvParams p;
     p.row_ptr = d_row_ptr; p.col = d_col; p.coeff = d_coeff; p.vec = d_vec; p.out = d_out; p.rows = rows; p.accumulate = accumulate; p.scale = nullptr;
     TmpBuf ds;
-    if (prime_field) {
-        const hfp3 k = (scale ? hfp3::from_words(scale) : hfp3::one()).table_form().table_form();     // r 2^214 raw
-        if ((rc = ds.alloc(24)) != IOPX_OK) return rc;
-        if ((rc = upload(ds.p, k.w, 24)) != IOPX_OK) return rc;
-        p.scale = ds.u64();
-        { ProfScope ps_("k_spmv_fp3"); hipLaunchKernelGGL(k_spmv_fp3, dim3(eo_grid(rows)), dim3(256), 0, stream(), p); }
-    } else {
-        if (scale) {
-            if ((rc = ds.alloc(24)) != IOPX_OK) return rc;
-            if ((rc = upload(ds.p, scale, 24)) != IOPX_OK) return rc;
-            p.scale = ds.u64();
-        }
-        { ProfScope ps_("k_spmv_gf192"); hipLaunchKernelGGL(k_spmv_gf192, dim3(eo_grid(rows)), dim3(256), 0, stream(), p); }
+    uint64_t k[F::WORDS];
+    bool have = scale != nullptr;
+    if constexpr (F::PRIME) {       // always a constant: it also rescales the data x data products (r 2^214 / r 2^266 raw)
+        const typename F::H t = (scale ? F::H::from_words(scale) : F::H::one()).table_form().table_form();
+        memcpy(k, t.w, F::BYTES);
+        have = true;
+    } else if (scale) {
+        memcpy(k, scale, F::BYTES);
     }
+    if (have) {
+        if ((rc = ds.alloc(F::BYTES)) != IOPX_OK) return rc;
+        if ((rc = upload(ds.p, k, F::BYTES)) != IOPX_OK) return rc;
+        p.scale = ds.u64();
+    }
+    { ProfScope ps_(F::spmv_label); hipLaunchKernelGGL(F::spmv, dim3(eo_grid(rows)), dim3(256), 0, stream(), p); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
+}
+
+extern "C" {
+
+int iopx_lincomb_gf192_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out)
+{
+    return lincomb_common<EoGf>(d_oracles, num_oracles, coefficients, nullptr, n, d_out);
+}
+int iopx_lincomb_fp3_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out)
+{
+    return lincomb_common<EoFp>(d_oracles, num_oracles, coefficients, nullptr, n, d_out);
+}
+int iopx_lincomb_bn128_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out)
+{
+    return lincomb_common<EoBn>(d_oracles, num_oracles, coefficients, nullptr, n, d_out);
+}
+// sum_i c_i o_i + constant: single_matrix_denominator::evaluated_contents (libiop/protocols/encoded/lincheck/holographic_lincheck_aux.tcc:117-143)
+int iopx_lincomb_affine_gf192_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
+                                  uint64_t *d_out)
+{
+    if (!constant) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    return lincomb_common<EoGf>(d_oracles, num_oracles, coefficients, constant, n, d_out);
+}
+int iopx_lincomb_affine_fp3_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
+                                uint64_t *d_out)
+{
+    if (!constant) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    return lincomb_common<EoFp>(d_oracles, num_oracles, coefficients, constant, n, d_out);
+}
+int iopx_lincomb_affine_bn128_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
+                                  uint64_t *d_out)
+{
+    if (!constant) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    return lincomb_common<EoBn>(d_oracles, num_oracles, coefficients, constant, n, d_out);
 }
 
 int iopx_spmv_gf192_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
                         const uint64_t *scale, int accumulate, uint64_t *d_out)
 {
-    return spmv_common(d_row_ptr, d_col, d_coeff, rows, d_vec, scale, accumulate, d_out, false);
+    return spmv_common<EoGf>(d_row_ptr, d_col, d_coeff, rows, d_vec, scale, accumulate, d_out);
 }
 int iopx_spmv_fp3_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
                       const uint64_t *scale, int accumulate, uint64_t *d_out)
 {
-    return spmv_common(d_row_ptr, d_col, d_coeff, rows, d_vec, scale, accumulate, d_out, true);
+    return spmv_common<EoFp>(d_row_ptr, d_col, d_coeff, rows, d_vec, scale, accumulate, d_out);
+}
+int iopx_spmv_bn128_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
+                        const uint64_t *scale, int accumulate, uint64_t *d_out)
+{
+    return spmv_common<EoBn>(d_row_ptr, d_col, d_coeff, rows, d_vec, scale, accumulate, d_out);
 }
 
 int iopx_poly_div_vanishing_gf192_dev(const uint64_t *d_poly, size_t n_coeffs, const uint64_t *basis, size_t dim, const uint64_t *shift,
@@ -417,32 +583,43 @@ int iopx_poly_div_vanishing_gf192_dev(const uint64_t *d_poly, size_t n_coeffs, c
     return run_division(d_poly + 3 * N, M, min_off, d_quotient, terms_of_pass, launch);
 }
 
-int iopx_poly_div_vanishing_fp3_dev(const uint64_t *d_poly, size_t n_coeffs, size_t log_order, const uint64_t *shift, uint64_t *d_quotient)
+} // extern "C"
+
+template<class F>
+static int poly_div_vanishing_mul(const uint64_t *d_poly, size_t n_coeffs, size_t log_order, const uint64_t *shift, uint64_t *d_quotient)
 {
+    typedef typename F::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_poly || !shift || !d_quotient) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (log_order > 31) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_order %zu exceeds the 2-adicity of the field", log_order);
+    if (log_order > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_order %zu exceeds the 2-adicity of %s", log_order, F::TWO_ADICITY == 31 ? "the field" : F::NAME);
     const size_t N = (size_t)1 << log_order;
     if (n_coeffs <= N) return IOPX_OK;
     const size_t M = n_coeffs - N;
     // Z = X^N - c, c = shift^N (vanishing_polynomial.tcc:14-25): Q_j = P_{j+N} + c Q_{j+N}
-    hfp3 cur = hfp3::from_words(shift).pow((uint64_t)N);
+    H cur = H::from_words(shift).pow((uint64_t)N);
     int done = 0;
     auto terms_of_pass = [&](int k) {
         while (done < k) { cur = cur.squared(); ++done; }
         Term x;
         x.off = N << k;
-        const hfp3 t = cur.table_form();
-        memcpy(x.c, t.w, 24);
+        const H t = cur.table_form();
+        memcpy(x.c, t.w, F::BYTES);
         return std::vector<Term>(1, x);
     };
     auto launch = [&](const PolyDivParams &p) -> int {
-        { ProfScope ps_("k_polydiv_pass_fp3"); hipLaunchKernelGGL(k_polydiv_pass_fp3, dim3(eo_grid(p.M)), dim3(256), 0, stream(), p); }
+        { ProfScope ps_(F::polydiv_pass_label); hipLaunchKernelGGL(F::polydiv_pass, dim3(eo_grid(p.M)), dim3(256), 0, stream(), p); }
         IOPX_HIP(hipGetLastError());
         return IOPX_OK;
     };
-    return run_division(d_poly + 3 * N, M, N, d_quotient, terms_of_pass, launch);
+    return run_division(d_poly + F::WORDS * N, M, N, d_quotient, terms_of_pass, launch, F::WORDS, F::RAW_INPUTS);
 }
+
+extern "C" {
+
+int iopx_poly_div_vanishing_fp3_dev(const uint64_t *d_poly, size_t n_coeffs, size_t log_order, const uint64_t *shift, uint64_t *d_quotient)
+{ return poly_div_vanishing_mul<EoFp>(d_poly, n_coeffs, log_order, shift, d_quotient); }
+int iopx_poly_div_vanishing_bn128_dev(const uint64_t *d_poly, size_t n_coeffs, size_t log_order, const uint64_t *shift, uint64_t *d_quotient)
+{ return poly_div_vanishing_mul<EoBn>(d_poly, n_coeffs, log_order, shift, d_quotient); }
 
 } // extern "C"

@@ -1027,22 +1027,54 @@ int iopx_bn128_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) { r
 int iopx_fp3_host_pow(const uint64_t *a, uint64_t exponent, uint64_t *out) { return host_pow<FpArm>(a, exponent, out); }
 int iopx_bn128_host_pow(const uint64_t *a, uint64_t exponent, uint64_t *out) { return host_pow<BnArm>(a, exponent, out); }
 
-// ---- single-field entries ----
+} // extern "C"
+
 // d_out[l] = init * base^l for l < count, as ordinary libff elements (multi_lincheck's alpha powers, basic_lincheck_aux.tcc:37-45)
-int iopx_fp3_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init)
+template<class Arm>
+static int pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init)
 {
+    typedef typename Arm::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_out || !base || !init) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
     if (count == 0) return IOPX_OK;
     const int nb = (int)ceil_log2(count);
-    // build_pow writes multipliers (x 2^203); data are x 2^192: start from init 2^-11
-    const hfp3 init_d = hfp3::from_words(init) * hfp3::from_uint(2048).inverse();
-    if (((size_t)1 << nb) == count) return build_pow<FpArm>(d_out, hfp3::from_words(base), init_d, nb);
+    // build_pow writes multipliers (x 2^203 / x 2^261); data are x 2^192 / x 2^256: start from init / TABLE_FACTOR
+    const H init_d = H::from_words(init) * H::from_uint(Arm::TABLE_FACTOR).inverse();
+    if (((size_t)1 << nb) == count) return build_pow<Arm>(d_out, H::from_words(base), init_d, nb);
     TmpBuf full;
-    if ((rc = full.alloc((((size_t)1) << nb) * 24)) != IOPX_OK) return rc;
-    if ((rc = build_pow<FpArm>(full.u64(), hfp3::from_words(base), init_d, nb)) != IOPX_OK) return rc;
-    return iopx::copy_d2d(d_out, full.p, count * 24);
+    if ((rc = full.alloc((((size_t)1) << nb) * Arm::BYTES)) != IOPX_OK) return rc;
+    if ((rc = build_pow<Arm>(full.u64(), H::from_words(base), init_d, nb)) != IOPX_OK) return rc;
+    return iopx::copy_d2d(d_out, full.p, count * Arm::BYTES);
+}
+
+extern "C" {
+
+// ---- single-field entries ----
+int iopx_fp3_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init) { return pow_table_dev<FpArm>(d_out, count, base, init); }
+int iopx_bn128_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init) { return pow_table_dev<BnArm>(d_out, count, base, init); }
+
+int iopx_bn128_host_add(const uint64_t *a, const uint64_t *b, uint64_t *out)
+{
+    if (!a || !b || !out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    const hbn r = hbn::from_words(a) + hbn::from_words(b);
+    memcpy(out, r.w, 32);
+    return IOPX_OK;
+}
+
+int iopx_bn128_host_sub(const uint64_t *a, const uint64_t *b, uint64_t *out)
+{
+    if (!a || !b || !out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    const hbn r = hbn::from_words(a) - hbn::from_words(b);
+    memcpy(out, r.w, 32);
+    return IOPX_OK;
+}
+
+int iopx_bn128_modulus(uint64_t *out)
+{
+    if (!out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    memcpy(out, hbn::P, 32);
+    return IOPX_OK;
 }
 
 int iopx_bn128_from_uint(uint64_t v, uint64_t *out)            // FieldT(v)

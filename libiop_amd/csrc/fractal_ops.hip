@@ -21,6 +21,8 @@
 #include "gf192_host.h"
 #include "fp3_dev.h"
 #include "fp3_host.h"
+#include "bn254_dev.h"
+#include "mul_field.h"
 #include "runtime.h"
 
 namespace iopx {
@@ -239,6 +241,36 @@ __global__ void __launch_bounds__(256) k_div_fp3(DivParams p)
     }
 }
 
+// alt_bn128 Fr: the same chain per lane (running products parked in the output buffer, 4 products per element) with the powers of 2^5 in
+// the place of 2^11, but every lane inverts its own total by Fermat (a bn9_sqr chain, ~330 products): with chains of 16 - 64 elements that
+// is what the LDS tree plus one lane's serial inversion would cost a workgroup, without LDS or barriers.  Multiples of r count as zero.
+__global__ void __launch_bounds__(256) k_bn_div(DivParams p)
+{
+    const size_t T = (size_t)gridDim.x * DIV_LANES;
+    const bn9 k256 = bnw_load(p.consts, 1), one_t = bnw_load(p.consts, 3), unscale_t = bnw_load(p.consts, 4);
+    for (unsigned lane = threadIdx.x; lane < DIV_LANES; lane += blockDim.x) {
+        const size_t tid = (size_t)blockIdx.x * DIV_LANES + lane;
+        if (tid >= p.n) continue;
+        bn9 run = one_t;
+        for (size_t j = tid; j < p.n; j += T) {
+            const bn9 d = bnw_load(p.den, j);
+            run = bn9_mul(run, bn9_is_zero_mod(d) ? k256 : d);  // a zero denominator is stepped over as a stored 1
+            bnw_pack(p.out + 4 * j, run);                       // parked as it is (weak): read back below, never returned
+        }
+        bn9 inv = bn9_mul(bn9_fermat_inverse(run, p.consts + 8), unscale_t);
+        const size_t count = (p.n - tid + T - 1) / T;
+        for (size_t i = count; i-- > 0; ) {
+            const size_t j = tid + i * T;
+            const bn9 d = bnw_load(p.den, j);
+            const bool zero = bn9_is_zero_mod(d);
+            const bn9 before = i ? bnw_load(p.out, j - T) : one_t;
+            const bn9 q = bn9_mul(before, inv);                 // (1 / d) 2^261
+            inv = bn9_mul(inv, zero ? k256 : d);
+            bnw_store_product(p.out, j, zero ? bn9_zero() : bn9_mul(p.num ? bnw_load(p.num, j) : k256, q));
+        }
+    }
+}
+
 // ---- subset sums over an affine subspace: out[j] = tab[0] + sum_{bit k of j} tab[1 + k] --------------------------------------
 __device__ __forceinline__ gf192 fo_subset_sum(const uint64_t *t, int m, uint32_t jlo, uint32_t jhi_uniform)
 {
@@ -260,6 +292,16 @@ __global__ void __launch_bounds__(256) k_geometric_offsets_fp3(uint64_t *out, co
     const fp3 cst = fp_load(c, 0);
     for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x)
         fp_store(out, j, fp_sub(cst, fp_mul(fp_load(hi, j >> 12), fp_load(lo, j & 4095))));
+}
+
+// alt_bn128 Fr: c 1 - hi lo in one reduction (-hi as 8r - hi limb-wise); hi is pre-divided by 2^5
+__global__ void __launch_bounds__(256) k_bn_geometric_offsets(uint64_t *out, const uint64_t *hi, const uint64_t *lo, const uint64_t *c, size_t n)
+{
+    const bn9 cst = bnw_load(c, 0), one_t = bn9_const(BN9_C261);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 a[2] = { bn9_negw(bnw_load(hi, j >> 12)), cst }, b[2] = { bnw_load(lo, j & 4095), one_t };
+        bnw_store_product(out, j, bn9_dot<2>(a, b));
+    }
 }
 
 // ---- rational linear combination: N = sum_i c_i N_i prod_{k != i} D_k, D = prod_k D_k ----------------------------------------
@@ -313,6 +355,42 @@ __global__ void __launch_bounds__(256) k_rational_combine_fp3(RationalParams p)
     }
 }
 
+// alt_bn128 Fr, NUM rationals: the denominators in the 2^261 form (one product with the raw 2^266 each), the last factor of every term
+// joins in one reduction (NUM <= 4 normalised operand pairs: bn9_dot's headroom)
+template<int NUM>
+__device__ __forceinline__ void bn_rational_combine(const RationalParams &p, size_t j)
+{
+    const bn9 k266 = bnw_load(p.c, NUM);
+    bn9 t[NUM], a[NUM], b[NUM];
+#pragma unroll
+    for (int k = 0; k < NUM; ++k) t[k] = bn9_mul(bnw_load(p.D[k], j), k266);
+    bn9 denom = bnw_load(p.D[0], j);
+#pragma unroll
+    for (int k = 1; k < NUM; ++k) denom = bn9_mul(denom, t[k]);
+#pragma unroll
+    for (int i = 0; i < NUM; ++i) {
+        bn9 cur = bn9_mul(bnw_load(p.N[i], j), bnw_load(p.c, i));
+        const int last = i == NUM - 1 ? NUM - 2 : NUM - 1;
+#pragma unroll
+        for (int k = 0; k < NUM; ++k) if (k != i && k != last) cur = bn9_mul(cur, t[k]);
+        a[i] = cur;
+        b[i] = last >= 0 ? t[last] : bnw_load(p.c, NUM + 1);    // a single rational: times the 2^261 form of 1
+    }
+    bnw_store_product(p.outN, j, bn9_dot<NUM>(a, b));
+    if (NUM == 1) bnw_store_product(p.outD, j, bn9_mul(denom, bnw_load(p.c, NUM + 1)));     // D itself, made canonical
+    else bnw_store_product(p.outD, j, denom);
+}
+
+__global__ void __launch_bounds__(256) k_bn_rational_combine(RationalParams p)
+{
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.n; j += (size_t)gridDim.x * blockDim.x) {
+        if (p.num == 1) bn_rational_combine<1>(p, j);
+        else if (p.num == 2) bn_rational_combine<2>(p, j);
+        else if (p.num == 3) bn_rational_combine<3>(p, j);
+        else bn_rational_combine<4>(p, j);
+    }
+}
+
 // ---- rational sumcheck constraint oracle ------------------------------------------------------------------------------------
 // affine subspaces: q(x) = (D(x) (p(x) + eps^-1 mu x^(|K| - 1)) - N(x)) / Z_K(x); x^(|K| - 1) = x^|K| / x with x^|K| a subset sum
 // and 1 / x supplied by the caller (iopx_gf192_div_dev over iopx_domain_offsets_gf192_dev); Z_K is constant on the cosets of K,
@@ -363,21 +441,63 @@ __global__ void __launch_bounds__(256) k_sumcheck_constraint_fp3(uint64_t *out, 
     }
 }
 
-// slots of three words: 0: 2^214 (raw), 1: 2^192 = the stored 1, 2: p - 2, 3: 2^203 = the device form of 1, 4: the device form of 2^-11,
-// 5: 2^609 (raw)
-static void fo_fp_consts(uint64_t (&c)[18])
+// alt_bn128 Fr: s = p x + c 1 in one reduction (data form), D s - N 1 in a second (scale 2^251), the inverse table carries 2^266
+__global__ void __launch_bounds__(256) k_bn_sumcheck_constraint(uint64_t *out, const uint64_t *pp, const uint64_t *N, const uint64_t *D,
+                                                                const uint64_t *xhi, const uint64_t *xlo, const uint64_t *zinv_scaled,
+                                                                const uint64_t *consts, size_t num_cosets, size_t n)
 {
-    const hfp3 k192 = hfp3::one(), k203 = k192.table_form(), k214 = k203.table_form();
-    const hfp3 unscale_t = hfp3::from_uint(2048).inverse().table_form();
-    memcpy(c, k214.w, 24); memcpy(c + 3, k192.w, 24);
-    c[6] = hfp3::P[0] - 2; c[7] = hfp3::P[1]; c[8] = hfp3::P[2];
-    memcpy(c + 9, k203.w, 24);
-    memcpy(c + 12, unscale_t.w, 24);
-    const hfp3 k609 = hfp3::from_uint(2).pow(417);              // stored words of 2^417: 2^417 2^192
-    memcpy(c + 15, k609.w, 24);
+    const bn9 c = bnw_load(consts, 0), one = bnw_load(consts, 1), one_t = bn9_const(BN9_C261);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 sa[2] = { bnw_load(pp, j), c }, sb[2] = { bn9_mul(bnw_load(xhi, j >> 12), bnw_load(xlo, j & 4095)), one_t };
+        const bn9 a[2] = { bnw_load(D, j), bn9_negw(bnw_load(N, j)) }, b[2] = { bn9_dot<2>(sa, sb), one };
+        bnw_store_product(out, j, bn9_mul(bn9_dot<2>(a, b), bnw_load(zinv_scaled, j & (num_cosets - 1))));
+    }
 }
 
-static int div_common(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t n, bool prime_field)
+// The two prime fields' kernels of this file behind one host implementation (mul_field.h)
+struct FoGf : Gf192Field {
+    static constexpr auto div = k_div_gf192; static constexpr const char *div_label = "k_div_gf192";
+    static constexpr size_t DIV_LDS = (size_t)DIV_TREE_NODES * 24 + 8;
+    static constexpr auto rational_combine = k_rational_combine_gf192; static constexpr const char *rational_combine_label = "k_rational_combine_gf192";
+};
+struct FoFp : FpField {
+    static constexpr auto div = k_div_fp3; static constexpr const char *div_label = "k_div_fp3";
+    static constexpr size_t DIV_LDS = (size_t)DIV_TREE_NODES * 24 + 8;
+    static constexpr uint64_t DIV_KEY = 0x646976;           // "div"
+    static constexpr auto geometric_offsets = k_geometric_offsets_fp3; static constexpr const char *geometric_offsets_label = "k_geometric_offsets_fp3";
+    static constexpr auto rational_combine = k_rational_combine_fp3; static constexpr const char *rational_combine_label = "k_rational_combine_fp3";
+    static constexpr auto sumcheck_constraint = k_sumcheck_constraint_fp3; static constexpr const char *sumcheck_constraint_label = "k_sumcheck_constraint_fp3";
+};
+struct FoBn : BnField {
+    static constexpr auto div = k_bn_div; static constexpr const char *div_label = "k_bn_div";
+    static constexpr size_t DIV_LDS = 0;
+    static constexpr uint64_t DIV_KEY = 0x646976626eull;    // "divbn"
+    static constexpr auto geometric_offsets = k_bn_geometric_offsets; static constexpr const char *geometric_offsets_label = "k_bn_geometric_offsets";
+    static constexpr auto rational_combine = k_bn_rational_combine; static constexpr const char *rational_combine_label = "k_bn_rational_combine";
+    static constexpr auto sumcheck_constraint = k_bn_sumcheck_constraint; static constexpr const char *sumcheck_constraint_label = "k_bn_sumcheck_constraint";
+};
+
+// slots of three words: 0: 2^214 (raw), 1: 2^192 = the stored 1, 2: p - 2, 3: 2^203 = the device form of 1, 4: the device form of 2^-11,
+// 5: 2^609 (raw)
+// (alt_bn128 Fr: slots of four words with 2^266, 2^256, r - 2, 2^261, the device form of 2^-5; slot 5 is edwards_Fr's alone)
+template<class F>
+static void fo_fp_consts(uint64_t (&c)[6 * F::WORDS])
+{
+    typedef typename F::H H;
+    const int W = F::WORDS;
+    const H k192 = H::one(), k203 = k192.table_form(), k214 = k203.table_form();
+    const H unscale_t = H::from_uint(F::TABLE_FACTOR).inverse().table_form();
+    memcpy(c, k214.w, F::BYTES); memcpy(c + W, k192.w, F::BYTES);
+    for (int i = 0; i < W; ++i) c[2 * W + i] = H::P[i];
+    c[2 * W] -= 2;
+    memcpy(c + 3 * W, k203.w, F::BYTES);
+    memcpy(c + 4 * W, unscale_t.w, F::BYTES);
+    const H k609 = H::from_uint(2).pow(417);                    // stored words of 2^417: 2^417 2^192
+    memcpy(c + 5 * W, k609.w, F::BYTES);
+}
+
+template<class F>
+static int div_common(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t n)
 {
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
@@ -387,18 +507,16 @@ static int div_common(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_
     DivParams p;
     p.num = d_num; p.den = d_den; p.out = d_out; p.consts = nullptr; p.n = n;
     TmpBuf dc;
-    if (prime_field) {
+    if constexpr (F::PRIME) {
         // the field's own constants: computed once per process, kept on the device
-        rc = cached_domain_table({ 0x646976 /* "div" */ }, [](std::vector<uint64_t> &w) -> int { uint64_t c[18]; fo_fp_consts(c); w.assign(c, c + 18); return IOPX_OK; }, dc);
+        rc = cached_domain_table({ F::DIV_KEY }, [](std::vector<uint64_t> &w) -> int { uint64_t c[6 * F::WORDS]; fo_fp_consts<F>(c); w.assign(c, c + 6 * F::WORDS); return IOPX_OK; }, dc);
         if (rc != IOPX_OK) return rc;
         p.consts = dc.u64();
     }
     // 16 elements per lane while that fills the GPU (the shared inversion is one lane's serial work per workgroup), 2048 workgroups at most
     size_t grid = (n + DIV_LANES * 16 - 1) / (DIV_LANES * 16);
     if (grid > 2048) grid = 2048;
-    const size_t bytes = n * 24 * (d_num ? 5 : 4), lds = (size_t)DIV_TREE_NODES * 24 + 8;
-    if (prime_field) { ProfScope ps_("k_div_fp3", bytes); hipLaunchKernelGGL(k_div_fp3, dim3((unsigned)grid), dim3(256), lds, stream(), p); }
-    else { ProfScope ps_("k_div_gf192", bytes); hipLaunchKernelGGL(k_div_gf192, dim3((unsigned)grid), dim3(256), lds, stream(), p); }
+    { ProfScope ps_(F::div_label, n * F::BYTES * (d_num ? 5 : 4)); hipLaunchKernelGGL(F::div, dim3((unsigned)grid), dim3(256), F::DIV_LDS, stream(), p); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -419,34 +537,37 @@ static int subset_sums(const std::vector<uint64_t> &plain, size_t m, uint64_t *d
     return IOPX_OK;
 }
 
-static int geometric_offsets(const hfp3 &base, const hfp3 &init, const hfp3 &c, size_t log_n, uint64_t *d_out)
+template<class F>
+static int geometric_offsets(const typename F::H &base, const typename F::H &init, const typename F::H &c, size_t log_n, uint64_t *d_out)
 {
+    typedef typename F::H H;
     int rc;
     TmpBuf hi, lo, dc;
-    const hfp3 unscale = hfp3::from_uint(2048).inverse();     // hi * lo comes out as value 2^203; libff's form is value 2^192
+    const H unscale = H::from_uint(F::TABLE_FACTOR).inverse();  // hi * lo comes out as value 2^203 (2^261); libff's form is value 2^192 (2^256)
     if ((rc = build_two_level(base, init * unscale, (int)log_n, hi, lo)) != IOPX_OK) return rc;
-    if ((rc = dc.alloc(24)) != IOPX_OK) return rc;
-    if ((rc = upload(dc.p, c.w, 24)) != IOPX_OK) return rc;
+    if ((rc = dc.alloc(F::BYTES)) != IOPX_OK) return rc;
+    if ((rc = upload(dc.p, c.w, F::BYTES)) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << log_n;
-    { ProfScope ps_("k_geometric_offsets_fp3", n * 24); hipLaunchKernelGGL(k_geometric_offsets_fp3, dim3(fo_grid(n)), dim3(256), 0, stream(), d_out,
+    { ProfScope ps_(F::geometric_offsets_label, n * F::BYTES); hipLaunchKernelGGL(F::geometric_offsets, dim3(fo_grid(n)), dim3(256), 0, stream(), d_out,
                                                                           (const uint64_t *)hi.u64(), (const uint64_t *)lo.u64(), (const uint64_t *)dc.u64(), n); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
+template<class F>
 static int rational_common(const void *const *d_N, const void *const *d_D, size_t num, const uint64_t *coeffs, size_t n, uint64_t *d_outN,
-                           uint64_t *d_outD, bool prime_field)
+                           uint64_t *d_outD)
 {
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_N || !d_D || !coeffs || !d_outN || !d_outD) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
     if (num == 0 || num > RATIONAL_MAX) return fail(IOPX_ERR_INVALID_ARGUMENT, "Expected same number of evaluations as in registration.");
-    std::vector<uint64_t> hc(coeffs, coeffs + 3 * num);
-    if (prime_field) {
-        for (size_t i = 0; i < num; ++i) { const hfp3 t = hfp3::from_words(coeffs + 3 * i).table_form(); memcpy(&hc[3 * i], t.w, 24); }
-        const hfp3 k203 = hfp3::one().table_form(), k214 = k203.table_form();
-        hc.insert(hc.end(), k214.w, k214.w + 3);
-        hc.insert(hc.end(), k203.w, k203.w + 3);
+    std::vector<uint64_t> hc(F::WORDS * num);
+    multiplier_words<F>(coeffs, num, hc.data());
+    if constexpr (F::PRIME) {       // the stored 1 in the device form (2^203 / 2^261) and once more (2^214 / 2^266), in that order after the coefficients: 2^214, 2^203
+        const typename F::H k203 = F::H::one().table_form(), k214 = k203.table_form();
+        hc.insert(hc.end(), k214.w, k214.w + F::WORDS);
+        hc.insert(hc.end(), k203.w, k203.w + F::WORDS);
     }
     TmpBuf dc;
     if ((rc = dc.alloc(hc.size() * 8)) != IOPX_OK) return rc;
@@ -458,9 +579,7 @@ static int rational_common(const void *const *d_N, const void *const *d_D, size_
         p.N[i] = (const uint64_t *)d_N[i]; p.D[i] = (const uint64_t *)d_D[i];
     }
     p.c = dc.u64(); p.outN = d_outN; p.outD = d_outD; p.num = (int)num; p.n = n;
-    const size_t bytes = n * 24 * (2 * num + 2);
-    if (prime_field) { ProfScope ps_("k_rational_combine_fp3", bytes); hipLaunchKernelGGL(k_rational_combine_fp3, dim3(fo_grid(n)), dim3(256), 0, stream(), p); }
-    else { ProfScope ps_("k_rational_combine_gf192", bytes); hipLaunchKernelGGL(k_rational_combine_gf192, dim3(fo_grid(n)), dim3(256), 0, stream(), p); }
+    { ProfScope ps_(F::rational_combine_label, n * F::BYTES * (2 * num + 2)); hipLaunchKernelGGL(F::rational_combine, dim3(fo_grid(n)), dim3(256), 0, stream(), p); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -471,8 +590,9 @@ using namespace iopx;
 
 extern "C" {
 
-int iopx_gf192_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count) { return div_common(d_num, d_den, d_out, count, false); }
-int iopx_fp3_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count) { return div_common(d_num, d_den, d_out, count, true); }
+int iopx_gf192_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count) { return div_common<FoGf>(d_num, d_den, d_out, count); }
+int iopx_fp3_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count) { return div_common<FoFp>(d_num, d_den, d_out, count); }
+int iopx_bn128_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count) { return div_common<FoBn>(d_num, d_den, d_out, count); }
 
 int iopx_domain_offsets_gf192_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)
 {
@@ -486,14 +606,43 @@ int iopx_domain_offsets_gf192_dev(const uint64_t *basis, size_t m, const uint64_
     return subset_sums(tab, m, d_out);
 }
 
-int iopx_domain_offsets_fp3_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)
+} // extern "C"
+
+template<class F>
+static int domain_offsets_mul(size_t log_n, const uint64_t *gen, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)
 {
+    typedef typename F::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!gen || !shift || !point || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (log_n > 31) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of the field", log_n);
-    return geometric_offsets(hfp3::from_words(gen), hfp3::from_words(shift), hfp3::from_words(point), log_n, d_out);
+    if (log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, F::TWO_ADICITY == 31 ? "the field" : F::NAME);
+    return geometric_offsets<F>(H::from_words(gen), H::from_words(shift), H::from_words(point), log_n, d_out);
 }
+
+template<class F>
+static int vanishing_evals_mul(size_t log_n, const uint64_t *gen, const uint64_t *shift, size_t vanishing_log_order, const uint64_t *vanishing_shift,
+                               const uint64_t *constant, uint64_t *d_out)
+{
+    typedef typename F::H H;
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!gen || !shift || !vanishing_shift || !constant || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (F::TWO_ADICITY < 31 && log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, F::NAME);
+    if (log_n > (size_t)F::TWO_ADICITY || vanishing_log_order > 62) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
+    const uint64_t order = (uint64_t)1 << vanishing_log_order;
+    // c - Z_H(x) = (c + shift_H^|H|) - x^|H|
+    const H vp_shift = H::from_words(vanishing_shift).pow(order);
+    const H zero = H();
+    const H c = H::from_words(constant) - (zero - vp_shift);
+    return geometric_offsets<F>(H::from_words(gen).pow(order), H::from_words(shift).pow(order), c, log_n, d_out);
+}
+
+extern "C" {
+
+int iopx_domain_offsets_fp3_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)
+{ return domain_offsets_mul<FoFp>(log_n, gen, shift, point, d_out); }
+int iopx_domain_offsets_bn128_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)
+{ return domain_offsets_mul<FoBn>(log_n, gen, shift, point, d_out); }
 
 int iopx_vanishing_evals_gf192_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *vanishing_basis, size_t vanishing_dim,
                                    const uint64_t *vanishing_shift, const uint64_t *constant, uint64_t *d_out)
@@ -513,28 +662,25 @@ int iopx_vanishing_evals_gf192_dev(const uint64_t *basis, size_t m, const uint64
 
 int iopx_vanishing_evals_fp3_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, size_t vanishing_log_order, const uint64_t *vanishing_shift,
                                  const uint64_t *constant, uint64_t *d_out)
-{
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (!gen || !shift || !vanishing_shift || !constant || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (log_n > 31 || vanishing_log_order > 62) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
-    const uint64_t order = (uint64_t)1 << vanishing_log_order;
-    // c - Z_H(x) = (c + shift_H^|H|) - x^|H|
-    const hfp3 vp_shift = hfp3::from_words(vanishing_shift).pow(order);
-    const hfp3 zero = hfp3();
-    const hfp3 c = hfp3::from_words(constant) - (zero - vp_shift);
-    return geometric_offsets(hfp3::from_words(gen).pow(order), hfp3::from_words(shift).pow(order), c, log_n, d_out);
-}
+{ return vanishing_evals_mul<FoFp>(log_n, gen, shift, vanishing_log_order, vanishing_shift, constant, d_out); }
+int iopx_vanishing_evals_bn128_dev(size_t log_n, const uint64_t *gen, const uint64_t *shift, size_t vanishing_log_order, const uint64_t *vanishing_shift,
+                                   const uint64_t *constant, uint64_t *d_out)
+{ return vanishing_evals_mul<FoBn>(log_n, gen, shift, vanishing_log_order, vanishing_shift, constant, d_out); }
 
 int iopx_rational_combine_gf192_dev(const void *const *d_numerators, const void *const *d_denominators, size_t num_rationals, const uint64_t *coefficients,
                                     size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out)
 {
-    return rational_common(d_numerators, d_denominators, num_rationals, coefficients, n, d_numerator_out, d_denominator_out, false);
+    return rational_common<FoGf>(d_numerators, d_denominators, num_rationals, coefficients, n, d_numerator_out, d_denominator_out);
 }
 int iopx_rational_combine_fp3_dev(const void *const *d_numerators, const void *const *d_denominators, size_t num_rationals, const uint64_t *coefficients,
                                   size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out)
 {
-    return rational_common(d_numerators, d_denominators, num_rationals, coefficients, n, d_numerator_out, d_denominator_out, true);
+    return rational_common<FoFp>(d_numerators, d_denominators, num_rationals, coefficients, n, d_numerator_out, d_denominator_out);
+}
+int iopx_rational_combine_bn128_dev(const void *const *d_numerators, const void *const *d_denominators, size_t num_rationals, const uint64_t *coefficients,
+                                    size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out)
+{
+    return rational_common<FoBn>(d_numerators, d_denominators, num_rationals, coefficients, n, d_numerator_out, d_denominator_out);
 }
 
 int iopx_rational_sumcheck_constraint_gf192_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, const uint64_t *d_xinv, const uint64_t *basis,
@@ -582,31 +728,36 @@ int iopx_rational_sumcheck_constraint_gf192_dev(const uint64_t *d_p, const uint6
     return IOPX_OK;
 }
 
-int iopx_rational_sumcheck_constraint_fp3_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, size_t log_n, const uint64_t *gen,
-                                              const uint64_t *shift, size_t summation_log_order, const uint64_t *summation_shift,
-                                              const uint64_t *claimed_sum, uint64_t *d_out)
+} // extern "C"
+
+template<class F>
+static int rational_sumcheck_constraint_mul(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, size_t log_n, const uint64_t *gen,
+                                            const uint64_t *shift, size_t summation_log_order, const uint64_t *summation_shift,
+                                            const uint64_t *claimed_sum, uint64_t *d_out)
 {
+    typedef typename F::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_p || !d_N || !d_D || !d_out || !gen || !shift || !summation_shift || !claimed_sum) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (summation_log_order > log_n || log_n > 31) return fail(IOPX_ERR_INVALID_ARGUMENT, "the summation domain must be a sub-domain of the codeword domain");
+    if (F::TWO_ADICITY < 31 && log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, F::NAME);
+    if (summation_log_order > log_n || log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "the summation domain must be a sub-domain of the codeword domain");
     const uint64_t order_k = (uint64_t)1 << summation_log_order;
     const size_t cosets = (size_t)1 << (log_n - summation_log_order);
-    const hfp3 g = hfp3::from_words(gen), s = hfp3::from_words(shift), ks = hfp3::from_words(summation_shift);
-    const hfp3 vp_shift = ks.pow(order_k), g_k = g.pow(order_k);
-    hfp3 cur = s.pow(order_k);
-    std::vector<uint64_t> zinv(3 * cosets);
+    const H g = H::from_words(gen), s = H::from_words(shift), ks = H::from_words(summation_shift);
+    const H vp_shift = ks.pow(order_k), g_k = g.pow(order_k);
+    H cur = s.pow(order_k);
+    std::vector<uint64_t> zinv(F::WORDS * cosets);
     for (size_t j = 0; j < cosets; ++j) {
-        const hfp3 z = cur - vp_shift;
+        const H z = cur - vp_shift;
         if (z.is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "the codeword domain intersects the summation domain");
-        const hfp3 zi = z.inverse().table_form().table_form();
-        memcpy(&zinv[3 * j], zi.w, 24);
+        const H zi = z.inverse().table_form().table_form();
+        memcpy(&zinv[F::WORDS * j], zi.w, F::BYTES);
         cur = cur * g_k;
     }
-    const hfp3 c = hfp3::from_uint(order_k).inverse() * hfp3::from_words(claimed_sum);     // mu / |K| (rational_sumcheck.tcc:47-51)
-    const hfp3 one = hfp3::one();
-    uint64_t consts[6];
-    memcpy(consts, c.w, 24); memcpy(consts + 3, one.w, 24);
+    const H c = H::from_uint(order_k).inverse() * H::from_words(claimed_sum);     // mu / |K| (rational_sumcheck.tcc:47-51)
+    const H one = H::one();
+    uint64_t consts[2 * F::WORDS];
+    memcpy(consts, c.w, F::BYTES); memcpy(consts + F::WORDS, one.w, F::BYTES);
     TmpBuf xhi, xlo, dz, dc;
     if ((rc = build_two_level(g, s, (int)log_n, xhi, xlo)) != IOPX_OK) return rc;
     if ((rc = dz.alloc(zinv.size() * 8)) != IOPX_OK) return rc;
@@ -614,12 +765,23 @@ int iopx_rational_sumcheck_constraint_fp3_dev(const uint64_t *d_p, const uint64_
     if ((rc = upload(dz.p, zinv.data(), zinv.size() * 8)) != IOPX_OK) return rc;
     if ((rc = upload(dc.p, consts, sizeof(consts))) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << log_n;
-    { ProfScope ps_("k_sumcheck_constraint_fp3", n * 24 * 4); hipLaunchKernelGGL(k_sumcheck_constraint_fp3, dim3(fo_grid(n)), dim3(256), 0, stream(), d_out, d_p, d_N, d_D,
+    { ProfScope ps_(F::sumcheck_constraint_label, n * F::BYTES * 4); hipLaunchKernelGGL(F::sumcheck_constraint, dim3(fo_grid(n)), dim3(256), 0, stream(), d_out, d_p, d_N, d_D,
                                                                              (const uint64_t *)xhi.u64(), (const uint64_t *)xlo.u64(), (const uint64_t *)dz.u64(),
                                                                              (const uint64_t *)dc.u64(), cosets, n); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
+
+extern "C" {
+
+int iopx_rational_sumcheck_constraint_fp3_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, size_t log_n, const uint64_t *gen,
+                                              const uint64_t *shift, size_t summation_log_order, const uint64_t *summation_shift,
+                                              const uint64_t *claimed_sum, uint64_t *d_out)
+{ return rational_sumcheck_constraint_mul<FoFp>(d_p, d_N, d_D, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out); }
+int iopx_rational_sumcheck_constraint_bn128_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, size_t log_n, const uint64_t *gen,
+                                                const uint64_t *shift, size_t summation_log_order, const uint64_t *summation_shift,
+                                                const uint64_t *claimed_sum, uint64_t *d_out)
+{ return rational_sumcheck_constraint_mul<FoBn>(d_p, d_N, d_D, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out); }
 
 // ---- host helpers: O(dim) field operations for the handful of scalars the protocol layer needs ----
 // Z_S(x) and Z_S's linear coefficient (its formal derivative, vanishing_polynomial.tcc:55-74) for S = span(basis) + shift

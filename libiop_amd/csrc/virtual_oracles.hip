@@ -14,6 +14,8 @@
 #include "gf192_host.h"
 #include "fp3_dev.h"
 #include "fp3_host.h"
+#include "bn254_dev.h"
+#include "mul_field.h"
 #include "runtime.h"
 
 namespace iopx {
@@ -53,6 +55,18 @@ __global__ void __launch_bounds__(256) k_rowcheck_fp(uint64_t *out, const uint64
     }
 }
 
+// alt_bn128 Fr (bn254_dev.h): Az Bz comes out as a b 2^251, Cz joins it at that scale through the stored 1 = 2^256 inside the same
+// reduction, and the inverse table carries 2^266 (table_form twice), exactly as above with 2^5 in the place of 2^11.
+__global__ void __launch_bounds__(256) k_bn_rowcheck(uint64_t *out, const uint64_t *az, const uint64_t *bz, const uint64_t *cz,
+                                                     const uint64_t *zinv_scaled, const uint64_t *one_stored, size_t num_cosets, size_t n)
+{
+    const bn9 one = bnw_load(one_stored, 0);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 a[2] = { bnw_load(az, j), bn9_negw(bnw_load(cz, j)) }, b[2] = { bnw_load(bz, j), one };
+        bnw_store_product(out, j, bn9_mul(bn9_dot<2>(a, b), bnw_load(zinv_scaled, j & (num_cosets - 1))));
+    }
+}
+
 // fz_virtual_oracle::evaluated_contents (libiop/protocols/encoded/r1cs_rs_iop/r1cs_rs_iop.tcc:181-222):
 //     result[x] = fw(x) * Z_I(x) + f_1v(x),      I = the input variable domain, f_1v already extended to the codeword domain.
 // Z_I is an affine linearized polynomial, so Z_I(x_j) = Z_I(shift) + sum_{bit k of j} Z_lin(basis[k])
@@ -80,6 +94,18 @@ __global__ void __launch_bounds__(256) k_fz_fp(uint64_t *out, const uint64_t *fw
     for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
         const fp3 z = fp_sub(fp_mul(fp_load(hi, j >> 12), fp_load(lo, j & 4095)), c);       // table form of Z_I(x_j)
         fp_store(out, j, fp_add(fp_mul(fp_load(fw, j), z), fp_load(f1v, j)));
+    }
+}
+
+// alt_bn128 Fr: fw Z_I + f1v 1 in one reduction (BN9_C261 is the table form of 1); the sum of two products is below 2r
+__global__ void __launch_bounds__(256) k_bn_fz(uint64_t *out, const uint64_t *fw, const uint64_t *f1v, const uint64_t *hi, const uint64_t *lo,
+                                               const uint64_t *vp_shift_t, size_t n)
+{
+    const bn9 c = bnw_load(vp_shift_t, 0), one_t = bn9_const(BN9_C261);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 z = bnw_sub(bn9_mul(bnw_load(hi, j >> 12), bnw_load(lo, j & 4095)), c);  // table form of Z_I(x_j)
+        const bn9 a[2] = { bnw_load(fw, j), bnw_load(f1v, j) }, b[2] = { z, one_t };
+        bnw_store_product(out, j, bn9_dot<2>(a, b));
     }
 }
 
@@ -177,6 +203,18 @@ __global__ void __launch_bounds__(256) k_sumcheck_g_fp(uint64_t *out, const uint
     }
 }
 
+// alt_bn128 Fr: (f - mu / |H|) 1 - h Z_H in one reduction, then times 1 / x_j from the second pair of tables
+__global__ void __launch_bounds__(256) k_bn_sumcheck_g(uint64_t *out, const uint64_t *f, const uint64_t *h, const uint64_t *zhi, const uint64_t *zlo,
+                                                       const uint64_t *ihi, const uint64_t *ilo, const uint64_t *consts, size_t n)
+{
+    const bn9 vp_shift_t = bnw_load(consts, 0), mu_scaled = bnw_load(consts, 1), one_t = bn9_const(BN9_C261);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 z = bnw_sub(bn9_mul(bnw_load(zhi, j >> 12), bnw_load(zlo, j & 4095)), vp_shift_t);
+        const bn9 a[2] = { bnw_sub(bnw_load(f, j), mu_scaled), bn9_negw(bnw_load(h, j)) }, b[2] = { one_t, z };
+        bnw_store_product(out, j, bn9_mul(bn9_dot<2>(a, b), bn9_mul(bnw_load(ihi, j >> 12), bnw_load(ilo, j & 4095))));
+    }
+}
+
 // multi_lincheck_virtual_oracle::evaluated_contents (libiop/protocols/encoded/lincheck/basic_lincheck_aux.tcc:102-144), given
 // p_alpha^1 and p_alpha^2 already extended to the codeword domain (two ordinary transforms, :112-118):
 //     result[x] = (sum_m r_m Mz_m(x)) * p_alpha^1(x) - fz(x) * p_alpha^2(x)
@@ -217,6 +255,35 @@ __global__ void __launch_bounds__(256) k_lincheck_fp(LincheckParams p)
         fp_store(p.out, j, fp_mul(fp_redc(w), rescale));
     }
 }
+
+// alt_bn128 Fr: sum_m r_m Mz_m four products per reduction; comb p1 - fz p2 in one reduction at scale 2^251, the last product
+// with 2^266 restores libff's form
+__global__ void __launch_bounds__(256) k_bn_lincheck(LincheckParams p)
+{
+    const bn9 rescale = bnw_load(p.r, p.num_matrices);
+    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.n; j += (size_t)gridDim.x * blockDim.x) {
+        const bn9 comb = bn9_sum_products([&](size_t m) { return bnw_load(p.mz[m], j); }, [&](size_t m) { return bnw_load(p.r, m); }, 0, (size_t)p.num_matrices);
+        const bn9 a[2] = { comb, bn9_negw(bnw_load(p.fz, j)) }, b[2] = { bnw_load(p.p1, j), bnw_load(p.p2, j) };
+        bnw_store_product(p.out, j, bn9_mul(bn9_dot<2>(a, b), rescale));
+    }
+}
+
+// The two prime fields' kernels of this file behind one host implementation (mul_field.h)
+struct VoGf : Gf192Field {
+    static constexpr auto lincheck = k_lincheck_add; static constexpr const char *lincheck_label = "k_lincheck_add";
+};
+struct VoFp : FpField {
+    static constexpr auto lincheck = k_lincheck_fp; static constexpr const char *lincheck_label = "k_lincheck_fp";
+    static constexpr auto rowcheck = k_rowcheck_fp; static constexpr const char *rowcheck_label = "k_rowcheck_fp";
+    static constexpr auto fz = k_fz_fp; static constexpr const char *fz_label = "k_fz_fp";
+    static constexpr auto sumcheck_g = k_sumcheck_g_fp; static constexpr const char *sumcheck_g_label = "k_sumcheck_g_fp";
+};
+struct VoBn : BnField {
+    static constexpr auto lincheck = k_bn_lincheck; static constexpr const char *lincheck_label = "k_bn_lincheck";
+    static constexpr auto rowcheck = k_bn_rowcheck; static constexpr const char *rowcheck_label = "k_bn_rowcheck";
+    static constexpr auto fz = k_bn_fz; static constexpr const char *fz_label = "k_bn_fz";
+    static constexpr auto sumcheck_g = k_bn_sumcheck_g; static constexpr const char *sumcheck_g_label = "k_bn_sumcheck_g";
+};
 
 static int vo_grid(size_t n)
 {
@@ -309,43 +376,49 @@ int iopx_rowcheck_gf192_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const ui
     return IOPX_OK;
 }
 
-int iopx_rowcheck_fp3_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, size_t log_n, const uint64_t *gen,
-                          const uint64_t *shift, size_t constraint_log_order, const uint64_t *constraint_shift, uint64_t *d_out)
+} // extern "C"
+
+template<class F>
+static int rowcheck_mul(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, size_t log_n, const uint64_t *gen,
+                        const uint64_t *shift, size_t constraint_log_order, const uint64_t *constraint_shift, uint64_t *d_out)
 {
+    typedef typename F::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_Az || !d_Bz || !d_Cz || !d_out || !gen || !shift || !constraint_shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (constraint_log_order > log_n || log_n > 31) return fail(IOPX_ERR_INVALID_ARGUMENT, "the constraint domain must be a sub-domain of the codeword domain");
+    if (F::TWO_ADICITY < 31 && log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, F::NAME);
+    if (constraint_log_order > log_n || log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "the constraint domain must be a sub-domain of the codeword domain");
     const size_t order_h = (size_t)1 << constraint_log_order, cosets = (size_t)1 << (log_n - constraint_log_order);
-    hfp3 g, s, hs;
-    memcpy(g.w, gen, 24); memcpy(s.w, shift, 24); memcpy(hs.w, constraint_shift, 24);
+    const H g = H::from_words(gen), s = H::from_words(shift), hs = H::from_words(constraint_shift);
     // Z_H(shift g^j) = (shift g^j)^|H| - shift_H^|H| for j < |L| / |H|
-    const hfp3 vp_shift = hs.pow(order_h), g_h = g.pow(order_h);
-    hfp3 cur = s.pow(order_h);
-    std::vector<hfp3> z(cosets);
+    const H vp_shift = hs.pow(order_h), g_h = g.pow(order_h);
+    H cur = s.pow(order_h);
+    std::vector<H> z(cosets);
     for (size_t j = 0; j < cosets; ++j) {
         z[j] = cur - vp_shift;
         if (z[j].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "the codeword domain intersects the constraint domain");
         cur = cur * g_h;
     }
     host_batch_inverse(z);
-    std::vector<uint64_t> zinv(3 * cosets);
+    std::vector<uint64_t> zinv(F::WORDS * cosets);
     for (size_t j = 0; j < cosets; ++j) {
-        const hfp3 zi = z[j].table_form().table_form();
-        memcpy(&zinv[3 * j], zi.w, 24);
+        const H zi = z[j].table_form().table_form();
+        memcpy(&zinv[F::WORDS * j], zi.w, F::BYTES);
     }
-    const hfp3 one = hfp3::one();
+    const H one = H::one();
     TmpBuf dz, done;
     if ((rc = dz.alloc(zinv.size() * 8)) != IOPX_OK) return rc;
-    if ((rc = done.alloc(24)) != IOPX_OK) return rc;
+    if ((rc = done.alloc(F::BYTES)) != IOPX_OK) return rc;
     if ((rc = upload(dz.p, zinv.data(), zinv.size() * 8)) != IOPX_OK) return rc;
-    if ((rc = upload(done.p, one.w, 24)) != IOPX_OK) return rc;
+    if ((rc = upload(done.p, one.w, F::BYTES)) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << log_n;
-    { ProfScope ps_("k_rowcheck_fp", 4 * n * 24); hipLaunchKernelGGL(k_rowcheck_fp, dim3(vo_grid(n)), dim3(256), 0, stream(), d_out, d_Az, d_Bz, d_Cz, (const uint64_t *)dz.u64(),
+    { ProfScope ps_(F::rowcheck_label, 4 * n * F::BYTES); hipLaunchKernelGGL(F::rowcheck, dim3(vo_grid(n)), dim3(256), 0, stream(), d_out, d_Az, d_Bz, d_Cz, (const uint64_t *)dz.u64(),
                                                         (const uint64_t *)done.u64(), cosets, n); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
+
+extern "C" {
 
 int iopx_fz_gf192_dev(const uint64_t *d_fw, const uint64_t *d_f1v, const uint64_t *basis, size_t m, const uint64_t *shift,
                       const uint64_t *input_basis, size_t input_dim, const uint64_t *input_shift, uint64_t *d_out)
@@ -379,27 +452,33 @@ int iopx_fz_gf192_dev(const uint64_t *d_fw, const uint64_t *d_f1v, const uint64_
     return IOPX_OK;
 }
 
-int iopx_fz_fp3_dev(const uint64_t *d_fw, const uint64_t *d_f1v, size_t log_n, const uint64_t *gen, const uint64_t *shift,
-                    size_t input_log_order, const uint64_t *input_shift, uint64_t *d_out)
+} // extern "C"
+
+template<class F>
+static int fz_mul(const uint64_t *d_fw, const uint64_t *d_f1v, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                  size_t input_log_order, const uint64_t *input_shift, uint64_t *d_out)
 {
+    typedef typename F::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_fw || !d_f1v || !d_out || !gen || !shift || !input_shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (input_log_order > log_n || log_n > 31) return fail(IOPX_ERR_INVALID_ARGUMENT, "Codeword domain must be bigger than the input variable domain.");
-    hfp3 g, s, is;
-    memcpy(g.w, gen, 24); memcpy(s.w, shift, 24); memcpy(is.w, input_shift, 24);
+    if (F::TWO_ADICITY < 31 && log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, F::NAME);
+    if (input_log_order > log_n || log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "Codeword domain must be bigger than the input variable domain.");
+    const H g = H::from_words(gen), s = H::from_words(shift), is = H::from_words(input_shift);
     const uint64_t order_i = (uint64_t)1 << input_log_order;
     TmpBuf hi, lo, dc;
     if ((rc = build_two_level(g.pow(order_i), s.pow(order_i), (int)log_n, hi, lo)) != IOPX_OK) return rc;
-    const hfp3 c = is.pow(order_i).table_form();
-    if ((rc = dc.alloc(24)) != IOPX_OK) return rc;
-    if ((rc = upload(dc.p, c.w, 24)) != IOPX_OK) return rc;
+    const H c = is.pow(order_i).table_form();
+    if ((rc = dc.alloc(F::BYTES)) != IOPX_OK) return rc;
+    if ((rc = upload(dc.p, c.w, F::BYTES)) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << log_n;
-    { ProfScope ps_("k_fz_fp", 3 * n * 24); hipLaunchKernelGGL(k_fz_fp, dim3(vo_grid(n)), dim3(256), 0, stream(), d_out, d_fw, d_f1v, (const uint64_t *)hi.u64(),
+    { ProfScope ps_(F::fz_label, 3 * n * F::BYTES); hipLaunchKernelGGL(F::fz, dim3(vo_grid(n)), dim3(256), 0, stream(), d_out, d_fw, d_f1v, (const uint64_t *)hi.u64(),
                                                   (const uint64_t *)lo.u64(), (const uint64_t *)dc.u64(), n); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
+
+extern "C" {
 
 int iopx_sumcheck_g_gf192_dev(const uint64_t *d_f, const uint64_t *d_h, const uint64_t *basis, size_t m, const uint64_t *shift,
                               const uint64_t *summation_basis, size_t summation_dim, const uint64_t *summation_shift,
@@ -459,46 +538,51 @@ int iopx_sumcheck_g_gf192_dev(const uint64_t *d_f, const uint64_t *d_h, const ui
     return IOPX_OK;
 }
 
-int iopx_sumcheck_g_fp3_dev(const uint64_t *d_f, const uint64_t *d_h, size_t log_n, const uint64_t *gen, const uint64_t *shift,
-                            size_t summation_log_order, const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out)
+} // extern "C"
+
+template<class F>
+static int sumcheck_g_mul(const uint64_t *d_f, const uint64_t *d_h, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                          size_t summation_log_order, const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out)
 {
+    typedef typename F::H H;
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_f || !d_h || !d_out || !gen || !shift || !summation_shift || !claimed_sum) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (summation_log_order > 62 || log_n > 31) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
-    hfp3 g, s, hs, mu;
-    memcpy(g.w, gen, 24); memcpy(s.w, shift, 24); memcpy(hs.w, summation_shift, 24); memcpy(mu.w, claimed_sum, 24);
+    if (F::TWO_ADICITY < 31 && log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "log_n %zu exceeds the 2-adicity of %s", log_n, F::NAME);
+    if (summation_log_order > 62 || log_n > (size_t)F::TWO_ADICITY) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
+    const H g = H::from_words(gen), s = H::from_words(shift), hs = H::from_words(summation_shift), mu = H::from_words(claimed_sum);
     if (s.is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "zero coset shift");
     const uint64_t order_h = (uint64_t)1 << summation_log_order;
     TmpBuf zhi, zlo, ihi, ilo, dc;
     if ((rc = build_two_level(g.pow(order_h), s.pow(order_h), (int)log_n, zhi, zlo)) != IOPX_OK) return rc;
     if ((rc = build_two_level(g.inverse(), s.inverse(), (int)log_n, ihi, ilo)) != IOPX_OK) return rc;
-    const hfp3 vp_shift_t = hs.pow(order_h).table_form();
-    const hfp3 mu_scaled = hfp3::from_uint(order_h).inverse() * mu;              // |H|^-1 mu, a data value (sumcheck.tcc:46-49)
-    uint64_t consts[6];
-    memcpy(consts, vp_shift_t.w, 24); memcpy(consts + 3, mu_scaled.w, 24);
-    if ((rc = dc.alloc(48)) != IOPX_OK) return rc;
-    if ((rc = upload(dc.p, consts, 48)) != IOPX_OK) return rc;
+    const H vp_shift_t = hs.pow(order_h).table_form();
+    const H mu_scaled = H::from_uint(order_h).inverse() * mu;              // |H|^-1 mu, a data value (sumcheck.tcc:46-49)
+    uint64_t consts[2 * F::WORDS];
+    memcpy(consts, vp_shift_t.w, F::BYTES); memcpy(consts + F::WORDS, mu_scaled.w, F::BYTES);
+    if ((rc = dc.alloc(sizeof(consts))) != IOPX_OK) return rc;
+    if ((rc = upload(dc.p, consts, sizeof(consts))) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << log_n;
-    { ProfScope ps_("k_sumcheck_g_fp", 3 * n * 24); hipLaunchKernelGGL(k_sumcheck_g_fp, dim3(vo_grid(n)), dim3(256), 0, stream(), d_out, d_f, d_h, (const uint64_t *)zhi.u64(),
+    { ProfScope ps_(F::sumcheck_g_label, 3 * n * F::BYTES); hipLaunchKernelGGL(F::sumcheck_g, dim3(vo_grid(n)), dim3(256), 0, stream(), d_out, d_f, d_h, (const uint64_t *)zhi.u64(),
                                                           (const uint64_t *)zlo.u64(), (const uint64_t *)ihi.u64(), (const uint64_t *)ilo.u64(), (const uint64_t *)dc.u64(), n); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
+template<class F>
 static int lincheck_common(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz, const uint64_t *d_p1,
-                           const uint64_t *d_p2, size_t n, uint64_t *d_out, bool prime_field)
+                           const uint64_t *d_p2, size_t n, uint64_t *d_out)
 {
     int rc = ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!d_fz || !d_Mz || !r_Mz || !d_p1 || !d_p2 || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
     if (num_matrices == 0 || num_matrices > LINCHECK_MAX_MATRICES)
         return fail(IOPX_ERR_INVALID_ARGUMENT, "multi_lincheck uses more constituent oracles than what was provided.");
-    std::vector<uint64_t> hr(r_Mz, r_Mz + 3 * num_matrices);
-    if (prime_field) {
-        for (size_t m = 0; m < num_matrices; ++m) { const hfp3 t = hfp3::from_words(r_Mz + 3 * m).table_form(); memcpy(&hr[3 * m], t.w, 24); }
-        const hfp3 k = hfp3::one().table_form().table_form();
-        hr.insert(hr.end(), k.w, k.w + 3);
+    std::vector<uint64_t> hr(F::WORDS * num_matrices);
+    multiplier_words<F>(r_Mz, num_matrices, hr.data());
+    if constexpr (F::PRIME) {       // the rescaling constant of the data x data products
+        const typename F::H k = F::H::one().table_form().table_form();
+        hr.insert(hr.end(), k.w, k.w + F::WORDS);
     }
     TmpBuf dr;
     if ((rc = dr.alloc(hr.size() * 8)) != IOPX_OK) return rc;
@@ -508,22 +592,50 @@ static int lincheck_common(const uint64_t *d_fz, const void *const *d_Mz, size_t
     p.fz = d_fz; p.p1 = d_p1; p.p2 = d_p2; p.out = d_out; p.r = dr.u64();
     for (size_t m = 0; m < num_matrices; ++m) p.mz[m] = (const uint64_t *)d_Mz[m];
     p.num_matrices = (int)num_matrices; p.n = n;
-    if (prime_field) { ProfScope ps_("k_lincheck_fp", (num_matrices + 4) * n * 24); hipLaunchKernelGGL(k_lincheck_fp, dim3(vo_grid(n)), dim3(256), 0, stream(), p); }
-    else { ProfScope ps_("k_lincheck_add", (num_matrices + 4) * n * 24); hipLaunchKernelGGL(k_lincheck_add, dim3(vo_grid(n)), dim3(256), 0, stream(), p); }
+    { ProfScope ps_(F::lincheck_label, (num_matrices + 4) * n * F::BYTES); hipLaunchKernelGGL(F::lincheck, dim3(vo_grid(n)), dim3(256), 0, stream(), p); }
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
+extern "C" {
+
 int iopx_lincheck_gf192_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz,
                             const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out)
 {
-    return lincheck_common(d_fz, d_Mz, num_matrices, r_Mz, d_p_alpha_prime, d_p_alpha_ABC, n, d_out, false);
+    return lincheck_common<VoGf>(d_fz, d_Mz, num_matrices, r_Mz, d_p_alpha_prime, d_p_alpha_ABC, n, d_out);
 }
 
 int iopx_lincheck_fp3_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz,
                           const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out)
 {
-    return lincheck_common(d_fz, d_Mz, num_matrices, r_Mz, d_p_alpha_prime, d_p_alpha_ABC, n, d_out, true);
+    return lincheck_common<VoFp>(d_fz, d_Mz, num_matrices, r_Mz, d_p_alpha_prime, d_p_alpha_ABC, n, d_out);
 }
+
+int iopx_lincheck_bn128_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz,
+                            const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out)
+{
+    return lincheck_common<VoBn>(d_fz, d_Mz, num_matrices, r_Mz, d_p_alpha_prime, d_p_alpha_ABC, n, d_out);
+}
+
+int iopx_rowcheck_fp3_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, size_t log_n, const uint64_t *gen,
+                          const uint64_t *shift, size_t constraint_log_order, const uint64_t *constraint_shift, uint64_t *d_out)
+{ return rowcheck_mul<VoFp>(d_Az, d_Bz, d_Cz, log_n, gen, shift, constraint_log_order, constraint_shift, d_out); }
+int iopx_rowcheck_bn128_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, size_t log_n, const uint64_t *gen,
+                            const uint64_t *shift, size_t constraint_log_order, const uint64_t *constraint_shift, uint64_t *d_out)
+{ return rowcheck_mul<VoBn>(d_Az, d_Bz, d_Cz, log_n, gen, shift, constraint_log_order, constraint_shift, d_out); }
+
+int iopx_fz_fp3_dev(const uint64_t *d_fw, const uint64_t *d_f1v, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                    size_t input_log_order, const uint64_t *input_shift, uint64_t *d_out)
+{ return fz_mul<VoFp>(d_fw, d_f1v, log_n, gen, shift, input_log_order, input_shift, d_out); }
+int iopx_fz_bn128_dev(const uint64_t *d_fw, const uint64_t *d_f1v, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                      size_t input_log_order, const uint64_t *input_shift, uint64_t *d_out)
+{ return fz_mul<VoBn>(d_fw, d_f1v, log_n, gen, shift, input_log_order, input_shift, d_out); }
+
+int iopx_sumcheck_g_fp3_dev(const uint64_t *d_f, const uint64_t *d_h, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                            size_t summation_log_order, const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out)
+{ return sumcheck_g_mul<VoFp>(d_f, d_h, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out); }
+int iopx_sumcheck_g_bn128_dev(const uint64_t *d_f, const uint64_t *d_h, size_t log_n, const uint64_t *gen, const uint64_t *shift,
+                              size_t summation_log_order, const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out)
+{ return sumcheck_g_mul<VoBn>(d_f, d_h, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out); }
 
 } // extern "C"

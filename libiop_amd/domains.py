@@ -29,6 +29,13 @@ class Domain:
             self.basis = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, 3)
             self.shift = np.ascontiguousarray(shift, dtype=np.uint64).reshape(3)
             self.dim = self.basis.shape[0]
+        elif getattr(field, "words", 3) == 4:                            # alt_bn128 Fr: the same coset, four-word elements
+            self.dim = int(log_n)
+            self.shift_int = int(shift) % field.P
+            if self.shift_int == 0:
+                raise ValueError("coset_shift was supplied as 0, it was likely intended to be 1")
+            self.shift = field.from_int(self.shift_int)
+            self.gen = field.subgroup_generator(self.dim)
         else:
             self.dim = int(log_n)
             self.shift_int = int(shift) % la.EDWARDS_FR_MODULUS          # canonical integer
@@ -66,6 +73,8 @@ class Domain:
             if not np.array_equal(self.basis, la.standard_basis(self.dim)):
                 raise ValueError("subspace.element_outside_of_subset() is only supported for standard basis")
             return host.gf_to_words(host.gf_from_words(self.shift) ^ (1 << self.dim))
+        if getattr(self.field, "words", 3) == 4:
+            return (self.shift_int * self.field.GENERATOR) % self.field.P
         return (self.shift_int * la.EDWARDS_FR_GENERATOR) % la.EDWARDS_FR_MODULUS
 
     def reindex_by_subset(self, reindex_subset_dim, index):
@@ -227,6 +236,34 @@ class EdwardsFr:
         return out
 
 
+class AltBn128Fr(EdwardsFr):
+    """libff::alt_bn128_Fr (254 bits, 4 Montgomery limbs, x * 2^256 mod r), multiplicative arm: the device operators of the
+    protocol layer.  No prover runs over it yet: challenge sampling (the hashchain extractor into this field) is not here."""
+    name, additive, elem_bytes, soundness_bits, words = "alt_bn128_Fr", False, 32, 253, 4
+    P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+    GENERATOR, TWO_ADICITY = 5, 28
+
+    def to_int(self, words):
+        v = sum(int(w) << (64 * k) for k, w in enumerate(np.asarray(words, dtype=np.uint64).reshape(4)))
+        return v * pow(1 << 256, -1, self.P) % self.P
+
+    def from_int(self, v):
+        m = int(v) % self.P * (1 << 256) % self.P
+        return np.array([(m >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)], dtype=np.uint64)
+
+    def zero(self):
+        return np.zeros(4, dtype=np.uint64)
+
+    def subgroup_generator(self, log_order):
+        """multiplicative_generator^((r - 1) / 2^log_order) (subgroup.tcc:55-59)"""
+        if log_order > self.TWO_ADICITY:
+            raise ValueError("log_order %d exceeds the 2-adicity of alt_bn128 Fr" % log_order)
+        return self.from_int(pow(self.GENERATOR, (self.P - 1) >> log_order, self.P))
+
+    def squeeze(self, hashchain, n):
+        raise NotImplementedError("challenge sampling into alt_bn128 Fr belongs to the prover over this field")
+
+
 class MerkleTree:
     """A BCS Merkle tree resident on the device: (2L - 1, 32) uint8 nodes in heap order (merkle_tree.tcc:92-229)."""
 
@@ -246,8 +283,17 @@ class DeviceOps:
     """The device operators of the path, dispatched on the domain type.  Vectors are (count, 3) int64 torch tensors on the
     device the library is bound to; every call enqueues on the library's stream and returns without synchronising."""
 
+    def __new__(cls, lib, torch, device, field, *args, **kwargs):
+        # alt_bn128 Fr has its own entries and four-word vectors; GF(2^192) and edwards_Fr run this class as it is.  Only DeviceOps itself is
+        # redirected: a subclass (the sharded operators of libiop_amd/dist.py) is built as asked, and __init__ refuses the field there
+        if cls is DeviceOps and getattr(field, "words", 3) == 4:
+            cls = AltBn128DeviceOps
+        return object.__new__(cls)
+
     def __init__(self, lib, torch, device, field):
         self.lib, self.torch, self.device, self.field = lib, torch, device, field
+        if getattr(field, "words", 3) == 4 and not isinstance(self, AltBn128DeviceOps):
+            raise NotImplementedError("%s: no operators over a four-word field (alt_bn128 Fr runs on one GPU, through DeviceOps)" % type(self).__name__)
         # The provers interleave torch ops (copies, index assignments, torch.cat, buffers recycled by the caching allocator) with
         # library kernels WITHOUT host synchronisation: that is only ordered when both enqueue on the same stream.  Refuse the
         # unshared configuration instead of racing (libiop_amd/dist.py's collectives have their own host-synchronised fallback).
@@ -554,6 +600,183 @@ class DeviceOps:
                 self.lib.poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.basis, domain.shift, out.data_ptr())
             else:
                 self.lib.poly_div_vanishing_multiplicative_dev(d_poly.data_ptr(), n_coeffs, domain.dim, domain.shift, out.data_ptr())
+        return out
+
+
+class AltBn128DeviceOps(DeviceOps):
+    """DeviceOps over AltBn128Fr: (count, 4) int64 vectors, the iopx_*_bn128_dev entries.  Operators without a single-field
+    entry of their own (batches, re-extension) loop over the single-vector ones."""
+    W = 4
+
+    def query_responses(self, d_oracles, domain, positions):
+        return self.lib.query_responses_dev([t.data_ptr() for t in d_oracles], 32, domain.size, positions)
+
+    def empty(self, n):
+        return self.torch.empty((max(int(n), 1), 4), dtype=self.torch.int64, device=self.device)[: int(n)]
+
+    def upload(self, host_words):
+        a = np.ascontiguousarray(host_words, dtype=np.uint64).reshape(-1, 4)
+        t = self.empty(a.shape[0])
+        if a.shape[0]:
+            self.lib.h2d(t.data_ptr(), a)
+        return t
+
+    def download(self, t, count=None):
+        n = t.shape[0] if count is None else count
+        out = np.empty((n, 4), dtype=np.uint64)
+        if n:
+            self.lib.d2h(out, t.data_ptr())
+        return out
+
+    # ---- transforms ----
+    def FFT(self, d_coeffs, n_coeffs, domain):
+        out = self.empty(domain.size)
+        self.lib._check(self.lib.c.iopx_mul_fft_bn128_dev(d_coeffs.data_ptr(), int(n_coeffs), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
+        return out
+
+    def FFT_batch(self, d_coeffs_list, n_coeffs, domain):
+        return [self.FFT(t, n_coeffs, domain) for t in d_coeffs_list]
+
+    def IFFT(self, d_evals, domain):
+        out = self.empty(domain.size)
+        self.lib._check(self.lib.c.iopx_mul_ifft_bn128_dev(d_evals.data_ptr(), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
+        return out
+
+    def IFFT_batch(self, d_evals_list, domain):
+        return [self.IFFT(t, domain) for t in d_evals_list]
+
+    def IFFT_batch_packed(self, packed, batch, domain):
+        n = domain.size
+        return [self.IFFT(packed[k * n:(k + 1) * n], domain) for k in range(batch)]
+
+    def reextend_packed(self, packed, batch, eval_domain, codeword_domain):
+        return self.FFT_batch(self.IFFT_batch_packed(packed, batch, eval_domain), eval_domain.size, codeword_domain)
+
+    def _coset_range(self, codeword_domain, d):
+        raise NotImplementedError("coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
+
+    def IFFT_of_known_degree(self, d_evals, degree, domain):
+        out = self.empty(1 << _log2(degree))
+        self.lib._check(self.lib.c.iopx_mul_ifft_known_degree_bn128_dev(d_evals.data_ptr(), int(degree), domain.dim, _p(domain.gen), _p(domain.shift),
+                                                                        out.data_ptr()))
+        return out
+
+    # ---- FRI / Merkle ----
+    def fold(self, d_f, domain, coset_size, x_i, next_domain=None):
+        out = self.empty(domain.size // coset_size)
+        self.lib._check(self.lib.c.iopx_fri_fold_mul_bn128_dev(d_f.data_ptr(), domain.dim, _p(domain.gen), _p(domain.shift), int(coset_size),
+                                                               _p(x_i), out.data_ptr()))
+        return out
+
+    def merkle_tree(self, d_oracles, domain, coset_size):
+        leaves = domain.size // coset_size
+        nodes = self.torch.empty((2 * leaves - 1, 32), dtype=self.torch.uint8, device=self.device)
+        self.lib.merkle_tree_dev([t.data_ptr() for t in d_oracles], 32, domain.size, coset_size, nodes.data_ptr(), domain_type=domain.domain_type)
+        return MerkleTree(self.lib, nodes, leaves)
+
+    def ldt_combine(self, d_oracles, degrees, random_coefficients, domain):
+        out = self.empty(domain.size)
+        rc = np.ascontiguousarray(random_coefficients, dtype=np.uint64).reshape(-1, 4)
+        if rc.shape[0] != 2 * len(d_oracles):
+            raise ValueError("Expected the nunmber of random coefficients to be twice the number of oracles.")
+        ptrs = (la._vp * len(d_oracles))(*[t.data_ptr() for t in d_oracles])
+        deg = (la._sz * len(degrees))(*[int(d) for d in degrees])
+        self.lib._check(self.lib.c.iopx_ldt_combine_bn128_dev(ptrs, len(d_oracles), deg, _p(rc), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
+        return out
+
+    # ---- virtual oracles ----
+    def rowcheck(self, d_az, d_bz, d_cz, codeword_domain, constraint_domain):
+        out = self.empty(codeword_domain.size)
+        self.lib.bn128_rowcheck_dev(d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift,
+                                    constraint_domain.dim, constraint_domain.shift, out.data_ptr())
+        return out
+
+    def fz(self, d_fw, d_f1v, codeword_domain, input_domain):
+        out = self.empty(codeword_domain.size)
+        self.lib.bn128_fz_dev(d_fw.data_ptr(), d_f1v.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift, input_domain.dim,
+                              input_domain.shift, out.data_ptr())
+        return out
+
+    def sumcheck_g(self, d_f, d_h, codeword_domain, summation_domain, claimed_sum):
+        out = self.empty(codeword_domain.size)
+        self.lib.bn128_sumcheck_g_dev(d_f.data_ptr(), d_h.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift,
+                                      summation_domain.dim, summation_domain.shift, claimed_sum, out.data_ptr())
+        return out
+
+    def lincheck(self, d_fz, d_mz, r_mz, d_p1, d_p2, n):
+        out = self.empty(n)
+        self.lib.bn128_lincheck_dev(d_fz.data_ptr(), [t.data_ptr() for t in d_mz], r_mz, d_p1.data_ptr(), d_p2.data_ptr(), n, out.data_ptr())
+        return out
+
+    def lincomb(self, d_oracles, coefficients, n):
+        out = self.empty(n)
+        self.lib.bn128_lincomb_dev([t.data_ptr() for t in d_oracles], coefficients, n, out.data_ptr())
+        return out
+
+    # ---- vector-sized steps ----
+    def sub(self, d_a, d_b):
+        out = self.empty(d_a.shape[0])
+        self.lib.bn128_sub_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
+        return out
+
+    def mul(self, d_a, d_b):
+        out = self.empty(d_a.shape[0])
+        self.lib.bn128_mul_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
+        return out
+
+    def inv(self, d_a):
+        out = self.empty(d_a.shape[0])
+        self.lib.bn128_inv_dev(d_a.data_ptr(), out.data_ptr(), d_a.shape[0])
+        return out
+
+    def pow_table(self, count, base, init):
+        out = self.empty(count)
+        self.lib.bn128_pow_table_dev(out.data_ptr(), count, base, init)
+        return out
+
+    def spmv(self, csr, d_vec, d_out=None, scale=None, accumulate=False):
+        out = self.empty(csr.rows) if d_out is None else d_out
+        self.lib.bn128_spmv_dev(csr.d_row_ptr.data_ptr(), csr.d_col.data_ptr(), csr.d_coeff.data_ptr(), csr.rows, d_vec.data_ptr(), out.data_ptr(),
+                                scale=scale, accumulate=accumulate)
+        return out
+
+    def div(self, d_num, d_den):
+        out = self.empty(d_den.shape[0])
+        self.lib.bn128_div_dev(d_num.data_ptr() if d_num is not None else None, d_den.data_ptr(), out.data_ptr(), d_den.shape[0])
+        return out
+
+    def domain_offsets(self, domain, point):
+        out = self.empty(domain.size)
+        self.lib.bn128_domain_offsets_dev(domain.dim, domain.gen, domain.shift, point, out.data_ptr())
+        return out
+
+    def vanishing_evals(self, vanishing_domain, domain, constant):
+        out = self.empty(domain.size)
+        self.lib.bn128_vanishing_evals_dev(domain.dim, domain.gen, domain.shift, vanishing_domain.dim, vanishing_domain.shift, constant, out.data_ptr())
+        return out
+
+    def lincomb_affine(self, d_oracles, coefficients, constant, n):
+        out = self.empty(n)
+        self.lib.bn128_lincomb_affine_dev([t.data_ptr() for t in d_oracles], coefficients, constant, n, out.data_ptr())
+        return out
+
+    def rational_combine(self, d_numerators, d_denominators, coefficients, n):
+        N, D = self.empty(n), self.empty(n)
+        self.lib.bn128_rational_combine_dev([t.data_ptr() for t in d_numerators], [t.data_ptr() for t in d_denominators], coefficients, n,
+                                            N.data_ptr(), D.data_ptr())
+        return N, D
+
+    def rational_sumcheck_constraint(self, d_p, d_N, d_D, codeword_domain, summation_domain, claimed_sum):
+        out = self.empty(codeword_domain.size)
+        L, K = codeword_domain, summation_domain
+        self.lib.bn128_rational_sumcheck_constraint_dev(d_p.data_ptr(), d_N.data_ptr(), d_D.data_ptr(), L.dim, L.gen, L.shift, K.dim, K.shift,
+                                                        claimed_sum, out.data_ptr())
+        return out
+
+    def poly_div_vanishing(self, d_poly, n_coeffs, domain, out=None):
+        out = self.empty(max(n_coeffs - domain.size, 0)) if out is None else out
+        if n_coeffs > domain.size:
+            self.lib.bn128_poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.dim, domain.shift, out.data_ptr())
         return out
 
 

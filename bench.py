@@ -12,13 +12,18 @@ the witness already resident in HBM (libiop_amd/aurora.py over the C ABI).
 `value` = the proof's FFT work in the REFERENCE's operation count (per 2^m-point transform 1.5 n m
 multiplications + (n/2) m (m-1)/2 + n m additions, summed over every transform the reference prover runs) divided by the
 prover's wall-clock seconds: prover seconds and FFT field-ops/s in one number; `ms_per_step` is the prover time itself.
-The roofline line is for the dominant kernel of THAT run; config.secondary holds configs[1] (one 2^22 FFT) and
-config.secondary_fractal configs[4]'s Fractal prover on this GPU.
+
+A plain run does what that figure needs and no more: it creates the instance, warms up, times the steps, writes the outputs if asked to and prints the
+line.  Everything else is behind --full: the CPU baseline (the oracle prover on a sample, before the GPU is busy), the second prover's cross-check of
+the transcript, the reference's schedule on the same kernels, one proof under the library's profiler (config.stages_ms, the roofline block: for the
+dominant kernel of THAT run), each rank of 2 / 4 / 8 played alone (config.rank_replay), and config.secondary (configs[1]: one 2^22 FFT),
+config.secondary_fri (configs[2]) and config.secondary_fractal (configs[4]'s Fractal prover on this GPU).  The --no-* options take parts of --full away.
 
 N > 1 (one process per GPU): the SAME native prover, iopx_aurora_prove_dist, with every codeword-domain vector split over the ranks by
 contiguous cosets (libiop_amd/cpp/dist.hpp) and an RCCL communicator created through the C ABI; "strong" scaling: one proof.
 
     python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full                (the same timed steps, then every other figure and check: about half a minute more)
     python bench.py --gpus 1 --steps 5 --warmup 1 --dump-outputs DIR   (also writes DIR/transcript.npy: the last timed proof's bytes)
     python bench.py --gpus N ...                      (starts torch.distributed.run itself, as a child process, when RANK is unset)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
@@ -240,16 +245,109 @@ def rank_replay(lib, torch, native, params, world, rank, steps=5, warmup=2):
             "collectives_per_proof": calls, "collective_payload_bytes_this_rank": payload}
 
 
-def main():
+def kernel_figures(lib, torch, step, log_n, prover_s, world, ref_ops):
+    """--full: one more proof under the library's profiler.  Returns the entries of `config` and the roofline block that are computed from it
+    (prover_s: the timed loop's seconds per proof, ref_ops: the reference's operation count of the proof's transforms)."""
+    # per-kernel durations of one more proof, live, with HIP events on the stream the kernels are launched on.  The timed loop builds every round's
+    # Merkle tree on the library's side stream, beside the next round's transforms; while the profiler records the library keeps those sections
+    # on the main stream (iopx_side_stream_begin), so that every kernel is timed running alone and the durations add up.  The proof before it runs
+    # the same way without the profiler (option IOPX_MERKLE_STREAM = 0, looked up per round): its wall time is what the kernel sum is compared with
+    lib.comm_stats(reset=True)
+    prev_merkle_stream = lib.get_option("IOPX_MERKLE_STREAM", 1)
+    lib.set_option("IOPX_MERKLE_STREAM", 0)
+    try:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        torch.cuda.synchronize()
+        serial_proof_s = time.perf_counter() - t0
+        lib.profile_begin()
+        step()
+        prof = lib.profile_report()
+    finally:
+        lib.set_option("IOPX_MERKLE_STREAM", prev_merkle_stream)
+    comm_calls, comm_bytes = lib.comm_stats()
+    dom_name, (dom_cnt, dom_ms, dom_bytes) = max(prof.items(), key=lambda kv: kv[1][1])
+    dom_avg_s = dom_ms / dom_cnt / 1e3
+    alg_bytes_per_launch = dom_bytes / dom_cnt if dom_bytes else None
+    achieved = (dom_bytes / (dom_ms / 1e3) / 1e9) if dom_bytes else None
+    # HBM bytes per launch of that kernel: NOT measured in this run (PMC counters need rocprofv3 passes of their own) — taken from the
+    # committed PMC run of the same kernels and labelled with its file; null when that run covered other kernel sources
+    traffic, traffic_source = None, None
+    for tname in ("r06_traffic_aurora.json", "r05_traffic_aurora.json"):         # the newest collection whose sources are the ones that run now
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", tname)))
+            if tj.get("log_n") == log_n and dom_name in tj.get("kernels", {}) and tj.get("kernel_sources_sha256") == kernel_sources_digest():
+                traffic = tj["kernels"][dom_name]["traffic_bytes_per_launch"]
+                traffic_source = "profiles/%s (rocprofv3 --pmc passes of this command, collected %s)" % (tname, tj.get("collected", "?"))
+                break
+        except (OSError, ValueError):
+            pass
+    # ALU ceiling: the rate measured live in this run (field products of the launches / their HIP-event time) against the VALU-issue
+    # ceiling of the kernel's instruction mix (tools/alu_model.py: ISA histogram x per-class cycles measured by tools/ubench/valu_rates)
+    products = getattr(lib, "last_profile_products", {})
+    device_products = sum(products.values())          # every field multiplication the profiled proof's kernels reported (this rank)
+    model = alu_model()
+    alu = {}
+    if model:
+        for kname, kmod in model["kernels"].items():
+            # the model's kernels are templates; the profile has one name per instantiation that ran (k_bfly_upper_fwd / _inv, ...): the batch form
+            # of the edge pass has an instruction mix of its own and is left out
+            members = [k for k in prof if k.startswith(kname) and not k.endswith("_batch")]
+            p_sum, ms_sum = sum(products.get(k, 0) for k in members), sum(prof[k][1] for k in members)
+            if p_sum and ms_sum:
+                rate = p_sum / (ms_sum / 1e3)
+                alu[kname] = {"products_per_s": rate, "ceiling_products_per_s": kmod["alu_ceiling_products_per_s"],
+                              "alu_ceiling_frac": rate / kmod["alu_ceiling_products_per_s"], "cycles_per_wave_product_model": kmod["cycles_per_wave_butterfly"]}
+    fft_kernels = ("k_phase1", "k_bfly_upper", "k_bfly_edge", "k_pad_copy", "k_rs_combine", "k_fill")
+    fft_ms = sum(v[1] for k, v in prof.items() if k.startswith(fft_kernels))
+    config = {
+        "stages_ms": device_stages(prof),                # kernel time of one proof under the reference's profiling block names
+        "device_field_products_per_proof": device_products if world == 1 else None,
+        "device_field_products_per_proof_this_rank": device_products,
+        "device_products_per_s": device_products * world / prover_s if device_products else None,
+        "collectives_per_proof": comm_calls, "collective_payload_bytes_per_proof_this_rank": comm_bytes,
+        "fft_stage": {"ms": fft_ms, "field_ops_per_s": ref_ops / (fft_ms / 1e3) if fft_ms else None,
+                      "note": "transform kernels only (k_phase1, k_bfly_upper, k_bfly_edge, padding): HIP-event time inside one proof"},
+    }
+    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic,
+                "kernel": dom_name, "launches_per_step": dom_cnt, "avg_launch_ms": dom_avg_s * 1e3,
+                "algorithmic_bytes_per_launch": alg_bytes_per_launch,
+                "traffic_source": traffic_source,
+                "binding": "integer VALU issue (gfx950 has no carry-less multiply: a GF(2^192) product is ~450-1000 VALU ops)",
+                "alu_ceiling_frac": next((v["alu_ceiling_frac"] for k, v in alu.items() if dom_name.startswith(k)), None),
+                "alu": alu,
+                "note": "frac = algorithmic bytes / HBM peak as the contract asks; the kernel is bound by VALU issue, for which alu_ceiling_frac is the "
+                        "figure: measured products/s over the ceiling of the kernel's instruction mix at the per-class issue costs measured on this GPU "
+                        "(profiles/r06_alu_model.json, profiles/r05_valu_rates.txt)",
+                "kernels_ms_per_step": {k: round(v[1], 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
+                "kernel_launches_per_step": {k: v[0] for k, v in prof.items()},
+                "kernel_algorithmic_bytes_per_launch": {k: round(v[2] / v[0]) for k, v in prof.items() if v[2]},
+                # the profiled proof's kernel time (HIP events) against the timed loop's wall time per proof: launch gaps + host work + read-backs
+                "kernels_ms_total": round(sum(v[1] for v in prof.values()), 3),
+                # idle time between consecutive launches of the profiled proof (HIP events; the longest gaps name the kernels on both sides)
+                "launch_gaps": getattr(lib, "last_profile_gaps", None),
+                "host_gap_ms": round(prover_s * 1e3 - sum(v[1] for v in prof.values()), 3) if prof else None,
+                "host_gap_note": "timed loop's ms per proof minus the profiled proof's kernel sum; negative since round 5: the loop overlaps each round's Merkle tree with the "
+                                 "next round's kernels on a second stream, the profiled proof (ms_per_proof_trees_on_main_stream) does not",
+                "ms_per_proof_trees_on_main_stream": round(serial_proof_s * 1e3, 3)}
+    return config, roofline
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline figure: the CPU baseline, the second prover's cross-check, the "
+                         "reference's schedule, the profiled proof (stages, roofline), the replayed ranks and the secondary workloads; the --no-* options take parts away")
     ap.add_argument("--log-n", type=int, default=20, help="log2 of the number of R1CS constraints")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the oracle prover's sample ahead of the GPU work")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the reference's schedule, the replayed ranks and the secondary workloads")
     ap.add_argument("--no-cross-check", action="store_true",
-                    help="skip the second prover's proof after the timed loop (profiling runs: its reference-schedule launches would mix into the per-kernel counters)")
+                    help="with --full: skip the second prover's proof after the timed loop (profiling runs: its reference-schedule launches would mix into the per-kernel counters)")
     ap.add_argument("--force-sharded", action="store_true",
                     help="use the multi-GPU operator set even with one rank (exercises the RCCL calls on a 1-GPU box; run under torch.distributed.run)")
     ap.add_argument("--throughput", action="store_true",
@@ -260,16 +358,23 @@ def main():
                     help="with --world N on ONE GPU: time rank R of the N-rank prover alone (collectives completed locally; compute path only) and print that line")
     ap.add_argument("--world", type=int, default=8, help="the world size --replay-rank plays a rank of")
     ap.add_argument("--no-warm", action="store_true", help="do not call iopx_aurora_instance_warm: config.first_proof_ms is then the cold first proof")
-    ap.add_argument("--no-rank-replay", action="store_true", help="skip config.rank_replay (ranks 0 and N-1 of 2, 4, 8 played alone on this GPU)")
-    ap.add_argument("--cpu-all-cores", action="store_true", help="also time one independent oracle proof per host core at once (not in the reference, which is single-threaded)")
+    ap.add_argument("--no-rank-replay", action="store_true", help="with --full: skip config.rank_replay (ranks 0 and N-1 of 2, 4, 8 played alone on this GPU)")
+    ap.add_argument("--cpu-all-cores", action="store_true", help="with --full: also time one independent oracle proof per host core at once (not in the reference, which is single-threaded)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one returned (the proof's transcript bytes, as float32) to DIR/transcript.npy; the seeded "
                          "instance is the same on every run, so two builds can be compared output for output")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs is not None and args.replay_rank is not None:
         ap.error("--dump-outputs: a replayed rank's proof is meaningless (collectives completed locally); run without --replay-rank")
+    if not args.full:           # a plain run: the headline figure alone, so every part of --full is off
+        args.no_cpu_baseline = args.no_secondary = args.no_cross_check = args.no_rank_replay = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # RCCL prints a version banner on STDOUT at NCCL_DEBUG=VERSION/INFO (seen on the GPU box: five lines ahead of the JSON line);
     # stdout carries the one JSON line only, so the debug level is pinned to WARN unless IOPX_NCCL_DEBUG says otherwise
@@ -315,14 +420,16 @@ def main():
     else:
         ops = domains.DeviceOps(lib, torch, dev, field)
     n = 1 << args.log_n
-    cs, primary, auxiliary = r1cs.generate_r1cs_example(ops, n, 15, n - 1, SEED)         # untimed: the statement and witness
     params = aurora.AuroraParameters(field, n, n - 1, 15)
-    d_assignment = ops.upload(aurora.assignment_vector(field, primary, auxiliary))      # resident in HBM before the timed region
+    cross_check = world == 1 and not args.no_cross_check
+    if cross_check:             # the Python prover's own copy of the statement and witness, resident in HBM before the timed region
+        cs, primary, auxiliary = r1cs.generate_r1cs_example(ops, n, 15, n - 1, SEED)
+        d_assignment = ops.upload(aurora.assignment_vector(field, primary, auxiliary))
     torch.cuda.synchronize()
 
     # Every N: the native prover behind the C ABI (libiop_amd/cpp/aurora.hpp inside the library; iopx_aurora_prove on one GPU,
     # iopx_aurora_prove_dist over the communicator otherwise — the same code, libiop_amd/cpp/dist.hpp) on its own copy of the same seeded
-    # instance; the Python prover (libiop_amd/aurora.py) proves it once below as a cross-check of the transcript bytes
+    # instance; under --full the Python prover (libiop_amd/aurora.py) proves it once below as a cross-check of the transcript bytes
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     native = lib.aurora_example_instance(0, n, 15, n - 1, SEED)
@@ -400,11 +507,10 @@ def main():
     # the second, independently written prover (libiop_amd/aurora.py; over libiop_amd/dist.py's operators under --force-sharded) on the same
     # instance; with N > 1 ranks rank 0 proves the instance once more on its own GPU alone instead (no collective involved): the distributed
     # transcript must be the single-GPU prover's
-    if world == 1:
-        if not args.no_cross_check:
-            check = aurora.aurora_snark_prover(ops, cs, primary, None, params, d_assignment=d_assignment).serialize()
-            assert check == transcript.serialize(), "native prover's transcript differs from the Python prover's"
-    elif rank == 0 and comm is not None:
+    if cross_check:
+        check = aurora.aurora_snark_prover(ops, cs, primary, None, params, d_assignment=d_assignment).serialize()
+        assert check == transcript.serialize(), "native prover's transcript differs from the Python prover's"
+    elif args.full and world > 1 and rank == 0 and comm is not None:
         assert lib.aurora_prove(native, 128, params.RS_extra_dimensions, 2) == transcript.serialize(), "distributed transcript differs from the single-GPU prover's"
 
     # the same proof by the reference's own schedule (every virtual oracle over the whole codeword domain, coefficient forms: IOPX_HEAD_EVAL=0, read per
@@ -424,60 +530,6 @@ def main():
             lib.clear_option("IOPX_HEAD_EVAL")
         assert t_ref.serialize() == transcript.serialize(), "the two schedules produced different transcripts"
         reference_schedule = {"ms_per_step": ref_s * 1e3, "steps": 5, "transcript_equal": True}
-
-    # per-kernel durations of one more proof, live, with HIP events on the stream the kernels are launched on.  The timed loop builds every round's
-    # Merkle tree on the library's side stream, beside the next round's transforms; while the profiler records the library keeps those sections
-    # on the main stream (iopx_side_stream_begin), so that every kernel is timed running alone and the durations add up.  The proof before it runs
-    # the same way without the profiler (option IOPX_MERKLE_STREAM = 0, looked up per round): its wall time is what the kernel sum is compared with
-    lib.comm_stats(reset=True)
-    prev_merkle_stream = lib.get_option("IOPX_MERKLE_STREAM", 1)
-    lib.set_option("IOPX_MERKLE_STREAM", 0)
-    try:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        serial_proof_s = time.perf_counter() - t0
-        lib.profile_begin()
-        step()
-        prof = lib.profile_report()
-    finally:
-        lib.set_option("IOPX_MERKLE_STREAM", prev_merkle_stream)
-    comm_calls, comm_bytes = lib.comm_stats()
-    dom_name, (dom_cnt, dom_ms, dom_bytes) = max(prof.items(), key=lambda kv: kv[1][1])
-    dom_avg_s = dom_ms / dom_cnt / 1e3
-    alg_bytes_per_launch = dom_bytes / dom_cnt if dom_bytes else None
-    achieved = (dom_bytes / (dom_ms / 1e3) / 1e9) if dom_bytes else None
-    # HBM bytes per launch of that kernel: NOT measured in this run (PMC counters need rocprofv3 passes of their own) — taken from the
-    # committed PMC run of the same kernels and labelled with its file; null when that run covered other kernel sources
-    traffic, traffic_source = None, None
-    for tname in ("r06_traffic_aurora.json", "r05_traffic_aurora.json"):         # the newest collection whose sources are the ones that run now
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", tname)))
-            if tj.get("log_n") == args.log_n and dom_name in tj.get("kernels", {}) and tj.get("kernel_sources_sha256") == kernel_sources_digest():
-                traffic = tj["kernels"][dom_name]["traffic_bytes_per_launch"]
-                traffic_source = "profiles/%s (rocprofv3 --pmc passes of this command, collected %s)" % (tname, tj.get("collected", "?"))
-                break
-        except (OSError, ValueError):
-            pass
-    # ALU ceiling: the rate measured live in this run (field products of the launches / their HIP-event time) against the VALU-issue
-    # ceiling of the kernel's instruction mix (tools/alu_model.py: ISA histogram x per-class cycles measured by tools/ubench/valu_rates)
-    products = getattr(lib, "last_profile_products", {})
-    device_products = sum(products.values())          # every field multiplication the profiled proof's kernels reported (this rank)
-    model = alu_model()
-    alu = {}
-    if model:
-        for kname, kmod in model["kernels"].items():
-            # the model's kernels are templates; the profile has one name per instantiation that ran (k_bfly_upper_fwd / _inv, ...): the batch form
-            # of the edge pass has an instruction mix of its own and is left out
-            members = [k for k in prof if k.startswith(kname) and not k.endswith("_batch")]
-            p_sum, ms_sum = sum(products.get(k, 0) for k in members), sum(prof[k][1] for k in members)
-            if p_sum and ms_sum:
-                rate = p_sum / (ms_sum / 1e3)
-                alu[kname] = {"products_per_s": rate, "ceiling_products_per_s": kmod["alu_ceiling_products_per_s"],
-                              "alu_ceiling_frac": rate / kmod["alu_ceiling_products_per_s"], "cycles_per_wave_product_model": kmod["cycles_per_wave_butterfly"]}
-    fft_kernels = ("k_phase1", "k_bfly_upper", "k_bfly_edge", "k_pad_copy", "k_rs_combine", "k_fill")
-    fft_ms = sum(v[1] for k, v in prof.items() if k.startswith(fft_kernels))
 
     final_dim = params.codeword_domain_dim - sum(params.localization_parameters)
     inventory = aurora_transform_inventory(args.log_n, params.RS_extra_dimensions, final_dim)
@@ -515,7 +567,6 @@ def main():
                                "what": "create: the seeded statement and witness built on the host and moved to HBM; warm: iopx_aurora_instance_warm — the device pool grown to "
                                        "a proof's footprint, plans / twiddle tables / per-domain tables / transposed lincheck matrices built (one discarded proof)",
                                "one_time_costs_ms": one_time_costs, "first_proof_one_time_costs_ms": first_proof_costs},
-            "stages_ms": device_stages(prof),                # kernel time of one proof under the reference's profiling block names
             "prover": ("native: iopx_aurora_prove (libiop_amd/cpp/aurora.hpp behind the C ABI); transcript equal to libiop_amd/aurora.py's" if comm is None else
                        "native: iopx_aurora_prove_dist (libiop_amd/cpp/aurora.hpp + dist.hpp behind the C ABI, RCCL communicator of %d rank(s)); transcript equal to "
                        "the single-GPU prover's" % world),
@@ -523,48 +574,24 @@ def main():
                          "virtual oracles over the head of the codeword domain (as many points as their polynomial has coefficients), f_1 folded there and re-extended, "
                          "confirmed on a second window; h, f_w and f_1 re-extended without coefficient forms (DESIGN.md section 4)"),
             "reference_schedule": reference_schedule,          # field_ops_per_s filled in below
-            "device_field_products_per_proof": device_products if world == 1 else None,
-            "device_field_products_per_proof_this_rank": device_products,
-            "device_products_per_s": device_products * world / prover_s if device_products else None,
-            "collectives_per_proof": comm_calls, "collective_payload_bytes_per_proof_this_rank": comm_bytes,
             "codeword_domain_dim": params.codeword_domain_dim, "localization": params.localization_parameters,
             "fri_query_repetitions": params.fri_query_repetitions, "pow_bits": params.pow_bits,
             "argument_bytes": len(transcript.serialize()) if transcript is not None else None,
             # tests/golden/oracle_aurora_transcript_digests_large.json holds the CPU oracle prover's digest for this instance (2^16, 2^18, 2^20)
             "transcript_blake2b": __import__("hashlib").blake2b(transcript.serialize(), digest_size=32).hexdigest() if transcript is not None else None,
-            # ... and tests/golden/reference_over_shim.json what libiop's OWN prover produced for it (tests/harness: the reference's sources compiled unmodified over a
-            # stand-in libff in the build container; 2^20: 4253 s on one core) — data, read here only to say whether the timed proof is that proof
-            "transcript_equals_the_references_own_prover": reference_own_digest_equal(args.log_n, transcript),
             "ref_fft_mults_per_proof": mults, "ref_fft_adds_per_proof": adds,
-            "fft_stage": {"ms": fft_ms, "field_ops_per_s": (mults + adds) / (fft_ms / 1e3) if fft_ms else None,
-                          "note": "transform kernels only (k_phase1, k_bfly_upper, k_bfly_edge, padding): HIP-event time inside one proof"},
             "multi_gpu": ("throughput mode: %d independent proofs, one per rank, no collective (not BASELINE's sharded config: a labelled secondary figure)" % world
                           if (args.throughput and world > 1) else
                           "one proof sharded over %d ranks by contiguous cosets of every codeword (libiop_amd/cpp/dist.hpp)" % world if world > 1 else "single GPU"),
         },
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic,
-                     "kernel": dom_name, "launches_per_step": dom_cnt, "avg_launch_ms": dom_avg_s * 1e3,
-                     "algorithmic_bytes_per_launch": alg_bytes_per_launch,
-                     "traffic_source": traffic_source,
-                     "binding": "integer VALU issue (gfx950 has no carry-less multiply: a GF(2^192) product is ~450-1000 VALU ops)",
-                     "alu_ceiling_frac": next((v["alu_ceiling_frac"] for k, v in alu.items() if dom_name.startswith(k)), None),
-                     "alu": alu,
-                     "note": "frac = algorithmic bytes / HBM peak as the contract asks; the kernel is bound by VALU issue, for which alu_ceiling_frac is the "
-                             "figure: measured products/s over the ceiling of the kernel's instruction mix at the per-class issue costs measured on this GPU "
-                             "(profiles/r06_alu_model.json, profiles/r05_valu_rates.txt)",
-                     "kernels_ms_per_step": {k: round(v[1], 4) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])},
-                     "kernel_launches_per_step": {k: v[0] for k, v in prof.items()},
-                     "kernel_algorithmic_bytes_per_launch": {k: round(v[2] / v[0]) for k, v in prof.items() if v[2]},
-                     # the profiled proof's kernel time (HIP events) against the timed loop's wall time per proof: launch gaps + host work + read-backs
-                     "kernels_ms_total": round(sum(v[1] for v in prof.values()), 3),
-                     # idle time between consecutive launches of the profiled proof (HIP events; the longest gaps name the kernels on both sides)
-                     "launch_gaps": getattr(lib, "last_profile_gaps", None),
-                     "host_gap_ms": round(prover_s * 1e3 - sum(v[1] for v in prof.values()), 3) if prof else None,
-                     "host_gap_note": "timed loop's ms per proof minus the profiled proof's kernel sum; negative since round 5: the loop overlaps each round's Merkle tree with the "
-                                      "next round's kernels on a second stream, the profiled proof (ms_per_proof_trees_on_main_stream) does not",
-                     "ms_per_proof_trees_on_main_stream": round(serial_proof_s * 1e3, 3)},
     }
+
+    if args.full:
+        figures, out["roofline"] = kernel_figures(lib, torch, step, args.log_n, prover_s, world, mults + adds)
+        out["config"].update(figures)
+        # tests/golden/reference_over_shim.json holds what libiop's OWN prover produced for this instance (tests/harness: the reference's sources compiled
+        # unmodified over a stand-in libff; 2^20: 4253 s on one core) — data, read here only to say whether the timed proof is that proof
+        out["config"]["transcript_equals_the_references_own_prover"] = reference_own_digest_equal(args.log_n, transcript)
 
     if rank == 0 and world == 1 and not args.no_secondary and not args.no_rank_replay:
         # the N-rank prover's per-rank compute path, measured on this GPU: ranks 0 (which evaluates the heads) and N - 1 of 2, 4 and 8

@@ -131,6 +131,19 @@ def test_bench_starts_its_own_ranks_for_several_gpus(monkeypatch):
     assert e.value.code == 0 and len(calls) == 1 and calls[0][1:3] == ["-m", "torch.distributed.run"]
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """`bench.py --gpus 1 --steps N --warmup W` does what its headline figure needs and nothing else: the CPU baseline, the second prover's cross-check,
+    the reference's schedule, the replayed ranks and the secondary workloads are parts of --full, which the --no-* options narrow as before."""
+    import bench
+    parts = ("no_cpu_baseline", "no_secondary", "no_cross_check", "no_rank_replay")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and (plain.steps, plain.warmup) == (3, 1) and all(getattr(plain, p) for p in parts)
+    full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert full.full and (full.steps, full.warmup) == (3, 1) and not any(getattr(full, p) for p in parts)
+    narrowed = bench.parse_args(["--full", "--no-cpu-baseline", "--no-secondary"])
+    assert narrowed.full and narrowed.no_cpu_baseline and narrowed.no_secondary and not narrowed.no_cross_check and not narrowed.no_rank_replay
+
+
 def test_bench_line_helpers():
     """bench.py's round-5 additions that need no GPU: the kernel -> reference-block mapping of one proof's profile, the headline-size CPU figure with the digest
     it was accepted on (the golden digest the GPU tests compare the 2^20 transcript with), and the oracle's block timers under the reference's names."""

@@ -4,7 +4,7 @@ out=$1; shift
 : > "$out"
 for e in "$@"; do
   echo "== $e" >> "$out"
-  env $e python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
+  env $e python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-secondary 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = j['roofline']

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 export IOPX_MERKLE_STREAM=0
 cd /tmp
 STEPS=5; WARM=2
-BENCH="python3 $R/bench.py --steps $STEPS --warmup $WARM --no-cpu-baseline --no-secondary --no-cross-check"
+BENCH="python3 $R/bench.py --steps $STEPS --warmup $WARM --full --no-cpu-baseline --no-secondary --no-cross-check"
 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/${P}_prof -- $BENCH > $R/gpurun_out/${P}_bench_under_rocprof.json 2> $R/gpurun_out/${P}_prof.err
 rocprofv3 --pmc FETCH_SIZE -d $R/gpurun_out/${P}_pmc_fetch -- $BENCH > /dev/null 2> $R/gpurun_out/${P}_pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE -d $R/gpurun_out/${P}_pmc_write -- $BENCH > /dev/null 2> $R/gpurun_out/${P}_pmc_write.err

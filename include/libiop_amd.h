@@ -292,6 +292,9 @@ int iopx_poseidon_shipped_params(int bcs_hash_type, size_t state_size, iopx_pose
 int iopx_bn128_to_montgomery_dev(const uint64_t *d_canonical, uint64_t *d_out, size_t count);
 /* poseidon::apply_permutation (poseidon.tcc:273-297) on `count` states of state_size Montgomery elements, in place. */
 int iopx_poseidon_permute_bn128_dev(const iopx_poseidon_params *params, uint64_t *d_states, size_t count);
+/* The same permutation on ONE state in host memory (no device needed): what the Fiat-Shamir sponge of a proof runs between rounds
+ * (algebraic_hashchain, algebraic_sponge.tcc:136-206). */
+int iopx_poseidon_permute_bn128_host(const iopx_poseidon_params *params, uint64_t *state);
 /* merkle_tree<FieldT, FieldT> with algebraic_leafhash / algebraic_two_to_one_hash over a Poseidon sponge
  * (algebraic_sponge.tcc:18-100,220-265; merkle_tree.tcc:92-151,200-229).  Oracles hold Montgomery elements (32 bytes);
  *   salts   NULL, or num_leaves * 32 bytes: the zk salt of leaf i is parsed as algebraic_sponge.tcc:110-125 does and
@@ -591,6 +594,11 @@ int iopx_fp3_modulus(uint64_t *out);
  * caller releases with iopx_host_free. */
 #define IOPX_FIELD_GF192 0
 #define IOPX_FIELD_EDWARDS_FR 1
+#define IOPX_FIELD_ALT_BN128_FR 2   /* the FRI-only SNARK (iopx_fri_snark_prove, iopx_fri_snark_prove_hashed); no Aurora / Fractal instance over it yet */
+/* bcs_hash_type (libiop/bcs/hashing/hash_enum.hpp:21-26), as iopx_poseidon_shipped_params takes it */
+#define IOPX_HASH_BLAKE2B 1
+#define IOPX_HASH_POSEIDON_STARKWARE 2
+#define IOPX_HASH_POSEIDON_HIGH_ALPHA 3
 typedef struct iopx_r1cs {
     size_t num_constraints, num_variables, num_inputs;
     const uint64_t *row_ptr[3];   /* A, B, C: num_constraints + 1 offsets each */
@@ -628,6 +636,14 @@ int iopx_fractal_prove(iopx_aurora_instance *instance, size_t security_parameter
 int iopx_fri_snark_prove(int field, const uint64_t *d_poly_coeffs, size_t n_coeffs, size_t codeword_domain_dim, size_t RS_extra_dimensions,
                          size_t FRI_localization_parameter, size_t num_interactive_repetitions, size_t num_query_repetitions, uint8_t **transcript,
                          size_t *transcript_bytes);
+/* The same prover with the BCS hash family named (default_bcs_params, common_bcs_parameters.tcc:9-27): IOPX_HASH_BLAKE2B is iopx_fri_snark_prove.  The
+ * Poseidon families exist over IOPX_FIELD_ALT_BN128_FR only (hash_enum.tcc:12-24; IOPX_ERR_INVALID_ARGUMENT otherwise): Poseidon trees with digests that
+ * are field elements (32 bytes of mont_repr in the transcript), the algebraic sponge hashchain — which absorbs every root, so no root is deferred — and
+ * the Poseidon proof of work (work parameter dim + 3 + 7 at cost 128: the same dim + 3 bits).  Over IOPX_FIELD_ALT_BN128_FR coefficients are 4 words per
+ * element (mont_repr) and codeword_domain_dim <= 28; the field has no distributed form (iopx_fri_snark_prove_dist with a communicator fails). */
+int iopx_fri_snark_prove_hashed(int field, int bcs_hash_type, const uint64_t *d_poly_coeffs, size_t n_coeffs, size_t codeword_domain_dim, size_t RS_extra_dimensions,
+                                size_t FRI_localization_parameter, size_t num_interactive_repetitions, size_t num_query_repetitions, uint8_t **transcript,
+                                size_t *transcript_bytes);
 int iopx_aurora_instance_free(iopx_aurora_instance *instance);
 int iopx_host_free(void *p);
 

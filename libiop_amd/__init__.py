@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = [
     "iopx_fractal_index", "iopx_fractal_prove",
     "iopx_memcpy_d2h_deferrable", "iopx_comm_rccl_unique_id", "iopx_comm_create_rccl", "iopx_comm_create_callbacks", "iopx_comm_create_replay", "iopx_comm_is_replay", "iopx_cold_stats", "iopx_cold_add", "iopx_gf192_mul_halves_dev", "iopx_mul_fft_fp3_windows_dev", "iopx_set_option", "iopx_clear_option", "iopx_get_option", "iopx_comm_destroy", "iopx_comm_rank",
     "iopx_comm_all_gather_dev", "iopx_comm_all_reduce_u64_dev", "iopx_comm_broadcast_dev", "iopx_comm_all_to_all_dev", "iopx_comm_sendrecv_dev", "iopx_comm_stats", "iopx_comm_bind_transforms", "iopx_add_taylor_inv_gf192_dev", "iopx_add_combine_inv_gf192_dev",
-    "iopx_interleave_dev", "iopx_gather_rows_dev", "iopx_fri_snark_prove", "iopx_fri_snark_prove_dist", "iopx_add_fft_gf192_dist_dev", "iopx_add_ifft_gf192_dist_dev", "iopx_aurora_prove_dist", "iopx_fractal_index_dist", "iopx_fractal_prove_dist",
+    "iopx_interleave_dev", "iopx_gather_rows_dev", "iopx_fri_snark_prove", "iopx_fri_snark_prove_dist", "iopx_fri_snark_prove_hashed", "iopx_poseidon_permute_bn128_host", "iopx_add_fft_gf192_dist_dev", "iopx_add_ifft_gf192_dist_dev", "iopx_aurora_prove_dist", "iopx_fractal_index_dist", "iopx_fractal_prove_dist",
     "iopx_mul_fft_bn128_dev", "iopx_mul_fft_bn128", "iopx_mul_ifft_bn128_dev", "iopx_mul_ifft_bn128", "iopx_mul_ifft_known_degree_bn128_dev",
     "iopx_fri_fold_mul_bn128_dev", "iopx_fri_fold_mul_bn128", "iopx_ldt_combine_bn128_dev",
     "iopx_bn128_subgroup_generator", "iopx_bn128_multiplicative_generator", "iopx_bn128_host_mul", "iopx_bn128_host_pow", "iopx_bn128_host_inverse", "iopx_bn128_from_uint",
@@ -118,6 +118,10 @@ class _PoseidonParamsC(ctypes.Structure):
 
 def _ints_to_words4(values):
     return np.array([[(int(v) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)] for v in values], dtype=np.uint64).reshape(-1, 4)
+
+
+FIELD_GF192, FIELD_EDWARDS_FR, FIELD_ALT_BN128_FR = 0, 1, 2                 # IOPX_FIELD_*
+HASH_BLAKE2B, HASH_POSEIDON_STARKWARE, HASH_POSEIDON_HIGH_ALPHA = 1, 2, 3   # IOPX_HASH_*: the reference's bcs_hash_type
 
 
 class PoseidonParams:
@@ -602,6 +606,13 @@ class Library:
             self.free(d)
         return st
 
+    def poseidon_permute_host(self, params, state):
+        """The same permutation on one (state_size, 4) Montgomery state on the host (the Fiat-Shamir sponge's): no device needed."""
+        st = np.ascontiguousarray(state, dtype=np.uint64).reshape(params.state_size, 4).copy()
+        self.c.iopx_poseidon_permute_bn128_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self.c.iopx_poseidon_permute_bn128_host(ctypes.byref(params.c), _vp(st.ctypes.data)))
+        return st
+
     def merkle_tree_poseidon(self, params, oracles, coset_size, domain_type=DOMAIN_MULTIPLICATIVE, salts=None):
         """merkle_tree<FieldT, FieldT> with the algebraic leaf / two-to-one hashes (algebraic_sponge.tcc:220-265).
         Returns the (2L-1, 4) uint64 node array (Montgomery words), row 0 = get_root()."""
@@ -1044,8 +1055,16 @@ class Library:
         return self._transcript_call(self.c.iopx_fractal_prove_dist, instance, comm, int(security_parameter), int(RS_extra_dimensions), int(FRI_localization_parameter))
 
     def fri_snark_prove(self, field_code, d_poly_coeffs, n_coeffs, codeword_domain_dim, RS_extra_dimensions, FRI_localization_parameter=2,
-                        num_interactive_repetitions=1, num_query_repetitions=10, comm=None):
-        """FRI_snark_prover through the C ABI (libiop_amd/cpp/fri.hpp inside the library): the canonical transcript bytes; `comm`: distributed."""
+                        num_interactive_repetitions=1, num_query_repetitions=10, comm=None, hash=None):
+        """FRI_snark_prover through the C ABI (libiop_amd/cpp/fri.hpp inside the library): the canonical transcript bytes; `comm`: distributed.
+        `hash`: a bcs_hash_type (HASH_BLAKE2B, HASH_POSEIDON_STARKWARE, HASH_POSEIDON_HIGH_ALPHA) through iopx_fri_snark_prove_hashed; None: BLAKE2b."""
+        if hash is not None:
+            if comm is not None:
+                raise ValueError("the hashed entry has no distributed form")
+            self.c.iopx_fri_snark_prove_hashed.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _sz, _sz, _sz, _sz, _sz, _sz, ctypes.POINTER(ctypes.c_void_p),
+                                                            ctypes.POINTER(_sz)]
+            return self._transcript_call(self.c.iopx_fri_snark_prove_hashed, int(field_code), int(hash), _vp(d_poly_coeffs), int(n_coeffs), int(codeword_domain_dim),
+                                         int(RS_extra_dimensions), int(FRI_localization_parameter), int(num_interactive_repetitions), int(num_query_repetitions))
         self.c.iopx_fri_snark_prove_dist.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, _sz, _sz, _sz, _sz, _sz, _sz, ctypes.POINTER(ctypes.c_void_p),
                                                       ctypes.POINTER(_sz)]
         return self._transcript_call(self.c.iopx_fri_snark_prove_dist, int(field_code), comm, _vp(d_poly_coeffs), int(n_coeffs), int(codeword_domain_dim),

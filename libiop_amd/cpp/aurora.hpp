@@ -36,10 +36,22 @@ template<typename FieldT> struct held_words {
 template<typename FieldT> inline held_words<FieldT> shift_words(const field_subset<FieldT> &D) { return held_words<FieldT>{ D.shift() }; }
 template<typename FieldT> inline held_words<FieldT> gen_words(const field_subset<FieldT> &D) { return held_words<FieldT>{ D.generator() }; }
 template<typename FieldT> inline bool additive(const field_subset<FieldT> &D) { return D.type() == affine_subspace_type; }
+// 32-byte elements are alt_bn128 Fr's (multiplicative cosets only, one GPU): the _bn128 entries of the same seams
+template<typename FieldT> struct is_bn128 { static const bool value = sizeof(FieldT) == 32; };
+template<typename FieldT> inline void require_whole(const field_subset<FieldT> &D)
+{
+    if (is_bn128<FieldT>::value && (D.distributed() || additive(D))) throw std::invalid_argument("alt_bn128 Fr: multiplicative cosets on one GPU only");
+}
 
 template<typename FieldT>
 device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coeffs, const field_subset<FieldT> &D)            // fft.tcc:407-419
 {
+    require_whole(D);
+    if (is_bn128<FieldT>::value) {                                                           // no window outputs from this transform: the prover gathers them
+        device_vector<FieldT> out(D.num_elements());
+        check(iopx_mul_fft_bn128_dev(coeffs.words(), n_coeffs, D.dimension(), gen_words(D), shift_words(D), out.words()));
+        return out;
+    }
     if (D.distributed()) {                                                                   // dist.hpp: this rank's part of the codeword
         device_vector<FieldT> out(dist::local_size(D));
         if (additive(D)) {                                                                   // its coset range of the transform; phase 1 on the coefficients is replicated
@@ -81,8 +93,10 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
 {
     if (D.distributed()) throw std::logic_error("inverse transform of a distributed vector: gather it first");
     if (evals.size() != D.num_elements()) throw std::invalid_argument("IFFT: evaluation count != domain size");
+    require_whole(D);
     device_vector<FieldT> out(D.num_elements());
-    if (additive(D)) check(iopx_add_ifft_gf192_dev(evals.words(), basis_words(D), D.dimension(), shift_words(D), out.words()));
+    if (is_bn128<FieldT>::value) check(iopx_mul_ifft_bn128_dev(evals.words(), D.dimension(), gen_words(D), shift_words(D), out.words()));
+    else if (additive(D)) check(iopx_add_ifft_gf192_dev(evals.words(), basis_words(D), D.dimension(), shift_words(D), out.words()));
     else check(iopx_mul_ifft_fp3_dev(evals.words(), D.dimension(), gen_words(D), shift_words(D), out.words()));
     return out;
 }
@@ -197,6 +211,12 @@ template<typename FieldT>
 device_vector<FieldT> IFFT_of_known_degree(const device_vector<FieldT> &evals, std::size_t degree, const field_subset<FieldT> &D)
 {
     const std::size_t k = detail::log2_ceil(degree), count = (std::size_t)1 << k;
+    require_whole(D);
+    if (is_bn128<FieldT>::value) {
+        device_vector<FieldT> out(count);
+        check(iopx_mul_ifft_known_degree_bn128_dev(evals.words(), degree, D.dimension(), gen_words(D), shift_words(D), out.words()));
+        return out;
+    }
     if (D.distributed()) {
         // Subspaces read the first 2^k evaluations (fft.tcc:458-475): rank 0's head.  Cosets read every (|D| / 2^k)-th (fft.tcc:435-456):
         // all on rank 0 while that stride is a multiple of N, at stride / N in its sub-coset (whose shift is the domain's).  Rank 0
@@ -231,8 +251,10 @@ device_vector<FieldT> fold(const device_vector<FieldT> &f, const field_subset<Fi
         return next_distributed ? part : dist::gather_layout<FieldT>(part, D_in.type());
     }
     const field_subset<FieldT> &D = D_in;
+    require_whole(D);
     device_vector<FieldT> out(D.num_elements() / coset_size);
-    if (additive(D)) check(iopx_fri_fold_add_gf192_dev(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    if (is_bn128<FieldT>::value) check(iopx_fri_fold_mul_bn128_dev(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    else if (additive(D)) check(iopx_fri_fold_add_gf192_dev(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
     else check(iopx_fri_fold_mul_fp3_dev(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
     return out;
 }
@@ -572,7 +594,11 @@ public:
         const field_subset<FieldT> L = dist::local_domain(D);
         const std::vector<const void *> ptrs = dev::pointers(c);
         device_vector<FieldT> out(L.num_elements());
-        if (dev::additive(L))
+        dev::require_whole(L);
+        if (dev::is_bn128<FieldT>::value)
+            check(iopx_ldt_combine_bn128_dev(ptrs.data(), ptrs.size(), degrees_.data(), detail::words(coefficients_.data()), L.dimension(), dev::gen_words(L),
+                                             dev::shift_words(L), out.words()));
+        else if (dev::additive(L))
             check(iopx_ldt_combine_gf192_dev(ptrs.data(), ptrs.size(), degrees_.data(), detail::words(coefficients_.data()), dev::basis_words(L), L.dimension(),
                                              dev::shift_words(L), out.words()));
         else

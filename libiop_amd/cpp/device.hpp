@@ -12,7 +12,7 @@
 namespace libiop_amd {
 
 // ---- host scalars of FieldT (per-proof constants only) --------------------------------------------------------------------------
-template<typename FieldT>
+template<typename FieldT, std::size_t Bytes = sizeof(FieldT)>
 struct field_host {
     static_assert(sizeof(FieldT) == 24, "libiop_amd accelerates 24-byte field elements (libff::gf192 / libff::edwards_Fr layout)");
     static bool additive() { return field_kind<FieldT>::type == affine_subspace_type; }
@@ -100,6 +100,31 @@ struct field_host {
     }
     // libff::soundness_log_of_field_size_helper: the extension degree for binary fields, floor(log2 p) for prime fields
     static std::size_t soundness_bits() { return additive() ? 192 : 180; }
+};
+
+// 32-byte elements: libff::alt_bn128_Fr's layout (four Montgomery limbs), multiplicative cosets only; the iopx_bn128_* host helpers
+template<typename FieldT>
+struct field_host<FieldT, 32> {
+    static bool additive() { return false; }
+    static FieldT from_words(const uint64_t *w) { FieldT r; std::memcpy((void *)&r, w, 32); return r; }
+    static FieldT zero() { const uint64_t w[4] = { 0, 0, 0, 0 }; return from_words(w); }
+    static FieldT from_uint(uint64_t v) { uint64_t w[4]; check(iopx_bn128_from_uint(v, w)); return from_words(w); }
+    static FieldT one() { return from_uint(1); }
+    static bool is_zero(const FieldT &a) { const uint64_t *w = detail::words(&a); return (w[0] | w[1] | w[2] | w[3]) == 0; }
+    static FieldT add(const FieldT &a, const FieldT &b) { uint64_t w[4]; check(iopx_bn128_host_add(detail::words(&a), detail::words(&b), w)); return from_words(w); }
+    static FieldT sub(const FieldT &a, const FieldT &b) { uint64_t w[4]; check(iopx_bn128_host_sub(detail::words(&a), detail::words(&b), w)); return from_words(w); }
+    static FieldT mul(const FieldT &a, const FieldT &b) { uint64_t w[4]; check(iopx_bn128_host_mul(detail::words(&a), detail::words(&b), w)); return from_words(w); }
+    static FieldT pow(const FieldT &a, uint64_t e) { uint64_t w[4]; check(iopx_bn128_host_pow(detail::words(&a), e, w)); return from_words(w); }
+    static FieldT neg(const FieldT &a) { return sub(zero(), a); }
+    static FieldT inverse(const FieldT &a) { uint64_t w[4]; check(iopx_bn128_host_inverse(detail::words(&a), w)); return from_words(w); }
+    static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x) { return sub(pow(x, S.num_elements()), pow(S.shift(), S.num_elements())); }
+    static FieldT vanishing_derivative(const field_subset<FieldT> &S, const FieldT &x) { return mul(from_uint(S.num_elements()), pow(x, S.num_elements() - 1)); }
+    static bool element_in_domain(const field_subset<FieldT> &S, const FieldT &x)
+    {
+        const FieldT r = pow(mul(x, inverse(S.shift())), S.num_elements()), o = one();
+        return std::memcmp(&r, &o, sizeof(FieldT)) == 0;
+    }
+    static std::size_t soundness_bits() { return 253; }                  // floor(log2 r)
 };
 
 // ---- device memory -----------------------------------------------------------------------------------------------------------------

@@ -112,11 +112,11 @@ field_subset<FieldT> local_domain(const field_subset<FieldT> &D, std::size_t ran
     if (rank == (std::size_t)-1) rank = c.rank;
     if (D.type() == affine_subspace_type) {
         const std::size_t m = D.dimension(), r = c.log_world;
-        uint64_t s[3];
+        uint64_t s[sizeof(FieldT) / 8];
         const FieldT D_shift = D.shift();
-        std::memcpy(s, detail::words(&D_shift), 24);
+        std::memcpy(s, detail::words(&D_shift), sizeof(FieldT));
         for (std::size_t k = 0; k < r; ++k)
-            if ((rank >> k) & 1) for (int w = 0; w < 3; ++w) s[w] ^= detail::words(&D.basis()[m - r + k])[w];
+            if ((rank >> k) & 1) for (std::size_t w = 0; w < sizeof(FieldT) / 8; ++w) s[w] ^= detail::words(&D.basis()[m - r + k])[w];
         return field_subset<FieldT>(affine_subspace<FieldT>(std::vector<FieldT>(D.basis().begin(), D.basis().begin() + (m - r)), field_host<FieldT>::from_words(s)));
     }
     // (shift g^rank) <g^N>: the default generator of order n / N is g^N (subgroup.tcc:55-59: multiplicative_generator^((p - 1) / order))
@@ -168,11 +168,11 @@ field_subset<FieldT> window_domain(const field_subset<FieldT> &D, const window &
     if (D.type() == affine_subspace_type) {
         const std::size_t d = detail::log2_ceil(w.count);
         if (w.stride != 1 || ((std::size_t)1 << d) != w.count || w.first % w.count || w.first + w.count > D.num_elements()) throw std::invalid_argument("not a window of this subspace");
-        uint64_t s[3];                                        // element_by_index(first) (subspace.tcc:56-71)
+        uint64_t s[sizeof(FieldT) / 8];                       // element_by_index(first) (subspace.tcc:56-71)
         const FieldT D_shift = D.shift();
-        std::memcpy(s, detail::words(&D_shift), 24);
+        std::memcpy(s, detail::words(&D_shift), sizeof(FieldT));
         for (std::size_t k = d; k < D.dimension(); ++k)
-            if ((w.first >> k) & 1) for (int i = 0; i < 3; ++i) s[i] ^= detail::words(&D.basis()[k])[i];
+            if ((w.first >> k) & 1) for (std::size_t i = 0; i < sizeof(FieldT) / 8; ++i) s[i] ^= detail::words(&D.basis()[k])[i];
         return field_subset<FieldT>(affine_subspace<FieldT>(std::vector<FieldT>(D.basis().begin(), D.basis().begin() + d), field_host<FieldT>::from_words(s)));
     }
     if (w.count * w.stride != D.num_elements() || w.first >= w.stride) throw std::invalid_argument("not a window of this coset");

@@ -64,12 +64,14 @@ public:
 
 // FRI_snark_prover (fri_snark.tcc:43-77): commits, reduces and folds the codeword of the polynomial with the given coefficients (at most
 // poly_degree_bound of them, resident in HBM) — over a distributed codeword domain (dist.hpp) each rank extends its own part.
+// HashPolicy: `blake2b` (the default: what default_bcs_params wires for every field) or `poseidon` (alt_bn128 Fr only), iop.hpp.
 namespace detail {
-template<typename FieldT, typename Finish>
-auto run_FRI_prover(const device_vector<FieldT> &poly_coefficients, const FRI_snark_parameters &parameters, Finish finish) -> decltype(finish(std::declval<bcs_prover<FieldT> &>()))
+template<typename FieldT, typename HashPolicy, typename Finish>
+auto run_FRI_prover(const device_vector<FieldT> &poly_coefficients, const FRI_snark_parameters &parameters, const HashPolicy &hash, Finish finish)
+    -> decltype(finish(std::declval<bcs_prover<FieldT> &>()))
 {
     if (poly_coefficients.size() > parameters.poly_degree_bound_) throw std::invalid_argument("more coefficients than the tested degree bound");
-    bcs_prover<FieldT> IOP(parameters.pow_bits_);
+    bcs_prover<FieldT> IOP(parameters.pow_bits_, nullptr, hash.template family<FieldT>());
     FRI_iop_protocol<FieldT> protocol(IOP, parameters);
     protocol.register_interactions();
     IOP.seal_interaction_registrations();
@@ -80,16 +82,16 @@ auto run_FRI_prover(const device_vector<FieldT> &poly_coefficients, const FRI_sn
 }
 } // namespace detail
 
-template<typename FieldT>
-bcs_transformation_transcript<FieldT> FRI_snark_prover(const device_vector<FieldT> &poly_coefficients, const FRI_snark_parameters &parameters)
+template<typename FieldT, typename HashPolicy = blake2b>
+bcs_transformation_transcript<FieldT> FRI_snark_prover(const device_vector<FieldT> &poly_coefficients, const FRI_snark_parameters &parameters, const HashPolicy &hash = HashPolicy())
 {
-    return detail::run_FRI_prover<FieldT>(poly_coefficients, parameters, [](bcs_prover<FieldT> &IOP) { return IOP.get_transcript(); });
+    return detail::run_FRI_prover<FieldT>(poly_coefficients, parameters, hash, [](bcs_prover<FieldT> &IOP) { return IOP.get_transcript(); });
 }
 
-template<typename FieldT>
-std::string FRI_snark_prover_serialized(const device_vector<FieldT> &poly_coefficients, const FRI_snark_parameters &parameters)
+template<typename FieldT, typename HashPolicy = blake2b>
+std::string FRI_snark_prover_serialized(const device_vector<FieldT> &poly_coefficients, const FRI_snark_parameters &parameters, const HashPolicy &hash = HashPolicy())
 {
-    return detail::run_FRI_prover<FieldT>(poly_coefficients, parameters, [](bcs_prover<FieldT> &IOP) { return IOP.get_transcript_bytes(); });
+    return detail::run_FRI_prover<FieldT>(poly_coefficients, parameters, hash, [](bcs_prover<FieldT> &IOP) { return IOP.get_transcript_bytes(); });
 }
 
 } // namespace libiop_amd

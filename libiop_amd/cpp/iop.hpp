@@ -7,13 +7,15 @@
 //   device_vector<FieldT>                       the storage behind oracle<FieldT> (pooled device memory, iopx_pool_alloc)
 //   oracle<FieldT>, virtual_oracle<FieldT>      iop/oracles.hpp:22-95 (evaluated_contents() downloads lazily)
 //   blake2b_hashchain<FieldT>                   bcs/hashing/blake2b.tcc:10-110, 162-257, blake2b.cpp:50-74 (host, 32-byte state)
+//   algebraic_hashchain<FieldT>                 bcs/hashing/algebraic_sponge.tcc:18-100, 136-206 over Poseidon (host; alt_bn128 Fr)
+//   bcs_hash_family<FieldT>, blake2b, poseidon  the hash family of a proof: hashchain + trees + proof of work (common_bcs_parameters.tcc:9-27)
 //   bcs_prover<FieldT>                          iop.tcc:22-433 registration + rounds, bcs_common.tcc:399-696 one tree per
 //                                               (round, domain), bcs_prover.tcc:23-98 round end + proof of work, :136-233 transcript
 //   bcs_transformation_transcript<FieldT>       bcs/bcs_common.hpp:36-106
 //
 // Only 32-byte roots, O(log n) challenges and, at the end, the queried values and authentication paths cross PCIe
-// (iopx_transfer_stats counts them).  Non-zk, BLAKE2b digests (what default_bcs_params wires for both accelerated fields).
-// FieldT is any 24-byte type with libff::gf192's or libff::edwards_Fr's layout; field_kind<FieldT> says which.
+// (iopx_transfer_stats counts them).  Non-zk; BLAKE2b digests (what default_bcs_params wires for the 24-byte fields) or, over alt_bn128 Fr, Poseidon ones.
+// FieldT is any 24-byte type with libff::gf192's or libff::edwards_Fr's layout, or a 32-byte one with libff::alt_bn128_Fr's; field_kind<FieldT> says which.
 #pragma once
 #include <algorithm>
 #include <functional>
@@ -68,13 +70,14 @@ struct verifier_random_message_handle { std::size_t id; };
 struct query_position_handle { std::size_t id; bool random; };
 struct query_handle { std::size_t id; };
 
-// ---- Fiat-Shamir hashchain (bcs/hashing/blake2b.tcc) ----------------------------------------------------------------------------
-typedef std::string hash_digest;        // 32 raw bytes (binary_hash_digest)
+// ---- Fiat-Shamir hashchains (bcs/hashing/blake2b.tcc, algebraic_sponge.tcc) ------------------------------------------------------
+typedef std::string hash_digest;        // 32 raw bytes: a BLAKE2b digest (binary_hash_digest), or the mont_repr of an alt_bn128 Fr element (hash_type = FieldT)
 
 template<typename FieldT>
 class blake2b_hashchain {
     uint8_t state_[32];
     uint64_t squeeze_index_ = 0;
+    static const std::size_t WORDS = sizeof(FieldT) / 8;
 public:
     // absorb() never mixes its input in (reference quirk F8), so a challenge is a function of the round structure alone.  bcs_prover relies on that:
     // it queues the roots' read-backs and builds trees beside the next round (defer_roots / merkle_aside).  A hashchain that really absorbs — the
@@ -84,8 +87,10 @@ public:
     // :50-61 — hashes the first digest_len bytes of state || input: the state advances to BLAKE2b-256(state) whatever is absorbed
     // (reference behaviour F8 of SURVEY.md, reproduced because the verifier does the same)
     void absorb() { uint8_t next[32]; check(iopx_blake2b_host(next, 32, state_, 32, nullptr, 0)); std::memcpy(state_, next, 32); }
-    // :76-86, :162-257 — element i of squeeze number q = keyed BLAKE2b(state || q, key = i), written raw into the element; prime
-    // field: bits above the modulus MSB cleared, retried with key += num_elements until below p (the bytes ARE mont_repr)
+    void absorb(const hash_digest &) { absorb(); }
+    void absorb(const std::vector<FieldT> &) { absorb(); }
+    // :76-86, :162-257 — element i of squeeze number q = keyed BLAKE2b(state || q, key = i), sizeof(FieldT) bytes written raw into the element; prime
+    // field (three or four limbs): bits above the modulus MSB cleared in the top limb, retried with key += num_elements until below p (the bytes ARE mont_repr)
     std::vector<FieldT> squeeze(std::size_t num_elements)
     {
         ++squeeze_index_;
@@ -93,20 +98,20 @@ public:
         std::memcpy(msg, state_, 32);
         std::memcpy(msg + 32, &squeeze_index_, 8);
         std::vector<FieldT> out(num_elements);
-        uint64_t modulus[3] = { 0, 0, 0 };
+        uint64_t modulus[WORDS] = {};
         const bool additive = field_host<FieldT>::additive();
-        if (!additive) check(iopx_fp3_modulus(modulus));
+        if (!additive) check(WORDS == 4 ? iopx_bn128_modulus(modulus) : iopx_fp3_modulus(modulus));
         for (std::size_t i = 0; i < num_elements; ++i) {
-            uint64_t key = i, w[3];
+            uint64_t key = i, w[WORDS];
             for (;;) {
-                check(iopx_blake2b_host(reinterpret_cast<uint8_t *>(w), 24, msg, 40, &key, 8));
+                check(iopx_blake2b_host(reinterpret_cast<uint8_t *>(w), 8 * WORDS, msg, 40, &key, 8));
                 if (additive) break;
                 key += num_elements;
                 int top = 63;
-                while (top > 0 && !((modulus[2] >> top) & 1)) --top;                         // modulus MSB within the top limb
-                w[2] &= (top == 63) ? ~0ull : ((1ull << (top + 1)) - 1);
+                while (top > 0 && !((modulus[WORDS - 1] >> top) & 1)) --top;                 // modulus MSB within the top limb
+                w[WORDS - 1] &= (top == 63) ? ~0ull : ((1ull << (top + 1)) - 1);
                 bool below = false;
-                for (int k = 2; k >= 0; --k) if (w[k] != modulus[k]) { below = w[k] < modulus[k]; break; }
+                for (int k = (int)WORDS - 1; k >= 0; --k) if (w[k] != modulus[k]) { below = w[k] < modulus[k]; break; }
                 if (below) break;
             }
             out[i] = field_host<FieldT>::from_words(w);
@@ -118,7 +123,7 @@ public:
     {
         const std::vector<FieldT> x = squeeze(1);
         uint8_t d[32];
-        check(iopx_blake2b_host(d, 32, &x[0], 24, nullptr, 0));
+        check(iopx_blake2b_host(d, 32, &x[0], sizeof(FieldT), nullptr, 0));
         return hash_digest(reinterpret_cast<const char *>(d), 32);
     }
     // :88-105 + blake2b.cpp:50-74
@@ -136,6 +141,163 @@ public:
     }
 };
 
+// algebraic_hashchain<FieldT, FieldT> over a Poseidon sponge (bcs/hashing/algebraic_sponge.tcc:18-100, 136-206; the chain of hash_enum.tcc:26-47), on
+// the host: the permutation is the library's host one over the same parameter tables as the device kernels.  FieldT: alt_bn128 Fr's layout.
+template<typename FieldT>
+class algebraic_hashchain {
+    static_assert(sizeof(FieldT) == 32, "the Poseidon hashchain runs over alt_bn128 Fr");
+    iopx_poseidon_params params_;
+    std::vector<FieldT> state_;
+    std::size_t rate_, next_unsqueezed_elem_ = 0;
+    bool currently_absorbing_ = false;
+    void apply_permutation() { check(iopx_poseidon_permute_bn128_host(&params_, detail::words(state_.data()))); }
+    void absorb_internal(const std::vector<FieldT> &in, std::size_t begin)                     // :32-62
+    {
+        for (;;) {
+            const std::size_t left = in.size() - begin, take = std::min(left, rate_);
+            for (std::size_t i = 0; i < take; ++i) state_[i] = field_host<FieldT>::add(state_[i], in[begin + i]);
+            if (left <= rate_) return;
+            apply_permutation();
+            begin += rate_;
+        }
+    }
+public:
+    static const bool absorbs_input = true;
+    explicit algebraic_hashchain(const iopx_poseidon_params &params)
+        : params_(params), state_(params.state_size, field_host<FieldT>::zero()), rate_(params.rate)
+    {
+        if (params.state_size - params.rate != 1) throw std::invalid_argument("the algebraic hashchain needs capacity 1 (algebraic_sponge.tcc:145)");
+    }
+    void absorb(const std::vector<FieldT> &in)                                                 // :18-30
+    {
+        if (currently_absorbing_) apply_permutation();
+        absorb_internal(in, 0);
+        currently_absorbing_ = true;
+    }
+    void absorb(const hash_digest &root)                                                       // :150-169: the root is a field element
+    {
+        if (root.size() != 32) throw std::invalid_argument("an algebraic root is one field element");
+        absorb(std::vector<FieldT>(1, field_host<FieldT>::from_words(reinterpret_cast<const uint64_t *>(root.data()))));
+    }
+    std::vector<FieldT> squeeze(std::size_t num_elements)                                      // :64-100
+    {
+        std::vector<FieldT> out(num_elements, field_host<FieldT>::zero());
+        if (currently_absorbing_) { next_unsqueezed_elem_ = 0; currently_absorbing_ = false; }
+        std::size_t at = 0;
+        for (;;) {
+            if (next_unsqueezed_elem_ == 0) apply_permutation();
+            while (next_unsqueezed_elem_ < rate_ && at < out.size()) out[at++] = state_[next_unsqueezed_elem_++];
+            if (at == out.size()) return out;
+            next_unsqueezed_elem_ = 0;
+        }
+    }
+    hash_digest squeeze_root_type()                                                            // :201-206
+    {
+        const std::vector<FieldT> x = squeeze(1);
+        return hash_digest(reinterpret_cast<const char *>(&x[0]), 32);
+    }
+    // :178-199 — word 0 of the element's canonical integer (libff::get_word_of_field_elem), mod the range
+    std::vector<std::size_t> squeeze_query_positions(std::size_t num_positions, std::size_t range_of_positions)
+    {
+        const std::vector<FieldT> x = squeeze(num_positions);
+        uint64_t raw_one[4] = { 1, 0, 0, 0 };                       // Montgomery product with the plain integer 1: x R * 1 / R = x
+        std::vector<std::size_t> out;
+        for (const FieldT &e : x) {
+            uint64_t canon[4];
+            check(iopx_bn128_host_mul(detail::words(&e), raw_one, canon));
+            out.push_back((std::size_t)(canon[0] % range_of_positions));
+        }
+        return out;
+    }
+};
+
+// ---- the hash family of a BCS transformation: hashchain, Merkle trees and proof of work together (bcs_transformation_parameters of
+// bcs_common.hpp:108-130 as default_bcs_params wires them, common_bcs_parameters.tcc:9-27).  The two models are named by the policy types
+// `blake2b` and `poseidon` that FRI_snark_prover<FieldT, HashPolicy> takes; bcs_prover holds the model behind this interface, so the protocol
+// classes keep referring to bcs_prover<FieldT>. ----
+template<typename FieldT>
+class bcs_hash_family {
+public:
+    virtual ~bcs_hash_family() {}
+    virtual bool absorbs_input() const = 0;
+    virtual void absorb(const hash_digest &root) = 0;
+    virtual void absorb(const std::vector<FieldT> &prover_messages) = 0;
+    virtual std::vector<FieldT> squeeze(std::size_t num_elements) = 0;
+    virtual hash_digest squeeze_root_type() = 0;
+    virtual std::vector<std::size_t> squeeze_query_positions(std::size_t num_positions, std::size_t range_of_positions) = 0;
+    virtual const iopx_poseidon_params *tree_params() const = 0;                              // null: BLAKE2b trees
+    // pow_parameters::pow_bitlen (pow.tcc:21-32) of default_bcs_params' pow_parameters(dim_h + 3 + log2(work_per_hash), work_per_hash)
+    virtual std::size_t pow_bitlen(std::size_t dim_h_plus_3) const = 0;
+    virtual hash_digest solve_pow(const hash_digest &challenge, std::size_t bitlen, const std::function<void()> &behind_the_grind) = 0;
+};
+
+namespace detail {
+inline std::size_t pow_bitlen_of(std::size_t work_parameter, std::size_t cost_per_hash)      // pow.tcc:21-32
+{
+    std::size_t log_hash_cost = log2_ceil(cost_per_hash);
+    if (((std::size_t)1 << log_hash_cost) > cost_per_hash) --log_hash_cost;
+    return work_parameter - log_hash_cost;
+}
+} // namespace detail
+
+template<typename FieldT>
+class blake2b_family : public bcs_hash_family<FieldT> {
+    blake2b_hashchain<FieldT> chain_;
+public:
+    bool absorbs_input() const override { return blake2b_hashchain<FieldT>::absorbs_input; }
+    void absorb(const hash_digest &root) override { chain_.absorb(root); }
+    void absorb(const std::vector<FieldT> &m) override { chain_.absorb(m); }
+    std::vector<FieldT> squeeze(std::size_t n) override { return chain_.squeeze(n); }
+    hash_digest squeeze_root_type() override { return chain_.squeeze_root_type(); }
+    std::vector<std::size_t> squeeze_query_positions(std::size_t n, std::size_t range) override { return chain_.squeeze_query_positions(n, range); }
+    const iopx_poseidon_params *tree_params() const override { return nullptr; }
+    std::size_t pow_bitlen(std::size_t dim_h_plus_3) const override { return detail::pow_bitlen_of(dim_h_plus_3, 1); }
+    hash_digest solve_pow(const hash_digest &challenge, std::size_t bitlen, const std::function<void()> &behind) override { return dist::solve_pow(challenge, bitlen, behind); }
+};
+
+template<typename FieldT>
+class poseidon_family : public bcs_hash_family<FieldT> {
+    iopx_poseidon_params params_;
+    algebraic_hashchain<FieldT> chain_;
+    static iopx_poseidon_params shipped(int bcs_hash_type) { iopx_poseidon_params p; check(iopx_poseidon_shipped_params(bcs_hash_type, 0, &p)); return p; }
+public:
+    explicit poseidon_family(int bcs_hash_type) : params_(shipped(bcs_hash_type)), chain_(params_) {}
+    bool absorbs_input() const override { return algebraic_hashchain<FieldT>::absorbs_input; }
+    void absorb(const hash_digest &root) override { chain_.absorb(root); }
+    void absorb(const std::vector<FieldT> &m) override { chain_.absorb(m); }
+    std::vector<FieldT> squeeze(std::size_t n) override { return chain_.squeeze(n); }
+    hash_digest squeeze_root_type() override { return chain_.squeeze_root_type(); }
+    std::vector<std::size_t> squeeze_query_positions(std::size_t n, std::size_t range) override { return chain_.squeeze_query_positions(n, range); }
+    const iopx_poseidon_params *tree_params() const override { return &params_; }
+    std::size_t pow_bitlen(std::size_t dim_h_plus_3) const override { return detail::pow_bitlen_of(dim_h_plus_3 + 7, 128); }    // work_per_hash 128
+    hash_digest solve_pow(const hash_digest &challenge, std::size_t bitlen, const std::function<void()> &behind) override
+    {
+        if (dist::ctx().active()) throw std::invalid_argument("the Poseidon proof of work is not split over ranks");
+        uint64_t answer[4];
+        check(iopx_pow_solve_poseidon_bn128(&params_, reinterpret_cast<const uint64_t *>(challenge.data()), bitlen, answer));
+        if (behind) behind();
+        return hash_digest(reinterpret_cast<const char *>(answer), 32);
+    }
+};
+
+// the hash policies
+struct blake2b {
+    template<typename FieldT> std::shared_ptr<bcs_hash_family<FieldT>> family() const { return std::make_shared<blake2b_family<FieldT>>(); }
+};
+struct poseidon {
+    int bcs_hash_type;                       // IOPX_HASH_POSEIDON_STARKWARE or IOPX_HASH_POSEIDON_HIGH_ALPHA
+    explicit poseidon(int type = IOPX_HASH_POSEIDON_STARKWARE) : bcs_hash_type(type) {}
+    template<typename FieldT> std::shared_ptr<bcs_hash_family<FieldT>> family() const
+    {
+        if (sizeof(FieldT) != 32) throw std::invalid_argument("Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
+        if (bcs_hash_type != IOPX_HASH_POSEIDON_STARKWARE && bcs_hash_type != IOPX_HASH_POSEIDON_HIGH_ALPHA) throw std::invalid_argument("Not a poseidon hash type");
+        return make<FieldT>(std::integral_constant<bool, sizeof(FieldT) == 32>());
+    }
+private:
+    template<typename FieldT> std::shared_ptr<bcs_hash_family<FieldT>> make(std::true_type) const { return std::make_shared<poseidon_family<FieldT>>(bcs_hash_type); }
+    template<typename FieldT> std::shared_ptr<bcs_hash_family<FieldT>> make(std::false_type) const { return nullptr; }
+};
+
 // ---- a BCS Merkle tree resident in HBM (bcs/merkle_tree.tcc:92-229) -------------------------------------------------------------
 // Over a distributed domain (dist.hpp) the tree is N sub-trees, one per rank over a contiguous run of leaves, under log2 N top levels:
 // the N sub-roots are all-gathered (32 bytes each) and the top levels are hashed on every rank.  Subspaces: the rank's block of every
@@ -150,12 +312,21 @@ class device_merkle_tree {
 public:
     device_merkle_tree() {}
     template<typename FieldT>
-    device_merkle_tree(const std::vector<device_vector<FieldT>> &oracles, const field_subset<FieldT> &domain, std::size_t coset_size)
+    // poseidon: null for a BLAKE2b tree, else the parameter set of a Poseidon tree over alt_bn128 Fr (digests: 32 bytes of mont_repr, same heap layout)
+    device_merkle_tree(const std::vector<device_vector<FieldT>> &oracles, const field_subset<FieldT> &domain, std::size_t coset_size,
+                       const iopx_poseidon_params *poseidon = nullptr)
         : distributed_(domain.distributed()), global_leaves_(domain.num_elements() / coset_size)
     {
         std::vector<const void *> ptrs;
         for (auto &o : oracles) ptrs.push_back(o.data());
         const int type = domain.type() == affine_subspace_type ? IOPX_DOMAIN_ADDITIVE : IOPX_DOMAIN_MULTIPLICATIVE;
+        if (poseidon) {
+            if (distributed_ || sizeof(FieldT) != 32) throw std::invalid_argument("Poseidon trees: alt_bn128 Fr on one GPU");
+            num_leaves_ = global_leaves_;
+            nodes_ = device_array<uint8_t>((2 * num_leaves_ - 1) * 32);
+            check(iopx_merkle_poseidon_bn128_dev(poseidon, ptrs.data(), ptrs.size(), domain.num_elements(), coset_size, type, nullptr, reinterpret_cast<uint64_t *>(nodes_.data())));
+            return;
+        }
         if (!distributed_) {
             num_leaves_ = global_leaves_;
             nodes_ = device_array<uint8_t>((2 * num_leaves_ - 1) * 32);
@@ -340,7 +511,7 @@ private:
     std::size_t pow_bitlen_;
     const bcs_prover_index<FieldT> *index_ = nullptr;                                        // bcs_prover.tcc:12-21
     bool is_holographic_ = false;
-    blake2b_hashchain<FieldT> hashchain_;
+    std::shared_ptr<bcs_hash_family<FieldT>> hash_;                                          // hashchain, trees and proof of work of one family
     // registrations (iop.tcc:22-263)
     std::vector<field_subset<FieldT>> domains_;
     std::vector<oracle_registration> oracle_regs_;
@@ -398,11 +569,14 @@ private:
 
     void run_hashchain_for_round(std::size_t round, std::size_t num_roots)                   // bcs_common.tcc:550-614
     {
-        for (std::size_t i = 0; i < num_roots; ++i) hashchain_.absorb();
-        hashchain_.absorb();                                                                 // the round's prover messages
+        for (std::size_t i = 0; i < num_roots; ++i) hash_->absorb(MT_roots_[processed_MTs_ - num_roots + i]);      // (empty while deferred: only a chain that ignores them defers)
+        std::vector<FieldT> message_concat(1, field_host<FieldT>::zero());                   // absorb_prover_messages, :565-590
+        const std::size_t mbegin = round == 0 ? 0 : num_prover_messages_at_end_of_round_[round - 1];
+        for (std::size_t m = mbegin; m < num_prover_messages_at_end_of_round_[round]; ++m) message_concat.insert(message_concat.end(), prover_messages_[m].begin(), prover_messages_[m].end());
+        hash_->absorb(message_concat);
         const std::size_t start = num_verifier_messages_at_end_of_round_[round];
         const std::size_t end = round == num_interaction_rounds_ - 1 ? 0 : num_verifier_messages_at_end_of_round_[round + 1];
-        for (std::size_t i = start; i < end; ++i) verifier_random_messages_[i] = hashchain_.squeeze(verifier_message_sizes_[i]);
+        for (std::size_t i = start; i < end; ++i) verifier_random_messages_[i] = hash_->squeeze(verifier_message_sizes_[i]);
     }
 
     std::size_t obtain_query_position(const query_position_handle &h, std::map<std::size_t, std::size_t> &random_cache, std::map<std::size_t, std::size_t> &det_cache)
@@ -411,7 +585,7 @@ private:
             auto it = random_cache.find(h.id);
             if (it != random_cache.end()) return it->second;
             const std::size_t n = domains_[random_position_domains_[h.id]].num_elements();
-            return random_cache[h.id] = hashchain_.squeeze_query_positions(1, n)[0];         // bcs_common.tcc:536-548
+            return random_cache[h.id] = hash_->squeeze_query_positions(1, n)[0];         // bcs_common.tcc:536-548
         }
         auto it = det_cache.find(h.id);
         if (it != det_cache.end()) return it->second;
@@ -441,8 +615,11 @@ private:
     }
 
 public:
-    explicit bcs_prover(std::size_t pow_work_parameter, const bcs_prover_index<FieldT> *index = nullptr) : pow_bitlen_(pow_work_parameter), index_(index)
+    // pow_work_parameter: dim_h + 3, the BLAKE2b work parameter of default_bcs_params; the family derives its own bit length from it
+    explicit bcs_prover(std::size_t pow_work_parameter, const bcs_prover_index<FieldT> *index = nullptr, std::shared_ptr<bcs_hash_family<FieldT>> hash = nullptr)
+        : index_(index), hash_(hash ? hash : blake2b().family<FieldT>())
     {
+        pow_bitlen_ = hash_->pow_bitlen(pow_work_parameter);
         outer_collector_ = dist::active_collector<FieldT>();          // this prover's transforms leave their wanted windows with it (dist::window_collector)
         dist::active_collector<FieldT>() = &collector_;
     }
@@ -665,17 +842,20 @@ private:
                 // ... and nothing else in the next round reads the tree, so its kernels (leaves, levels and the single-workgroup top: 5.7 ms of a
                 // 2^20 proof, 0.9 ms of it latency-bound) go to the library's side stream and run beside the next round's transforms; the query
                 // phase joins.  Not when distributed: the tree's collectives stay in the communicator's one stream order.  IOPX_MERKLE_STREAM=0: main stream.
-                const bool deferring = defer_roots() && !blake2b_hashchain<FieldT>::absorbs_input;      // a chain that absorbs needs every root before its round's challenges
+                const bool deferring = defer_roots() && !hash_->absorbs_input();      // a chain that absorbs needs every root before its round's challenges
                 const bool aside = deferring && merkle_aside() && !dist::ctx().active();
                 if (aside) check(iopx_side_stream_begin());
                 struct back_to_main { bool on; ~back_to_main() { if (on) (void)iopx_side_stream_end(); } } section{ aside };
-                MT_trees_[processed_MTs_] = device_merkle_tree(round_oracles, domains_[kv.first], cs);
+                MT_trees_[processed_MTs_] = device_merkle_tree(round_oracles, domains_[kv.first], cs, hash_->tree_params());
                 // The root is needed on the host for the TRANSCRIPT only: blake2b_hashchain::absorb never mixes its input in (reference quirk F8,
                 // bcs/hashing/blake2b.tcc:51-66), so every challenge is a function of the round structure and the prover may go on enqueuing the
                 // next round without waiting for this tree.  The read-back is queued with the query phase's (one drain of the stream for all of
                 // them); IOPX_DEFER_ROOTS=0 reads each root at its round end, as round 4 did (11 drains of about 40 us per 2^20 proof).
                 if (deferring) root_pending_[processed_MTs_] = 1;
-                else MT_roots_[processed_MTs_] = MT_trees_[processed_MTs_].get_root();
+                else {
+                    MT_roots_[processed_MTs_] = MT_trees_[processed_MTs_].get_root();
+                    if (hash_->absorbs_input()) (void)iopx_cold_add("bcs roots read at round end", 0.0);    // counted: the gate above is under test on the GPU
+                }
             } else {                                                                         // "The Merkle trees are already filled in by the preprocessor."
                 MT_trees_[processed_MTs_] = index_->trees[processed_MTs_];
                 MT_roots_[processed_MTs_] = index_->roots[processed_MTs_];
@@ -688,8 +868,8 @@ private:
         if (num_prover_rounds_done_ == num_interaction_rounds_ && !(is_holographic_ && num_interaction_rounds_ == 1)) {
             // The query phase (positions from the hashchain, gathers, one drain) does not depend on the answer: on one GPU it runs behind the grind's
             // first long batch.  The challenge is squeezed first, the query positions after it: the hashchain's order is the reference's either way.
-            const std::string challenge = hashchain_.squeeze_root_type();
-            pow_answer_ = dist::solve_pow(challenge, pow_bitlen_, [this] { extracted_ = extract_queries(); have_extracted_ = true; });   // split by candidate range over the ranks
+            const std::string challenge = hash_->squeeze_root_type();
+            pow_answer_ = hash_->solve_pow(challenge, pow_bitlen_, [this] { extracted_ = extract_queries(); have_extracted_ = true; });   // split by candidate range over the ranks
         }
     }
 public:

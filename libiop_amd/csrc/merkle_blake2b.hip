@@ -213,6 +213,50 @@ static bool launch_leaves_sub24(const LeafParams &p, size_t coset_size, unsigned
     return true;
 }
 
+// The same for 32-byte elements (alt_bn128 Fr) over cosets of a multiplicative domain: NO <= 4 oracles, CS = 2, 4 or 8 positions, no salts.  Four elements
+// are exactly one 128-byte BLAKE2b block, so the message is never held whole (CS = 8 x NO = 4 would be 128 words a lane): block b is elements
+// 4 b .. 4 b + 3 of the serialisation (oracle e / CS, position i + (e % CS) L), each fetched as two 16-byte loads (32-byte elements of a 16-byte
+// aligned array are 16-byte aligned), with e / CS and e % CS folded at compile time.  Same bytes into the same compressions as k_merkle_leaves.
+template<int NO, int CS>
+__global__ void __launch_bounds__(256) k_merkle_leaves_sub32(LeafParams p)
+{
+    constexpr int E = NO * CS, BLOCKS = (E + 3) / 4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.num_leaves; i += (size_t)gridDim.x * blockDim.x) {
+        uint64_t h[8];
+        b2b_init(h);
+#pragma unroll
+        for (int b = 0; b < BLOCKS; ++b) {
+            uint64_t m[16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * b + q;
+                if (e < E) {
+                    const b2b_u64x2 *src = (const b2b_u64x2 *)(p.inline_oracles[e / CS] + 4 * (i + (size_t)(e % CS) * p.num_leaves));
+                    const b2b_u64x2 lo = src[0], hi = src[1];
+                    m[4 * q] = lo[0]; m[4 * q + 1] = lo[1]; m[4 * q + 2] = hi[0]; m[4 * q + 3] = hi[1];
+                } else {
+                    m[4 * q] = 0; m[4 * q + 1] = 0; m[4 * q + 2] = 0; m[4 * q + 3] = 0;
+                }
+            }
+            b2b_compress(h, m, b + 1 == BLOCKS ? (uint64_t)E * 32 : (uint64_t)(b + 1) * 128, b + 1 == BLOCKS);
+        }
+        b2b_u64x2 *out = (b2b_u64x2 *)(p.nodes + 4 * (p.num_leaves - 1 + i));
+        b2b_u64x2 lo = { h[0], h[1] }, hi = { h[2], h[3] };
+        out[0] = lo;
+        out[1] = hi;
+    }
+}
+
+template<int NO>
+static bool launch_leaves_sub32(const LeafParams &p, size_t coset_size, unsigned grid)
+{
+    if (coset_size == 2) hipLaunchKernelGGL((k_merkle_leaves_sub32<NO, 2>), dim3(grid), dim3(256), 0, stream(), p);
+    else if (coset_size == 4) hipLaunchKernelGGL((k_merkle_leaves_sub32<NO, 4>), dim3(grid), dim3(256), 0, stream(), p);
+    else if (coset_size == 8) hipLaunchKernelGGL((k_merkle_leaves_sub32<NO, 8>), dim3(grid), dim3(256), 0, stream(), p);
+    else return false;
+    return true;
+}
+
 // VEC: the node array is 16-byte aligned (every array the library allocates is): four 16-byte loads, two 16-byte stores
 template<bool VEC>
 __device__ __forceinline__ void node_hash(uint64_t *nodes, size_t j)
@@ -370,8 +414,19 @@ static int merkle_blake2b_impl(const void *const *d_oracles, size_t num_oracles,
         // profile names per shape (oracles x coset size), as tools/make_traffic_json.py derives them from the kernel symbols
         static const char *const shape_names[4][2] = { { "k_merkle_leaves_1x2", "k_merkle_leaves_1x4" }, { "k_merkle_leaves_2x2", "k_merkle_leaves_2x4" },
                                                       { "k_merkle_leaves_3x2", "k_merkle_leaves_3x4" }, { "k_merkle_leaves_4x2", "k_merkle_leaves_4x4" } };
-        ProfScope ps_(fixed ? shape_names[num_oracles - 1][coset_size == 4] : "k_merkle_leaves", num_oracles * n * elem_bytes + L * 32);
-        if (fixed) {
+        // 32-byte elements: the sibling kernel (IOPX_LEAVES_SUB32=0: the general kernel, for the comparisons of the two)
+        bool fixed32 = elem_bytes == 32 && !d_salts && !p.additive && num_oracles <= 4 && (coset_size == 2 || coset_size == 4 || coset_size == 8) &&
+                       ((uintptr_t)d_nodes & 15) == 0 && iopx_get_option("IOPX_LEAVES_SUB32", 1) != 0;
+        for (size_t k = 0; fixed32 && k < num_oracles; ++k) fixed32 = ((uintptr_t)d_oracles[k] & 15) == 0;
+        ProfScope ps_(fixed ? shape_names[num_oracles - 1][coset_size == 4] : (fixed32 ? "k_merkle_leaves_sub32" : "k_merkle_leaves"), num_oracles * n * elem_bytes + L * 32);
+        if (fixed32) {
+            switch (num_oracles) {
+                case 1: fixed = launch_leaves_sub32<1>(p, coset_size, (unsigned)grid); break;
+                case 2: fixed = launch_leaves_sub32<2>(p, coset_size, (unsigned)grid); break;
+                case 3: fixed = launch_leaves_sub32<3>(p, coset_size, (unsigned)grid); break;
+                default: fixed = launch_leaves_sub32<4>(p, coset_size, (unsigned)grid); break;
+            }
+        } else if (fixed) {
             switch (num_oracles) {
                 case 1: fixed = launch_leaves_sub24<1>(p, coset_size, (unsigned)grid); break;
                 case 2: fixed = launch_leaves_sub24<2>(p, coset_size, (unsigned)grid); break;

@@ -23,6 +23,7 @@
 #include "runtime.h"
 #include "poseidon_tables.h"
 #include "bn254_dev.h"
+#include "bn254_host.h"
 
 namespace iopx {
 
@@ -460,6 +461,41 @@ int iopx_poseidon_permute_bn128_dev(const iopx_poseidon_params *params, uint64_t
     { ProfScope ps_("k_poseidon_permute"); if (P.t == 3) hipLaunchKernelGGL(k_poseidon_permute<3>, dim3(pgrid(count, 64)), dim3(64), 0, stream(), P, d_states, count);
       else hipLaunchKernelGGL(k_poseidon_permute<4>, dim3(pgrid(count, 64)), dim3(64), 0, stream(), P, d_states, count); }
     IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// poseidon::apply_permutation (poseidon.tcc:241-297) on ONE state on the host, over the same parameter tables as the kernels above: the
+// Fiat-Shamir sponge of a proof (algebraic_hashchain, libiop_amd/cpp/iop.hpp) permutes a handful of states per round, each depending on the last.
+int iopx_poseidon_permute_bn128_host(const iopx_poseidon_params *pp, uint64_t *state)
+{
+    if (!pp || !pp->ark || (!pp->mds && !pp->near_mds) || !state) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t t = pp->state_size, rounds = pp->full_rounds + pp->partial_rounds, half = pp->full_rounds / 2;
+    if (t != 3 && t != 4) return fail(IOPX_ERR_INVALID_ARGUMENT, "unsupported Poseidon state size %zu (3 or 4)", t);
+    if (pp->alpha != 3 && pp->alpha != 5 && pp->alpha != 17) return fail(IOPX_ERR_INVALID_ARGUMENT, "unsupported Poseidon alpha %zu", pp->alpha);
+    const hbn r2 = hbn::pow2_mod_p(512);                         // canonical integer -> Montgomery words
+    hbn s[4], mds[16];
+    for (size_t e = 0; e < t; ++e) s[e] = hbn::from_words(state + 4 * e);
+    if (!pp->near_mds) for (size_t i = 0; i < t * t; ++i) mds[i] = hbn::from_words(pp->mds + 4 * i) * r2;
+    auto sbox = [&](const hbn &x) {
+        hbn y = x.squared();
+        if (pp->alpha >= 5) y = y.squared();
+        if (pp->alpha == 17) y = y.squared().squared();
+        return y * x;
+    };
+    for (size_t round = 0; round < rounds; ++round) {
+        const bool full = round < half || round >= half + pp->partial_rounds;
+        for (size_t e = 0; e < t; ++e) s[e] = s[e] + hbn::from_words(pp->ark + 4 * (round * t + e)) * r2;
+        for (size_t e = 0; e < t; ++e) if (full || e == t - 1) s[e] = sbox(s[e]);
+        hbn o[4];
+        if (pp->near_mds) {
+            if (t == 3) { o[0] = s[0] + s[2]; o[1] = s[1] + s[0]; o[2] = s[2] + s[1]; }         // poseidon.tcc:198-211
+            else for (size_t e = 0; e < 4; ++e) for (size_t c = 0; c < 4; ++c) if (c != e) o[e] = o[e] + s[c];      // :213-224
+        } else {
+            for (size_t e = 0; e < t; ++e) for (size_t c = 0; c < t; ++c) o[e] = o[e] + mds[e * t + c] * s[c];       // :226-238
+        }
+        for (size_t e = 0; e < t; ++e) s[e] = o[e];
+    }
+    for (size_t e = 0; e < t; ++e) memcpy(state + 4 * e, s[e].w, 32);
     return IOPX_OK;
 }
 

@@ -36,22 +36,30 @@ template<typename FieldT> struct held_words {
 template<typename FieldT> inline held_words<FieldT> shift_words(const field_subset<FieldT> &D) { return held_words<FieldT>{ D.shift() }; }
 template<typename FieldT> inline held_words<FieldT> gen_words(const field_subset<FieldT> &D) { return held_words<FieldT>{ D.generator() }; }
 template<typename FieldT> inline bool additive(const field_subset<FieldT> &D) { return D.type() == affine_subspace_type; }
-// 32-byte elements are alt_bn128 Fr's (multiplicative cosets only, one GPU): the _bn128 entries of the same seams
-template<typename FieldT> struct is_bn128 { static const bool value = sizeof(FieldT) == 32; };
+// The domain as the domain-shaped operations of field_ops.hpp take it.  It points into its own copies of generator() and shift(): a temporary
+// in the call's argument list, never copied or stored.
+template<typename FieldT> struct domain_words : ops::domain {
+    const FieldT s, g;
+    explicit domain_words(const field_subset<FieldT> &D) : s(D.shift()), g(dev::additive(D) ? s : D.generator())
+    {
+        additive = dev::additive(D); basis = additive ? basis_words(D) : nullptr; gen = detail::words(&g); shift = detail::words(&s); dim = D.dimension();
+    }
+    domain_words(const domain_words &) = delete;
+};
+typedef ops::vector_ops V;
+typedef ops::prime_field_ops P;
 template<typename FieldT> inline void require_whole(const field_subset<FieldT> &D)
 {
-    if (is_bn128<FieldT>::value && (D.distributed() || additive(D))) throw std::invalid_argument("alt_bn128 Fr: multiplicative cosets on one GPU only");
+    typedef field_of<FieldT> F;
+    if ((D.distributed() && !F::vec->distributed) || (additive(D) && !F::additive))
+        throw std::invalid_argument(std::string(F::vec->name) + ": this field has no distributed or additive form");
 }
 
 template<typename FieldT>
 device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coeffs, const field_subset<FieldT> &D)            // fft.tcc:407-419
 {
     require_whole(D);
-    if (is_bn128<FieldT>::value) {                                                           // no window outputs from this transform: the prover gathers them
-        device_vector<FieldT> out(D.num_elements());
-        check(iopx_mul_fft_bn128_dev(coeffs.words(), n_coeffs, D.dimension(), gen_words(D), shift_words(D), out.words()));
-        return out;
-    }
+    const auto mul_fft = additive(D) ? nullptr : field_entry<FieldT>(&P::mul_fft, "FFT");
     if (D.distributed()) {                                                                   // dist.hpp: this rank's part of the codeword
         device_vector<FieldT> out(dist::local_size(D));
         if (additive(D)) {                                                                   // its coset range of the transform; phase 1 on the coefficients is replicated
@@ -60,14 +68,17 @@ device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coe
         } else {                                                                             // one ordinary transform over the rank's sub-coset
             if (n_coeffs > out.size()) throw std::invalid_argument("more coefficients than a residue class holds");
             const field_subset<FieldT> loc = dist::local_domain(D);
-            check(iopx_mul_fft_fp3_dev(coeffs.words(), n_coeffs, loc.dimension(), gen_words(loc), shift_words(loc), out.words()));
+            check(mul_fft(coeffs.words(), n_coeffs, loc.dimension(), gen_words(loc), shift_words(loc), out.words()));
         }
         return out;
     }
     device_vector<FieldT> out(D.num_elements());
     if (additive(D)) { check(iopx_add_fft_gf192_dev(coeffs.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), out.words())); return out; }
     // the windows the prover will ask for (dist::window_collector) leave the transform's last pass together with the codeword
-    dist::window_collector<FieldT> *col = dist::active_collector<FieldT>();
+    // (a field without that entry takes the plain transform: the prover gathers them)
+    const P *prime = field_of<FieldT>::prime;
+    const auto mul_fft_windows = prime ? prime->mul_fft_windows : nullptr;
+    dist::window_collector<FieldT> *col = mul_fft_windows ? dist::active_collector<FieldT>() : nullptr;
     if (col && col->domain_elements == D.num_elements() && !col->wanted.empty()) {
         typename dist::window_collector<FieldT>::entry e;
         std::size_t firsts[2], log_strides[2];
@@ -79,12 +90,12 @@ device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coe
             firsts[nw] = w.first; log_strides[nw] = detail::log2_ceil(w.stride); ptrs[nw] = e.windows.back().second.words();
             ++nw;
         }
-        check(iopx_mul_fft_fp3_windows_dev(coeffs.words(), n_coeffs, D.dimension(), gen_words(D), shift_words(D), out.words(), nw, firsts, log_strides, ptrs));
+        check(mul_fft_windows(coeffs.words(), n_coeffs, D.dimension(), gen_words(D), shift_words(D), out.words(), nw, firsts, log_strides, ptrs));
         e.codeword = out;
         col->produced.push_back(std::move(e));
         return out;
     }
-    check(iopx_mul_fft_fp3_dev(coeffs.words(), n_coeffs, D.dimension(), gen_words(D), shift_words(D), out.words()));
+    check(mul_fft(coeffs.words(), n_coeffs, D.dimension(), gen_words(D), shift_words(D), out.words()));
     return out;
 }
 
@@ -95,9 +106,8 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
     if (evals.size() != D.num_elements()) throw std::invalid_argument("IFFT: evaluation count != domain size");
     require_whole(D);
     device_vector<FieldT> out(D.num_elements());
-    if (is_bn128<FieldT>::value) check(iopx_mul_ifft_bn128_dev(evals.words(), D.dimension(), gen_words(D), shift_words(D), out.words()));
-    else if (additive(D)) check(iopx_add_ifft_gf192_dev(evals.words(), basis_words(D), D.dimension(), shift_words(D), out.words()));
-    else check(iopx_mul_ifft_fp3_dev(evals.words(), D.dimension(), gen_words(D), shift_words(D), out.words()));
+    if (additive(D)) check(iopx_add_ifft_gf192_dev(evals.words(), basis_words(D), D.dimension(), shift_words(D), out.words()));
+    else check(field_entry<FieldT>(&P::mul_ifft, "IFFT")(evals.words(), D.dimension(), gen_words(D), shift_words(D), out.words()));
     return out;
 }
 
@@ -212,11 +222,6 @@ device_vector<FieldT> IFFT_of_known_degree(const device_vector<FieldT> &evals, s
 {
     const std::size_t k = detail::log2_ceil(degree), count = (std::size_t)1 << k;
     require_whole(D);
-    if (is_bn128<FieldT>::value) {
-        device_vector<FieldT> out(count);
-        check(iopx_mul_ifft_known_degree_bn128_dev(evals.words(), degree, D.dimension(), gen_words(D), shift_words(D), out.words()));
-        return out;
-    }
     if (D.distributed()) {
         // Subspaces read the first 2^k evaluations (fft.tcc:458-475): rank 0's head.  Cosets read every (|D| / 2^k)-th (fft.tcc:435-456):
         // all on rank 0 while that stride is a multiple of N, at stride / N in its sub-coset (whose shift is the domain's).  Rank 0
@@ -237,7 +242,7 @@ device_vector<FieldT> IFFT_of_known_degree(const device_vector<FieldT> &evals, s
     }
     if (additive(D)) return IFFT<FieldT>(evals.slice(0, count), D.get_subset_of_order(count));
     device_vector<FieldT> out(count);
-    check(iopx_mul_ifft_known_degree_fp3_dev(evals.words(), degree, D.dimension(), gen_words(D), shift_words(D), out.words()));
+    check(field_entry<FieldT>(&P::mul_ifft_known_degree, "IFFT_of_known_degree")(evals.words(), degree, D.dimension(), gen_words(D), shift_words(D), out.words()));
     return out;
 }
 
@@ -253,9 +258,8 @@ device_vector<FieldT> fold(const device_vector<FieldT> &f, const field_subset<Fi
     const field_subset<FieldT> &D = D_in;
     require_whole(D);
     device_vector<FieldT> out(D.num_elements() / coset_size);
-    if (is_bn128<FieldT>::value) check(iopx_fri_fold_mul_bn128_dev(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
-    else if (additive(D)) check(iopx_fri_fold_add_gf192_dev(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
-    else check(iopx_fri_fold_mul_fp3_dev(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    if (additive(D)) check(iopx_fri_fold_add_gf192_dev(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    else check(field_entry<FieldT>(&P::fri_fold_mul, "fold")(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
     return out;
 }
 
@@ -264,8 +268,7 @@ device_vector<FieldT> sub(const device_vector<FieldT> &a, const device_vector<Fi
 {
     if (a.size() != b.size()) throw std::invalid_argument("sub: size mismatch");
     device_vector<FieldT> out(a.size());
-    if (field_host<FieldT>::additive()) check(iopx_gf192_add_dev(a.words(), b.words(), out.words(), a.size()));
-    else check(iopx_fp3_sub_dev(a.words(), b.words(), out.words(), a.size()));
+    check(field_entry<FieldT>(&V::sub, "sub")(a.words(), b.words(), out.words(), a.size()));
     return out;
 }
 
@@ -273,8 +276,7 @@ template<typename FieldT>
 device_vector<FieldT> pow_table(std::size_t count, const FieldT &base, const FieldT &init)                                      // out[l] = init * base^l
 {
     device_vector<FieldT> out(count);
-    if (field_host<FieldT>::additive()) check(iopx_gf192_pow_table_dev(out.words(), count, detail::words(&base), detail::words(&init)));
-    else check(iopx_fp3_pow_table_dev(out.words(), count, detail::words(&base), detail::words(&init)));
+    check(field_entry<FieldT>(&V::pow_table, "pow_table")(out.words(), count, detail::words(&base), detail::words(&init)));
     return out;
 }
 
@@ -283,10 +285,7 @@ template<typename FieldT>
 device_vector<FieldT> poly_div_vanishing(const device_vector<FieldT> &poly, std::size_t n_coeffs, const field_subset<FieldT> &D)
 {
     device_vector<FieldT> out(n_coeffs > D.num_elements() ? n_coeffs - D.num_elements() : 0);
-    if (n_coeffs > D.num_elements()) {
-        if (additive(D)) check(iopx_poly_div_vanishing_gf192_dev(poly.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), out.words()));
-        else check(iopx_poly_div_vanishing_fp3_dev(poly.words(), n_coeffs, D.dimension(), shift_words(D), out.words()));
-    }
+    if (n_coeffs > D.num_elements()) check(ops::poly_div_vanishing<field_of<FieldT>>(domain_words<FieldT>(D), poly.words(), n_coeffs, out.words()));
     return out;
 }
 
@@ -297,8 +296,7 @@ template<typename FieldT>
 device_vector<FieldT> div(const device_vector<FieldT> *num, const device_vector<FieldT> &den)        // batch_inverse(_and_mul), utils.tcc:57-118
 {
     device_vector<FieldT> out(den.size());
-    auto fn = field_host<FieldT>::additive() ? iopx_gf192_div_dev : iopx_fp3_div_dev;
-    check(fn(num ? num->words() : nullptr, den.words(), out.words(), den.size()));
+    check(field_entry<FieldT>(&V::div, "div")(num ? num->words() : nullptr, den.words(), out.words(), den.size()));
     return out;
 }
 
@@ -307,11 +305,7 @@ device_vector<FieldT> vanishing_evals(const field_subset<FieldT> &S, const field
 {
     const field_subset<FieldT> D = dist::local_domain(D_in);
     device_vector<FieldT> out(D.num_elements());
-    if (additive(D))
-        check(iopx_vanishing_evals_gf192_dev(basis_words(D), D.dimension(), shift_words(D), basis_words(S), S.dimension(), shift_words(S), detail::words(&constant),
-                                             out.words()));
-    else
-        check(iopx_vanishing_evals_fp3_dev(D.dimension(), gen_words(D), shift_words(D), S.dimension(), shift_words(S), detail::words(&constant), out.words()));
+    check(ops::vanishing_evals<field_of<FieldT>>(domain_words<FieldT>(D), domain_words<FieldT>(S), detail::words(&constant), out.words()));
     return out;
 }
 
@@ -440,12 +434,7 @@ public:
         const device_vector<FieldT> f1v = dev::FFT<FieldT>(f1v_coefficients_, I.num_elements(), D);                     // :211-212
         const field_subset<FieldT> L = dist::local_domain(D);                                 // pointwise: this rank's part is a domain of its own
         device_vector<FieldT> out(L.num_elements());
-        if (dev::additive(L))
-            check(iopx_fz_gf192_dev(constituents[0].words(), f1v.words(), dev::basis_words(L), L.dimension(), dev::shift_words(L), dev::basis_words(I),
-                                    I.dimension(), dev::shift_words(I), out.words()));
-        else
-            check(iopx_fz_fp3_dev(constituents[0].words(), f1v.words(), L.dimension(), dev::gen_words(L), dev::shift_words(L), I.dimension(), dev::shift_words(I),
-                                  out.words()));
+        check(ops::fz<field_of<FieldT>>(dev::domain_words<FieldT>(L), dev::domain_words<FieldT>(I), constituents[0].words(), f1v.words(), out.words()));
         return out;
     }
 };
@@ -465,12 +454,7 @@ public:
         const field_subset<FieldT> L = dist::local_domain(D);
         const field_subset<FieldT> &H = constraint_domain_;
         device_vector<FieldT> out(L.num_elements());
-        if (dev::additive(L))
-            check(iopx_rowcheck_gf192_dev(c[0].words(), c[1].words(), c[2].words(), dev::basis_words(L), L.dimension(), dev::shift_words(L), H.dimension(),
-                                          dev::shift_words(H), out.words()));
-        else
-            check(iopx_rowcheck_fp3_dev(c[0].words(), c[1].words(), c[2].words(), L.dimension(), dev::gen_words(L), dev::shift_words(L), H.dimension(),
-                                        dev::shift_words(H), out.words()));
+        check(ops::rowcheck<field_of<FieldT>>(dev::domain_words<FieldT>(L), c[0].words(), c[1].words(), c[2].words(), H.dimension(), dev::shift_words(H), out.words()));
         return out;
     }
 };
@@ -515,8 +499,7 @@ public:
         const std::vector<device_vector<FieldT>> p = dev::reextend_packed<FieldT>(p_alpha_evals_, 2, summation_domain_, D);                    // :94-98 + :112-118
         const std::vector<const void *> Mz = dev::pointers(c, 1);
         device_vector<FieldT> out(c[0].size());
-        auto fn = field_host<FieldT>::additive() ? iopx_lincheck_gf192_dev : iopx_lincheck_fp3_dev;
-        check(fn(c[0].words(), Mz.data(), Mz.size(), detail::words(r_Mz_.data()), p[0].words(), p[1].words(), c[0].size(), out.words()));
+        check(field_entry<FieldT>(&dev::V::lincheck, "lincheck")(c[0].words(), Mz.data(), Mz.size(), detail::words(r_Mz_.data()), p[0].words(), p[1].words(), c[0].size(), out.words()));
         return out;
     }
 };
@@ -539,8 +522,7 @@ public:
         if (c.size() != num_oracles_) throw std::invalid_argument("Random Linear Combination Oracle: Expected same number of evaluations as in registration.");
         const std::vector<const void *> ptrs = dev::pointers(c);
         device_vector<FieldT> out(c[0].size());
-        auto fn = field_host<FieldT>::additive() ? iopx_lincomb_gf192_dev : iopx_lincomb_fp3_dev;
-        check(fn(ptrs.data(), ptrs.size(), detail::words(coefficients_.data()), c[0].size(), out.words()));
+        check(field_entry<FieldT>(&dev::V::lincomb, "lincomb")(ptrs.data(), ptrs.size(), detail::words(coefficients_.data()), c[0].size(), out.words()));
         return out;
     }
 };
@@ -562,12 +544,7 @@ public:
         const field_subset<FieldT> L = dist::local_domain(D);
         const field_subset<FieldT> &H = summation_domain_;
         device_vector<FieldT> out(L.num_elements());
-        if (dev::additive(L))
-            check(iopx_sumcheck_g_gf192_dev(c[0].words(), c[1].words(), dev::basis_words(L), L.dimension(), dev::shift_words(L), dev::basis_words(H), H.dimension(),
-                                            dev::shift_words(H), detail::words(&claimed_sum_), out.words()));
-        else
-            check(iopx_sumcheck_g_fp3_dev(c[0].words(), c[1].words(), L.dimension(), dev::gen_words(L), dev::shift_words(L), H.dimension(), dev::shift_words(H),
-                                          detail::words(&claimed_sum_), out.words()));
+        check(ops::sumcheck_g<field_of<FieldT>>(dev::domain_words<FieldT>(L), dev::domain_words<FieldT>(H), c[0].words(), c[1].words(), detail::words(&claimed_sum_), out.words()));
         return out;
     }
 };
@@ -595,15 +572,7 @@ public:
         const std::vector<const void *> ptrs = dev::pointers(c);
         device_vector<FieldT> out(L.num_elements());
         dev::require_whole(L);
-        if (dev::is_bn128<FieldT>::value)
-            check(iopx_ldt_combine_bn128_dev(ptrs.data(), ptrs.size(), degrees_.data(), detail::words(coefficients_.data()), L.dimension(), dev::gen_words(L),
-                                             dev::shift_words(L), out.words()));
-        else if (dev::additive(L))
-            check(iopx_ldt_combine_gf192_dev(ptrs.data(), ptrs.size(), degrees_.data(), detail::words(coefficients_.data()), dev::basis_words(L), L.dimension(),
-                                             dev::shift_words(L), out.words()));
-        else
-            check(iopx_ldt_combine_fp3_dev(ptrs.data(), ptrs.size(), degrees_.data(), detail::words(coefficients_.data()), L.dimension(), dev::gen_words(L),
-                                           dev::shift_words(L), out.words()));
+        check(ops::ldt_combine<field_of<FieldT>>(dev::domain_words<FieldT>(L), ptrs.data(), ptrs.size(), degrees_.data(), detail::words(coefficients_.data()), out.words()));
         return out;
     }
 };
@@ -679,7 +648,7 @@ public:
                     const std::vector<device_vector<FieldT>> terms = { evals.slice(0, n), moved };
                     const std::vector<const void *> ptrs = dev::pointers(terms);
                     const FieldT coefficients[2] = { scale, F::neg(scale) };
-                    check(iopx_lincomb_gf192_dev(ptrs.data(), 2, detail::words(coefficients), n, h.words()));
+                    check(field_entry<FieldT>(&dev::V::lincomb, "lincomb")(ptrs.data(), 2, detail::words(coefficients), n, h.words()));
                 } else {
                     h = dev::poly_div_vanishing<FieldT>(dev::IFFT<FieldT>(evals, dist::head_domain(L_, count)), degree_bound_, H_);
                 }

@@ -12,62 +12,51 @@
 namespace libiop_amd {
 
 // ---- host scalars of FieldT (per-proof constants only) --------------------------------------------------------------------------
-template<typename FieldT, std::size_t Bytes = sizeof(FieldT)>
+// One body for all three fields, written against the table of field_ops.hpp: gf192 keeps its branches (xor, the subspace forms of Z_S),
+// everything else is the field's entry.  A size / kind the table does not have fails to compile.
+template<typename FieldT>
 struct field_host {
-    static_assert(sizeof(FieldT) == 24, "libiop_amd accelerates 24-byte field elements (libff::gf192 / libff::edwards_Fr layout)");
-    static bool additive() { return field_kind<FieldT>::type == affine_subspace_type; }
-    static FieldT from_words(const uint64_t *w) { FieldT r; std::memcpy((void *)&r, w, 24); return r; }
-    static FieldT zero() { const uint64_t w[3] = { 0, 0, 0 }; return from_words(w); }
+    typedef ops::field<sizeof(FieldT), field_kind<FieldT>::type == affine_subspace_type> table;
+    typedef ops::prime_field_ops P;
+    static const std::size_t WORDS = sizeof(FieldT) / 8;
+    template<typename Slot> static auto entry(Slot slot, const char *op) { return ops::entry<table>(slot, op); }
+    template<typename Fn> static FieldT binary(Fn fn, const FieldT &a, const FieldT &b) { uint64_t w[WORDS]; check(fn(detail::words(&a), detail::words(&b), w)); return from_words(w); }
+
+    static bool additive() { return table::additive; }
+    static FieldT from_words(const uint64_t *w) { FieldT r; std::memcpy((void *)&r, w, sizeof(FieldT)); return r; }
+    static FieldT zero() { const uint64_t w[WORDS] = {}; return from_words(w); }
     static FieldT from_uint(uint64_t v)
     {
-        uint64_t w[3] = { v, 0, 0 };
-        if (!additive()) check(iopx_fp3_from_uint(v, w));
+        uint64_t w[WORDS] = { v };
+        if (!additive()) check(entry(&P::from_uint, "from_uint")(v, w));
         return from_words(w);
     }
     static FieldT one() { return from_uint(1); }
-    static bool is_zero(const FieldT &a) { const uint64_t *w = detail::words(&a); return (w[0] | w[1] | w[2]) == 0; }
+    static bool is_zero(const FieldT &a) { uint64_t any = 0; for (std::size_t i = 0; i < WORDS; ++i) any |= detail::words(&a)[i]; return any == 0; }
     static FieldT add(const FieldT &a, const FieldT &b)
     {
-        uint64_t w[3];
-        if (additive()) for (int i = 0; i < 3; ++i) w[i] = detail::words(&a)[i] ^ detail::words(&b)[i];
-        else check(iopx_fp3_host_add(detail::words(&a), detail::words(&b), w));
+        if (!additive()) return binary(entry(&P::host_add, "add"), a, b);
+        uint64_t w[WORDS];
+        for (std::size_t i = 0; i < WORDS; ++i) w[i] = detail::words(&a)[i] ^ detail::words(&b)[i];
         return from_words(w);
     }
-    static FieldT mul(const FieldT &a, const FieldT &b)
-    {
-        uint64_t w[3];
-        if (additive()) check(iopx_gf192_host_mul(detail::words(&a), detail::words(&b), w));
-        else check(iopx_fp3_host_mul(detail::words(&a), detail::words(&b), w));
-        return from_words(w);
-    }
+    static FieldT sub(const FieldT &a, const FieldT &b) { return additive() ? add(a, b) : binary(entry(&P::host_sub, "sub"), a, b); }
+    static FieldT mul(const FieldT &a, const FieldT &b) { return binary(entry(&P::host_mul, "mul"), a, b); }
     static FieldT pow(const FieldT &a, uint64_t e)
     {
-        if (!additive()) { uint64_t w[3]; check(iopx_fp3_host_pow(detail::words(&a), e, w)); return from_words(w); }
+        if (!additive()) { uint64_t w[WORDS]; check(entry(&P::host_pow, "pow")(detail::words(&a), e, w)); return from_words(w); }
         FieldT r = one(), b = a;
         for (; e; e >>= 1) { if (e & 1) r = mul(r, b); b = mul(b, b); }
         return r;
     }
-    static FieldT sub(const FieldT &a, const FieldT &b)
-    {
-        if (additive()) return add(a, b);
-        uint64_t w[3];
-        check(iopx_fp3_host_sub(detail::words(&a), detail::words(&b), w));
-        return from_words(w);
-    }
     static FieldT neg(const FieldT &a) { return sub(zero(), a); }
-    static FieldT inverse(const FieldT &a)
-    {
-        uint64_t w[3];
-        if (additive()) check(iopx_gf192_inverse_host(detail::words(&a), w));
-        else check(iopx_fp3_host_inverse(detail::words(&a), w));
-        return from_words(w);
-    }
+    static FieldT inverse(const FieldT &a) { uint64_t w[WORDS]; check(entry(&P::host_inverse, "inverse")(detail::words(&a), w)); return from_words(w); }
     // Z_S(x) for the domain S (vanishing_polynomial::evaluation_at_point): the linearized polynomial of the subspace through the
     // library's host helper / x^|S| - shift^|S| (vanishing_polynomial.tcc:14-25)
     static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
-            uint64_t w[3];
+            uint64_t w[WORDS];
             const FieldT shift = S.shift();
             check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), w, nullptr));
             return from_words(w);
@@ -78,7 +67,7 @@ struct field_host {
     static FieldT vanishing_derivative(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
-            uint64_t w[3];
+            uint64_t w[WORDS];
             const FieldT shift = S.shift();
             check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), nullptr, w));
             return from_words(w);
@@ -98,34 +87,13 @@ struct field_host {
         const FieldT o = one();
         return std::memcmp(&r, &o, sizeof(FieldT)) == 0;
     }
-    // libff::soundness_log_of_field_size_helper: the extension degree for binary fields, floor(log2 p) for prime fields
-    static std::size_t soundness_bits() { return additive() ? 192 : 180; }
+    static std::size_t soundness_bits() { return table::vec->soundness_bits; }
 };
 
-// 32-byte elements: libff::alt_bn128_Fr's layout (four Montgomery limbs), multiplicative cosets only; the iopx_bn128_* host helpers
-template<typename FieldT>
-struct field_host<FieldT, 32> {
-    static bool additive() { return false; }
-    static FieldT from_words(const uint64_t *w) { FieldT r; std::memcpy((void *)&r, w, 32); return r; }
-    static FieldT zero() { const uint64_t w[4] = { 0, 0, 0, 0 }; return from_words(w); }
-    static FieldT from_uint(uint64_t v) { uint64_t w[4]; check(iopx_bn128_from_uint(v, w)); return from_words(w); }
-    static FieldT one() { return from_uint(1); }
-    static bool is_zero(const FieldT &a) { const uint64_t *w = detail::words(&a); return (w[0] | w[1] | w[2] | w[3]) == 0; }
-    static FieldT add(const FieldT &a, const FieldT &b) { uint64_t w[4]; check(iopx_bn128_host_add(detail::words(&a), detail::words(&b), w)); return from_words(w); }
-    static FieldT sub(const FieldT &a, const FieldT &b) { uint64_t w[4]; check(iopx_bn128_host_sub(detail::words(&a), detail::words(&b), w)); return from_words(w); }
-    static FieldT mul(const FieldT &a, const FieldT &b) { uint64_t w[4]; check(iopx_bn128_host_mul(detail::words(&a), detail::words(&b), w)); return from_words(w); }
-    static FieldT pow(const FieldT &a, uint64_t e) { uint64_t w[4]; check(iopx_bn128_host_pow(detail::words(&a), e, w)); return from_words(w); }
-    static FieldT neg(const FieldT &a) { return sub(zero(), a); }
-    static FieldT inverse(const FieldT &a) { uint64_t w[4]; check(iopx_bn128_host_inverse(detail::words(&a), w)); return from_words(w); }
-    static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x) { return sub(pow(x, S.num_elements()), pow(S.shift(), S.num_elements())); }
-    static FieldT vanishing_derivative(const field_subset<FieldT> &S, const FieldT &x) { return mul(from_uint(S.num_elements()), pow(x, S.num_elements() - 1)); }
-    static bool element_in_domain(const field_subset<FieldT> &S, const FieldT &x)
-    {
-        const FieldT r = pow(mul(x, inverse(S.shift())), S.num_elements()), o = one();
-        return std::memcmp(&r, &o, sizeof(FieldT)) == 0;
-    }
-    static std::size_t soundness_bits() { return 253; }                  // floor(log2 r)
-};
+// the field's C entry for one table slot, e.g. field_entry<FieldT>(&ops::vector_ops::mul, "mul")(a, b, out, count)
+template<typename FieldT, typename Slot> inline auto field_entry(Slot slot, const char *op) { return field_host<FieldT>::entry(slot, op); }
+// its selection, for the domain-shaped operations: ops::rowcheck<field_of<FieldT>>(...)
+template<typename FieldT> using field_of = typename field_host<FieldT>::table;
 
 // ---- device memory -----------------------------------------------------------------------------------------------------------------
 namespace detail {

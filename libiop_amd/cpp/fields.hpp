@@ -21,10 +21,10 @@ template<> struct field_kind<gf192_element> { static const field_subset_type typ
 struct edwards_Fr_element {
     uint64_t w[3];
     edwards_Fr_element() : w{ 0, 0, 0 } {}
-    explicit edwards_Fr_element(uint64_t v) { check(iopx_fp3_from_uint(v, w)); }
+    explicit edwards_Fr_element(uint64_t v) { check(ops::edwards_Fr.from_uint(v, w)); }
     bool operator==(const edwards_Fr_element &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2]; }
     bool operator!=(const edwards_Fr_element &o) const { return !(*this == o); }
-    edwards_Fr_element operator+(const edwards_Fr_element &o) const { edwards_Fr_element r; check(iopx_fp3_host_add(w, o.w, r.w)); return r; }
+    edwards_Fr_element operator+(const edwards_Fr_element &o) const { edwards_Fr_element r; check(ops::edwards_Fr.host_add(w, o.w, r.w)); return r; }
 };
 template<> struct field_kind<edwards_Fr_element> { static const field_subset_type type = multiplicative_coset_type; };
 
@@ -32,7 +32,7 @@ template<> struct field_kind<edwards_Fr_element> { static const field_subset_typ
 struct alt_bn128_Fr_element {
     uint64_t w[4];
     alt_bn128_Fr_element() : w{ 0, 0, 0, 0 } {}
-    explicit alt_bn128_Fr_element(uint64_t v) { check(iopx_bn128_from_uint(v, w)); }
+    explicit alt_bn128_Fr_element(uint64_t v) { check(ops::alt_bn128_Fr.from_uint(v, w)); }
     bool operator==(const alt_bn128_Fr_element &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
     bool operator!=(const alt_bn128_Fr_element &o) const { return !(*this == o); }
 };

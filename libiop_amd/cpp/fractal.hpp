@@ -23,8 +23,7 @@ device_vector<FieldT> mul(const device_vector<FieldT> &a, const device_vector<Fi
 {
     if (a.size() != b.size()) throw std::invalid_argument("mul: size mismatch");
     device_vector<FieldT> out(a.size());
-    auto fn = field_host<FieldT>::additive() ? iopx_gf192_mul_dev : iopx_fp3_mul_dev;
-    check(fn(a.words(), b.words(), out.words(), a.size()));
+    check(field_entry<FieldT>(&V::mul, "mul")(a.words(), b.words(), out.words(), a.size()));
     return out;
 }
 
@@ -33,8 +32,7 @@ device_vector<FieldT> domain_offsets(const field_subset<FieldT> &D_in, const Fie
 {
     const field_subset<FieldT> D = dist::local_domain(D_in);
     device_vector<FieldT> out(D.num_elements());
-    if (additive(D)) check(iopx_domain_offsets_gf192_dev(basis_words(D), D.dimension(), shift_words(D), detail::words(&point), out.words()));
-    else check(iopx_domain_offsets_fp3_dev(D.dimension(), gen_words(D), shift_words(D), detail::words(&point), out.words()));
+    check(ops::domain_offsets<field_of<FieldT>>(domain_words<FieldT>(D), detail::words(&point), out.words()));
     return out;
 }
 
@@ -61,8 +59,7 @@ device_vector<FieldT> lincomb_affine(const std::vector<device_vector<FieldT>> &o
 {
     const std::vector<const void *> ptrs = pointers(oracles);
     device_vector<FieldT> out(oracles[0].size());
-    auto fn = field_host<FieldT>::additive() ? iopx_lincomb_affine_gf192_dev : iopx_lincomb_affine_fp3_dev;
-    check(fn(ptrs.data(), ptrs.size(), detail::words(coefficients.data()), detail::words(&constant), oracles[0].size(), out.words()));
+    check(field_entry<FieldT>(&V::lincomb_affine, "lincomb_affine")(ptrs.data(), ptrs.size(), detail::words(coefficients.data()), detail::words(&constant), oracles[0].size(), out.words()));
     return out;
 }
 
@@ -71,8 +68,7 @@ device_vector<FieldT> scaled(const device_vector<FieldT> &v, const FieldT &scale
 {
     const void *ptr = v.data();
     device_vector<FieldT> out(v.size());
-    auto fn = field_host<FieldT>::additive() ? iopx_lincomb_gf192_dev : iopx_lincomb_fp3_dev;
-    check(fn(&ptr, 1, detail::words(&scale), v.size(), out.words()));
+    check(field_entry<FieldT>(&V::lincomb, "scaled")(&ptr, 1, detail::words(&scale), v.size(), out.words()));
     return out;
 }
 
@@ -161,8 +157,7 @@ public:
         std::vector<const void *> Mz;
         for (std::size_t m = 0; m < num_matrices_; ++m) Mz.push_back(c[1 + m].data());
         device_vector<FieldT> out(c[0].size());
-        auto fn = field_host<FieldT>::additive() ? iopx_lincheck_gf192_dev : iopx_lincheck_fp3_dev;
-        check(fn(c[0].words(), Mz.data(), Mz.size(), detail::words(r_Mz_.data()), p_alpha_prime.words(), c.back().words(), c[0].size(), out.words()));
+        check(field_entry<FieldT>(&dev::V::lincheck, "lincheck")(c[0].words(), Mz.data(), Mz.size(), detail::words(r_Mz_.data()), p_alpha_prime.words(), c.back().words(), c[0].size(), out.words()));
         return out;
     }
 };
@@ -199,8 +194,7 @@ class rational_linear_combination {
         {
             const std::vector<const void *> np = dev::pointers(numerators), dp = dev::pointers(denominators);
             device_vector<FieldT> N(numerators[0].size()), D(numerators[0].size());
-            auto fn = field_host<FieldT>::additive() ? iopx_rational_combine_gf192_dev : iopx_rational_combine_fp3_dev;
-            check(fn(np.data(), dp.data(), num_rationals, detail::words(coefficients.data()), numerators[0].size(), N.words(), D.words()));
+            check(field_entry<FieldT>(&dev::V::rational_combine, "rational_combine")(np.data(), dp.data(), num_rationals, detail::words(coefficients.data()), numerators[0].size(), N.words(), D.words()));
             last_key = dp; last_N = N; last_D = D; last_denominators = denominators;
             return { N, D };
         }
@@ -305,18 +299,15 @@ public:
         if (c.size() != 3) throw std::invalid_argument("sumcheck_constraint_oracle has three constituent oracles");
         const field_subset<FieldT> L = dist::local_domain(D);
         const field_subset<FieldT> &K = summation_domain_;
-        device_vector<FieldT> out(L.num_elements());
+        device_vector<FieldT> out(L.num_elements()), xinv;                                   // 1 / x over L: the subspace form reads it
         if (dev::additive(L)) {
             if (K.dimension() > L.dimension()) throw std::invalid_argument("the summation domain exceeds this rank's part of the codeword domain");
             for (std::size_t i = 0; i < K.dimension(); ++i)
                 if (std::memcmp(&K.basis()[i], &L.basis()[i], sizeof(FieldT)) != 0) throw std::invalid_argument("the summation domain must be spanned by a prefix of the codeword domain's basis");
-            const device_vector<FieldT> xinv = dev::div<FieldT>(nullptr, dev::domain_offsets<FieldT>(L, field_host<FieldT>::zero()));
-            check(iopx_rational_sumcheck_constraint_gf192_dev(c[0].words(), c[1].words(), c[2].words(), xinv.words(), dev::basis_words(L), L.dimension(), dev::shift_words(L),
-                                                              K.dimension(), dev::shift_words(K), detail::words(&claimed_sum_), out.words()));
-        } else {
-            check(iopx_rational_sumcheck_constraint_fp3_dev(c[0].words(), c[1].words(), c[2].words(), L.dimension(), dev::gen_words(L), dev::shift_words(L), K.dimension(),
-                                                            dev::shift_words(K), detail::words(&claimed_sum_), out.words()));
+            xinv = dev::div<FieldT>(nullptr, dev::domain_offsets<FieldT>(L, field_host<FieldT>::zero()));
         }
+        check(ops::rational_sumcheck_constraint<field_of<FieldT>>(dev::domain_words<FieldT>(L), c[0].words(), c[1].words(), c[2].words(), xinv.words(), K.dimension(),
+                                                                  dev::shift_words(K), detail::words(&claimed_sum_), out.words()));
         return out;
     }
 };

@@ -100,7 +100,7 @@ public:
         std::vector<FieldT> out(num_elements);
         uint64_t modulus[WORDS] = {};
         const bool additive = field_host<FieldT>::additive();
-        if (!additive) check(WORDS == 4 ? iopx_bn128_modulus(modulus) : iopx_fp3_modulus(modulus));
+        if (!additive) check(field_entry<FieldT>(&ops::prime_field_ops::modulus, "squeeze")(modulus));
         for (std::size_t i = 0; i < num_elements; ++i) {
             uint64_t key = i, w[WORDS];
             for (;;) {
@@ -200,12 +200,12 @@ public:
     std::vector<std::size_t> squeeze_query_positions(std::size_t num_positions, std::size_t range_of_positions)
     {
         const std::vector<FieldT> x = squeeze(num_positions);
-        uint64_t raw_one[4] = { 1, 0, 0, 0 };                       // Montgomery product with the plain integer 1: x R * 1 / R = x
+        const uint64_t raw_one[4] = { 1, 0, 0, 0 };                 // Montgomery product with the plain integer 1: x R * 1 / R = x
+        const FieldT plain_one = field_host<FieldT>::from_words(raw_one);
         std::vector<std::size_t> out;
         for (const FieldT &e : x) {
-            uint64_t canon[4];
-            check(iopx_bn128_host_mul(detail::words(&e), raw_one, canon));
-            out.push_back((std::size_t)(canon[0] % range_of_positions));
+            const FieldT canon = field_host<FieldT>::mul(e, plain_one);
+            out.push_back((std::size_t)(detail::words(&canon)[0] % range_of_positions));
         }
         return out;
     }

@@ -107,12 +107,12 @@ class multiplicative_coset {
     std::size_t order_;
     FieldT g_, shift_;
     static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32, "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
-    static constexpr bool bn128 = sizeof(FieldT) == 32;
+    typedef ops::layout<sizeof(FieldT)> F;                                                  // by size: the mirror asks nothing of FieldT beyond its bytes
+    typedef ops::prime_field_ops P;
     static FieldT host_mul(const FieldT &a, const FieldT &b)
     {
         FieldT r;
-        check(bn128 ? iopx_bn128_host_mul(detail::words(&a), detail::words(&b), detail::words(&r))
-                    : iopx_fp3_host_mul(detail::words(&a), detail::words(&b), detail::words(&r)));
+        check(ops::entry<F>(&P::host_mul, "multiplicative_coset")(detail::words(&a), detail::words(&b), detail::words(&r)));
         return r;
     }
 public:
@@ -124,8 +124,7 @@ public:
     multiplicative_coset(std::size_t order, const FieldT &shift) : order_(order), shift_(shift)        // subgroup.tcc:33-75, 199-215
     {
         if (order == 0 || (order & (order - 1))) throw std::invalid_argument("The order of the subgroup must be a power of two.");
-        check(bn128 ? iopx_bn128_subgroup_generator(detail::log2_ceil(order), detail::words(&g_))
-                    : iopx_fp3_subgroup_generator(detail::log2_ceil(order), detail::words(&g_)));
+        check(ops::entry<F>(&P::subgroup_generator, "multiplicative_coset")(detail::log2_ceil(order), detail::words(&g_)));
     }
     std::size_t num_elements() const { return order_; }
     std::size_t dimension() const { return detail::log2_ceil(order_); }
@@ -135,13 +134,13 @@ public:
     {
         if (index >= order_) throw std::invalid_argument("element index out of bounds");
         FieldT p;
-        check(bn128 ? iopx_bn128_host_pow(detail::words(&g_), index, detail::words(&p)) : iopx_fp3_host_pow(detail::words(&g_), index, detail::words(&p)));
+        check(ops::entry<F>(&P::host_pow, "element_by_index")(detail::words(&g_), index, detail::words(&p)));
         return host_mul(shift_, p);
     }
     FieldT element_outside_of_subset() const                                               // subgroup.tcc:311-315
     {
         FieldT gen;
-        check(bn128 ? iopx_bn128_multiplicative_generator(detail::words(&gen)) : iopx_fp3_multiplicative_generator(detail::words(&gen)));
+        check(ops::entry<F>(&P::multiplicative_generator, "element_outside_of_subset")(detail::words(&gen)));
         return host_mul(shift_, gen);
     }
     // subgroup.tcc:149-173

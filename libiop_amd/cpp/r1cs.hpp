@@ -55,8 +55,7 @@ struct sparse_matrix {
     void times_vector(const device_vector<FieldT> &vec, const device_vector<FieldT> &out, const FieldT *scale = nullptr, bool accumulate = false) const
     {
         if (out.size() != rows) throw std::invalid_argument("sparse_matrix::times_vector: output size != rows");
-        auto fn = field_host<FieldT>::additive() ? iopx_spmv_gf192_dev : iopx_spmv_fp3_dev;
-        check(fn(d_row_ptr.data(), d_col.data(), d_coeff.words(), rows, vec.words(), scale ? detail::words(scale) : nullptr, accumulate ? 1 : 0, out.words()));
+        check(field_entry<FieldT>(&ops::vector_ops::spmv, "times_vector")(d_row_ptr.data(), d_col.data(), d_coeff.words(), rows, vec.words(), scale ? detail::words(scale) : nullptr, accumulate ? 1 : 0, out.words()));
     }
     // The transpose with output row out_row_of_col[c] for column c; an entry's new column is its old row.
     sparse_matrix transposed_onto(std::size_t num_rows_out, const std::vector<std::size_t> &out_row_of_col) const
@@ -152,12 +151,12 @@ r1cs_example<FieldT> generate_r1cs_example(std::size_t num_constraints, std::siz
     };
     auto product = [&](const device_vector<FieldT> &a, const device_vector<FieldT> &b) {
         device_vector<FieldT> out(a.size());
-        check((H::additive() ? iopx_gf192_mul_dev : iopx_fp3_mul_dev)(a.words(), b.words(), out.words(), a.size()));
+        check(field_entry<FieldT>(&ops::vector_ops::mul, "mul")(a.words(), b.words(), out.words(), a.size()));
         return out;
     };
     const device_vector<FieldT> ab = product(gathered(d_z, a_idx), gathered(d_z, b_idx));
     device_vector<FieldT> z_inv(num_variables);
-    check((H::additive() ? iopx_gf192_inv_dev : iopx_fp3_inv_dev)(d_z.words(), z_inv.words(), num_variables));      // zero stays zero
+    check(field_entry<FieldT>(&ops::vector_ops::inv, "inv")(d_z.words(), z_inv.words(), num_variables));      // zero stays zero
     const std::vector<FieldT> coef = product(ab, gathered(z_inv, c_idx)).to_host(), ab_host = ab.to_host();
     r1cs_constraint_system<FieldT> &cs = ex.constraint_system;
     cs.primary_input_size_ = num_inputs;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/libiop_amd.h"
+#include "field_ops.hpp"                 // the per-field C entries; selected by sizeof(FieldT) here, the stubs do not see field_kind
 
 namespace libiop_amd {
 
@@ -81,12 +82,8 @@ std::vector<FieldT> multiplicative_FFT(const std::vector<FieldT> &poly_coeffs, c
                   "libiop_amd accelerates prime fields with libff::edwards_Fr's (three) or alt_bn128_Fr's (four Montgomery words) layout");
     const FieldT g = domain.generator(), shift = domain.shift();
     std::vector<FieldT> out(domain.num_elements());
-    if constexpr (sizeof(FieldT) == 24)
-        check(iopx_mul_fft_fp3(detail::words(poly_coeffs.data()), poly_coeffs.size(), domain.dimension(), detail::words(&g),
-                               detail::words(&shift), detail::words(out.data())));
-    else
-        check(iopx_mul_fft_bn128(detail::words(poly_coeffs.data()), poly_coeffs.size(), domain.dimension(), detail::words(&g),
-                                 detail::words(&shift), detail::words(out.data())));
+    check(ops::entry<ops::layout<sizeof(FieldT)>>(&ops::prime_field_ops::mul_fft_host, "multiplicative_FFT")(
+        detail::words(poly_coeffs.data()), poly_coeffs.size(), domain.dimension(), detail::words(&g), detail::words(&shift), detail::words(out.data())));
     return out;
 }
 
@@ -99,12 +96,8 @@ std::vector<FieldT> multiplicative_IFFT(const std::vector<FieldT> &evals, const 
     if (evals.size() != domain.num_elements()) throw std::invalid_argument("multiplicative_IFFT: evaluation count != domain size");
     const FieldT g = domain.generator(), shift = domain.shift();
     std::vector<FieldT> out(domain.num_elements());
-    if constexpr (sizeof(FieldT) == 24)
-        check(iopx_mul_ifft_fp3(detail::words(evals.data()), domain.dimension(), detail::words(&g), detail::words(&shift),
-                                detail::words(out.data())));
-    else
-        check(iopx_mul_ifft_bn128(detail::words(evals.data()), domain.dimension(), detail::words(&g), detail::words(&shift),
-                                  detail::words(out.data())));
+    check(ops::entry<ops::layout<sizeof(FieldT)>>(&ops::prime_field_ops::mul_ifft_host, "multiplicative_IFFT")(
+        detail::words(evals.data()), domain.dimension(), detail::words(&g), detail::words(&shift), detail::words(out.data())));
     return out;
 }
 
@@ -133,12 +126,8 @@ std::shared_ptr<std::vector<FieldT>> multiplicative_evaluate_next_f_i_over_entir
     if (f_i_evals->size() != f_i_domain.num_elements()) throw std::invalid_argument("f_i size != domain size");
     const FieldT g = f_i_domain.generator(), shift = f_i_domain.shift();
     auto next = std::make_shared<std::vector<FieldT>>(f_i_domain.num_elements() / coset_size);
-    if constexpr (sizeof(FieldT) == 24)
-        check(iopx_fri_fold_mul_fp3(detail::words(f_i_evals->data()), f_i_domain.dimension(), detail::words(&g), detail::words(&shift),
-                                    coset_size, detail::words(&x_i), detail::words(next->data())));
-    else
-        check(iopx_fri_fold_mul_bn128(detail::words(f_i_evals->data()), f_i_domain.dimension(), detail::words(&g), detail::words(&shift),
-                                      coset_size, detail::words(&x_i), detail::words(next->data())));
+    check(ops::entry<ops::layout<sizeof(FieldT)>>(&ops::prime_field_ops::fri_fold_mul_host, "multiplicative_evaluate_next_f_i_over_entire_domain")(
+        detail::words(f_i_evals->data()), f_i_domain.dimension(), detail::words(&g), detail::words(&shift), coset_size, detail::words(&x_i), detail::words(next->data())));
     return next;
 }
 
@@ -168,30 +157,19 @@ std::shared_ptr<std::vector<FieldT>> ldt_combine(const std::vector<std::shared_p
 {
     static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32,
                   "FieldT must have a 24-byte (libff::gf192 / libff::edwards_Fr) or, multiplicative only, a 32-byte (alt_bn128_Fr) layout");
-    if constexpr (sizeof(FieldT) == 32) {
-        if (!multiplicative) throw std::invalid_argument("ldt_combine: a 32-byte field has multiplicative domains only");
-    }
+    typedef ops::layout<sizeof(FieldT)> F;
     const std::size_t n = codeword_domain.num_elements();
+    const FieldT shift = codeword_domain.shift(), g = multiplicative ? codeword_domain.generator() : shift;
+    const ops::domain L = { !multiplicative, multiplicative ? nullptr : detail::words(codeword_domain.basis().data()), detail::words(&g), detail::words(&shift),
+                            codeword_domain.dimension() };
+    ops::subspace<F>(L, "ldt_combine");                                                     // a field without subspaces is refused before anything is allocated
     std::vector<void *> bufs(constituents.size() + 1, nullptr);
     auto result = std::make_shared<std::vector<FieldT>>(n);
-    const FieldT shift = codeword_domain.shift();
     int rc = IOPX_OK;
     for (std::size_t k = 0; k < bufs.size() && rc == IOPX_OK; ++k) rc = iopx_malloc(&bufs[k], n * sizeof(FieldT));
     for (std::size_t k = 0; k + 1 < bufs.size() && rc == IOPX_OK; ++k) rc = iopx_memcpy_h2d(bufs[k], constituents[k]->data(), n * sizeof(FieldT));
-    if (rc == IOPX_OK && multiplicative) {                                                  // ldt_reducer_aux.tcc:104-128
-        const FieldT g = codeword_domain.generator();
-        if constexpr (sizeof(FieldT) == 24)
-            rc = iopx_ldt_combine_fp3_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
-                                          codeword_domain.dimension(), detail::words(&g), detail::words(&shift), (uint64_t *)bufs.back());
-        else
-            rc = iopx_ldt_combine_bn128_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
-                                            codeword_domain.dimension(), detail::words(&g), detail::words(&shift), (uint64_t *)bufs.back());
-    } else if (rc == IOPX_OK) {                                                             // :78-103
-        if constexpr (sizeof(FieldT) == 24)
-            rc = iopx_ldt_combine_gf192_dev(bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()),
-                                            detail::words(codeword_domain.basis().data()), codeword_domain.dimension(), detail::words(&shift),
-                                            (uint64_t *)bufs.back());
-    }
+    if (rc == IOPX_OK)                                                                      // ldt_reducer_aux.tcc:104-128 (cosets) / :78-103 (subspaces)
+        rc = ops::ldt_combine<F>(L, bufs.data(), bufs.size() - 1, input_oracle_degrees.data(), detail::words(coefficients.data()), (uint64_t *)bufs.back());
     if (rc == IOPX_OK) rc = iopx_memcpy_d2h(result->data(), bufs.back(), n * sizeof(FieldT));
     for (void *b : bufs) if (b) iopx_free(b);
     check(rc);

@@ -203,6 +203,11 @@ int iopx_fp3_host_pow(const uint64_t *a, uint64_t exponent, uint64_t *out);
  *                                       (ldt_reducer_aux.tcc:104-128); arguments as iopx_ldt_combine_fp3_dev */
 int iopx_mul_fft_bn128_dev(const uint64_t *d_coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen,
                            const uint64_t *shift, uint64_t *d_out);
+/* ... with windows of the output from the same last pass: arguments and checks of iopx_mul_fft_fp3_windows_dev, four words per element */
+int iopx_mul_fft_bn128_windows_dev(const uint64_t *d_coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out,
+                                   size_t num_windows, const size_t *window_first, const size_t *window_log_stride, uint64_t *const *d_windows);
+/* the number of kernel passes the forward transform of n_coeffs coefficients over 2^log_n points takes (the same tiling for both prime fields) */
+int iopx_mul_fft_pass_count(size_t log_n, size_t n_coeffs, size_t *num_passes);
 int iopx_mul_fft_bn128(const uint64_t *coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen,
                        const uint64_t *shift, uint64_t *out);
 int iopx_mul_ifft_bn128_dev(const uint64_t *d_evals, size_t log_n, const uint64_t *gen, const uint64_t *shift,
@@ -594,7 +599,7 @@ int iopx_fp3_modulus(uint64_t *out);
  * caller releases with iopx_host_free. */
 #define IOPX_FIELD_GF192 0
 #define IOPX_FIELD_EDWARDS_FR 1
-#define IOPX_FIELD_ALT_BN128_FR 2   /* the FRI-only SNARK (iopx_fri_snark_prove, iopx_fri_snark_prove_hashed); no Aurora / Fractal instance over it yet */
+#define IOPX_FIELD_ALT_BN128_FR 2   /* Aurora instances (BLAKE2b or Poseidon: iopx_aurora_prove_hashed) and the FRI-only SNARK; no Fractal, no distributed prover */
 /* bcs_hash_type (libiop/bcs/hashing/hash_enum.hpp:21-26), as iopx_poseidon_shipped_params takes it */
 #define IOPX_HASH_BLAKE2B 1
 #define IOPX_HASH_POSEIDON_STARKWARE 2
@@ -603,10 +608,10 @@ typedef struct iopx_r1cs {
     size_t num_constraints, num_variables, num_inputs;
     const uint64_t *row_ptr[3];   /* A, B, C: num_constraints + 1 offsets each */
     const uint32_t *col[3];       /* column of each entry */
-    const uint64_t *coeff[3];     /* 3 words per entry */
+    const uint64_t *coeff[3];     /* 3 words per entry; 4 over IOPX_FIELD_ALT_BN128_FR */
 } iopx_r1cs;
 typedef struct iopx_aurora_instance iopx_aurora_instance;
-/* assignment: num_variables elements (primary inputs first), host memory */
+/* assignment: num_variables elements (primary inputs first), host memory; 3 words per element, 4 over IOPX_FIELD_ALT_BN128_FR (mont_repr) */
 int iopx_aurora_instance_create(const iopx_r1cs *r1cs, const uint64_t *assignment, int field, iopx_aurora_instance **out);
 /* generate_r1cs_example (libiop/relations/examples/r1cs_examples.tcc:23-78) seeded with SplitMix64 */
 int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_t num_inputs, size_t num_variables, uint64_t seed,
@@ -618,6 +623,12 @@ int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_
 int iopx_aurora_instance_warm(iopx_aurora_instance *instance, int protocol, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter);
 int iopx_aurora_prove(iopx_aurora_instance *instance, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter,
                       uint8_t **transcript, size_t *transcript_bytes);
+/* The same prover with the BCS hash family named: IOPX_HASH_BLAKE2B is iopx_aurora_prove.  The Poseidon families exist over IOPX_FIELD_ALT_BN128_FR
+ * only (as for iopx_fri_snark_prove_hashed): every round's roots are absorbed by the algebraic hashchain, so each tree's root is read back at its round's
+ * end.  Refused with IOPX_ERR_INVALID_ARGUMENT: Poseidon over a 24-byte field, an unknown hash, and — over IOPX_FIELD_ALT_BN128_FR — a parameter set
+ * whose codeword domain exceeds 2^28 points, a communicator (iopx_aurora_prove_dist), and iopx_fractal_index / iopx_fractal_prove. */
+int iopx_aurora_prove_hashed(iopx_aurora_instance *instance, int bcs_hash_type, size_t security_parameter, size_t RS_extra_dimensions,
+                             size_t FRI_localization_parameter, uint8_t **transcript, size_t *transcript_bytes);
 /* fractal_snark_indexer / fractal_snark_prover (libiop/snark/fractal_snark.tcc:114-162; non-zk, BLAKE2b; RS_extra_dimensions 3 and
  * localization 2 in profiling/instrument_fractal_snark.cpp:93-120) on the same instance handle (square matrices: num_constraints =
  * num_variables + 1).  iopx_fractal_index builds the prover index — twelve index oracles over the codeword domain, their Merkle tree and

@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "iopx_memcpy_d2h_deferrable", "iopx_comm_rccl_unique_id", "iopx_comm_create_rccl", "iopx_comm_create_callbacks", "iopx_comm_create_replay", "iopx_comm_is_replay", "iopx_cold_stats", "iopx_cold_add", "iopx_gf192_mul_halves_dev", "iopx_mul_fft_fp3_windows_dev", "iopx_set_option", "iopx_clear_option", "iopx_get_option", "iopx_comm_destroy", "iopx_comm_rank",
     "iopx_comm_all_gather_dev", "iopx_comm_all_reduce_u64_dev", "iopx_comm_broadcast_dev", "iopx_comm_all_to_all_dev", "iopx_comm_sendrecv_dev", "iopx_comm_stats", "iopx_comm_bind_transforms", "iopx_add_taylor_inv_gf192_dev", "iopx_add_combine_inv_gf192_dev",
     "iopx_interleave_dev", "iopx_gather_rows_dev", "iopx_fri_snark_prove", "iopx_fri_snark_prove_dist", "iopx_fri_snark_prove_hashed", "iopx_poseidon_permute_bn128_host", "iopx_add_fft_gf192_dist_dev", "iopx_add_ifft_gf192_dist_dev", "iopx_aurora_prove_dist", "iopx_fractal_index_dist", "iopx_fractal_prove_dist",
+    "iopx_mul_fft_bn128_windows_dev", "iopx_mul_fft_pass_count", "iopx_aurora_prove_hashed",
     "iopx_mul_fft_bn128_dev", "iopx_mul_fft_bn128", "iopx_mul_ifft_bn128_dev", "iopx_mul_ifft_bn128", "iopx_mul_ifft_known_degree_bn128_dev",
     "iopx_fri_fold_mul_bn128_dev", "iopx_fri_fold_mul_bn128", "iopx_ldt_combine_bn128_dev",
     "iopx_bn128_subgroup_generator", "iopx_bn128_multiplicative_generator", "iopx_bn128_host_mul", "iopx_bn128_host_pow", "iopx_bn128_host_inverse", "iopx_bn128_from_uint",
@@ -191,6 +192,8 @@ class Library:
         c.iopx_fri_fold_mul_fp3_dev.argtypes = [_vp, _sz, _u64p, _u64p, _sz, _u64p, _vp]
         c.iopx_fri_fold_mul_fp3.argtypes = [_u64p, _sz, _u64p, _u64p, _sz, _u64p, _u64p]
         c.iopx_mul_fft_bn128_dev.argtypes = [_vp, _sz, _sz, _u64p, _u64p, _vp]
+        c.iopx_mul_fft_bn128_windows_dev.argtypes = c.iopx_mul_fft_fp3_windows_dev.argtypes
+        c.iopx_mul_fft_pass_count.argtypes = [_sz, _sz, ctypes.POINTER(_sz)]
         c.iopx_mul_fft_bn128.argtypes = [_u64p, _sz, _sz, _u64p, _u64p, _u64p]
         c.iopx_mul_ifft_bn128_dev.argtypes = [_vp, _sz, _u64p, _u64p, _vp]
         c.iopx_mul_ifft_bn128.argtypes = [_u64p, _sz, _u64p, _u64p, _u64p]
@@ -509,6 +512,23 @@ class Library:
         if n != 1 << log_n:
             raise ValueError("%s: %d evaluations is not a power of two" % (what, n))
         return log_n
+
+    def multiplicative_FFT_pass_count(self, log_n, n_coeffs):
+        """kernel passes of the forward coset transform of n_coeffs coefficients over 2^log_n points (either prime field)"""
+        n = _sz(0)
+        self._check(self.c.iopx_mul_fft_pass_count(int(log_n), int(n_coeffs), ctypes.byref(n)))
+        return n.value
+
+    def multiplicative_FFT_windows_bn128_dev(self, d_coeffs, n_coeffs, log_n, shift, d_out, windows, gen=None):
+        """multiplicative_FFT_windows_dev over alt_bn128 Fr (four words per element): windows = [(first, log_stride, d_window), ...]"""
+        shift = _as_u64(shift, 4)
+        gen = _as_u64(self.bn128_subgroup_generator(log_n) if gen is None else gen, 4)
+        k = len(windows)
+        first = (_sz * max(k, 1))(*[int(w[0]) for w in windows])
+        log_stride = (_sz * max(k, 1))(*[int(w[1]) for w in windows])
+        dst = (_vp * max(k, 1))(*[w[2] for w in windows])
+        self._check(self.c.iopx_mul_fft_bn128_windows_dev(_vp(d_coeffs), int(n_coeffs), int(log_n), gen.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p),
+                                                          _vp(d_out), k, first, log_stride, dst))
 
     def multiplicative_FFT_bn128(self, poly_coeffs, log_n, shift, gen=None):
         """multiplicative_FFT(poly_coeffs, multiplicative_coset(2^log_n, shift)) over alt_bn128 Fr — fft.tcc:236-317."""
@@ -848,7 +868,8 @@ class Library:
     def aurora_instance(self, field_code, matrices, num_variables, num_inputs, assignment):
         """iopx_aurora_instance_create: an instance from the caller's own constraint system and variable assignment.  matrices = three
         (row_ptr, col, coeff) triples in CSR form (A, B, C; coeff: (entries, 3) uint64 words; column 0 is the constant 1), assignment =
-        (num_variables, 3) words, primary inputs first.  Release with aurora_instance_free."""
+        (num_variables, 3) words, primary inputs first; four words per element over FIELD_ALT_BN128_FR (2).  Release with aurora_instance_free."""
+        words = 4 if int(field_code) == 2 else 3
         class _R1CS(ctypes.Structure):
             _fields_ = [("num_constraints", _sz), ("num_variables", _sz), ("num_inputs", _sz), ("row_ptr", _u64p * 3),
                         ("col", ctypes.POINTER(ctypes.c_uint32) * 3), ("coeff", _u64p * 3)]
@@ -856,17 +877,24 @@ class Library:
         r.num_constraints, r.num_variables, r.num_inputs = len(matrices[0][0]) - 1, int(num_variables), int(num_inputs)
         for q, (row_ptr, col, coeff) in enumerate(matrices):
             rp, cl = np.ascontiguousarray(row_ptr, dtype=np.uint64), np.ascontiguousarray(col, dtype=np.uint32)
-            cf = np.ascontiguousarray(coeff, dtype=np.uint64).reshape(-1, 3)
+            cf = np.ascontiguousarray(coeff, dtype=np.uint64).reshape(-1, words)
             keep += [rp, cl, cf]
             r.row_ptr[q], r.col[q], r.coeff[q] = rp.ctypes.data_as(_u64p), cl.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cf.ctypes.data_as(_u64p)
-        z = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, 3)
+        z = np.ascontiguousarray(assignment, dtype=np.uint64).reshape(-1, words)
+        if z.shape[0] != r.num_variables:
+            raise ValueError("assignment: %d elements of %d words for %d variables" % (z.shape[0], words, r.num_variables))
         h = ctypes.c_void_p()
         self.c.iopx_aurora_instance_create.argtypes = [ctypes.c_void_p, _u64p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
         self._check(self.c.iopx_aurora_instance_create(ctypes.byref(r), z.ctypes.data_as(_u64p), int(field_code), ctypes.byref(h)))
         return h
 
-    def aurora_prove(self, instance, security_parameter=128, RS_extra_dimensions=5, FRI_localization_parameter=2):
-        """aurora_snark_prover through the C ABI: the canonical transcript bytes."""
+    def aurora_prove(self, instance, security_parameter=128, RS_extra_dimensions=5, FRI_localization_parameter=2, hash=None):
+        """aurora_snark_prover through the C ABI: the canonical transcript bytes.  `hash`: a bcs_hash_type (HASH_BLAKE2B, HASH_POSEIDON_STARKWARE,
+        HASH_POSEIDON_HIGH_ALPHA; Poseidon over alt_bn128 Fr only) through iopx_aurora_prove_hashed; None: BLAKE2b through iopx_aurora_prove."""
+        if hash is not None:
+            self.c.iopx_aurora_prove_hashed.argtypes = [ctypes.c_void_p, ctypes.c_int, _sz, _sz, _sz, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_sz)]
+            return self._transcript_call(self.c.iopx_aurora_prove_hashed, instance, int(hash), int(security_parameter), int(RS_extra_dimensions),
+                                         int(FRI_localization_parameter))
         buf, n = ctypes.c_void_p(), _sz(0)
         self.c.iopx_aurora_prove.argtypes = [ctypes.c_void_p, _sz, _sz, _sz, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(_sz)]
         self._check(self.c.iopx_aurora_prove(instance, int(security_parameter), int(RS_extra_dimensions), int(FRI_localization_parameter), ctypes.byref(buf), ctypes.byref(n)))

@@ -1,4 +1,4 @@
-// Aurora SNARK prover (non-zk, BLAKE2b) for C++ callers: the reference's composition, every vector in HBM.
+// Aurora SNARK prover (non-zk; BLAKE2b or, over alt_bn128 Fr, Poseidon) for C++ callers: the reference's composition, every vector in HBM.
 //
 //   aurora_snark_parameters / aurora_snark_prover        libiop/snark/aurora_snark.tcc:38-146
 //   aurora_iop_parameters, aurora_iop                    libiop/protocols/aurora_iop.tcc:3-186, 262-344
@@ -75,9 +75,10 @@ device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coe
     device_vector<FieldT> out(D.num_elements());
     if (additive(D)) { check(iopx_add_fft_gf192_dev(coeffs.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), out.words())); return out; }
     // the windows the prover will ask for (dist::window_collector) leave the transform's last pass together with the codeword
-    // (a field without that entry takes the plain transform: the prover gathers them)
+    // (a field without that entry takes the plain transform: the prover gathers them; so does alt_bn128 Fr under IOPX_BN128_FFT_WINDOWS=0)
     const P *prime = field_of<FieldT>::prime;
-    const auto mul_fft_windows = prime ? prime->mul_fft_windows : nullptr;
+    const bool with_windows = prime && (sizeof(FieldT) != 32 || iopx_get_option("IOPX_BN128_FFT_WINDOWS", 1) != 0);
+    const auto mul_fft_windows = with_windows ? prime->mul_fft_windows : nullptr;
     dist::window_collector<FieldT> *col = mul_fft_windows ? dist::active_collector<FieldT>() : nullptr;
     if (col && col->domain_elements == D.num_elements() && !col->wanted.empty()) {
         typename dist::window_collector<FieldT>::entry e;
@@ -129,7 +130,7 @@ std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &
         const bool copy_first = H_is_first_coset && range.first == 0 && range.second > 1 && H.shift() == L.shift();
         for (std::size_t k = 0; k < batch; ++k) {
             if (copy_first) outs[k].slice(0, n).copy_from(packed.slice(k * n, n));
-            ptrs.push_back(outs[k].words() + (copy_first ? 3 * n : 0));
+            ptrs.push_back(outs[k].words() + (copy_first ? sizeof(FieldT) / 8 * n : 0));
         }
         if (copy_first) { range.first = 1; range.second -= 1; }
         check(iopx_add_reextend_gf192_batch_dev(packed.words(), batch, basis_words(L), L.dimension(), H.dimension(), shift_words(H), shift_words(L), range.first,
@@ -365,9 +366,9 @@ struct aurora_snark_parameters {
         : security_parameter_(security_parameter), RS_extra_dimensions_(RS_extra_dimensions), num_constraints_(num_constraints), num_variables_(num_variables),
           num_inputs_(num_inputs)
     {
-        // bcs_prover (iop.hpp) hashes with 32-byte BLAKE2b digests = the reference's digest_len_bytes = 2 * security_parameter / 8
+        // bcs_prover (iop.hpp) hashes with 32-byte digests = the reference's digest_len_bytes = 2 * security_parameter / 8
         // (blake2b.tcc:15) for 128 only; other values would prove with digests the reference does not use
-        if (security_parameter != 128) throw std::invalid_argument("libiop_amd: security_parameter must be 128 (32-byte BLAKE2b digests)");
+        if (security_parameter != 128) throw std::invalid_argument("libiop_amd: security_parameter must be 128 (32-byte digests)");
         if (!is_pow2(num_constraints)) throw std::invalid_argument("number of constraints in the constraint system must a power of two.");
         if (!is_pow2(num_variables + 1)) throw std::invalid_argument("number of variables in the constraint system must be one less than a power of two.");
         if (!is_pow2(num_inputs + 1)) throw std::invalid_argument("number of inputs in the constraint system must be one less than a power of two.");
@@ -1159,10 +1160,10 @@ public:
 
 namespace detail {
 // registration, rounds, then `finish(IOP)`: the structured transcript or its canonical bytes
-template<typename FieldT, typename Finish>
+template<typename FieldT, typename HashPolicy, typename Finish>
 auto run_aurora_prover(const r1cs_constraint_system<FieldT> &constraint_system, const r1cs_primary_input<FieldT> &primary_input,
                        const r1cs_auxiliary_input<FieldT> &auxiliary_input, const aurora_snark_parameters<FieldT> &parameters,
-                       const device_vector<FieldT> *d_assignment, Finish finish) -> decltype(finish(std::declval<bcs_prover<FieldT> &>()))
+                       const device_vector<FieldT> *d_assignment, const HashPolicy &hash, Finish finish) -> decltype(finish(std::declval<bcs_prover<FieldT> &>()))
 {
     // IOPX_HOST_TIMING=1: wall-clock marks of the host-side phases on stderr (registration before the first kernel, the rounds, transcript extraction)
     const bool timing = iopx_get_option("IOPX_HOST_TIMING", 0) != 0;
@@ -1170,7 +1171,7 @@ auto run_aurora_prover(const r1cs_constraint_system<FieldT> &constraint_system, 
     auto mark = [&](const char *what) {
         if (timing) std::fprintf(stderr, "[iopx host] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
     };
-    bcs_prover<FieldT> IOP(parameters.pow_bits_);
+    bcs_prover<FieldT> IOP(parameters.pow_bits_, nullptr, hash.template family<FieldT>());
     aurora_iop<FieldT> full_protocol(IOP, constraint_system, parameters);
     full_protocol.register_interactions();
     IOP.seal_interaction_registrations();
@@ -1189,23 +1190,24 @@ auto run_aurora_prover(const r1cs_constraint_system<FieldT> &constraint_system, 
 } // namespace detail
 
 // aurora_snark_prover (aurora_snark.tcc:119-146).  With d_assignment — the (1, primary, auxiliary) vector already in HBM — the
-// witness never crosses PCIe inside the call.
-template<typename FieldT>
+// witness never crosses PCIe inside the call.  HashPolicy: `blake2b` (the default: what default_bcs_params wires for every field) or
+// `poseidon` (alt_bn128 Fr only), iop.hpp — as for FRI_snark_prover.
+template<typename FieldT, typename HashPolicy = blake2b>
 bcs_transformation_transcript<FieldT> aurora_snark_prover(const r1cs_constraint_system<FieldT> &constraint_system, const r1cs_primary_input<FieldT> &primary_input,
                                                           const r1cs_auxiliary_input<FieldT> &auxiliary_input, const aurora_snark_parameters<FieldT> &parameters,
-                                                          const device_vector<FieldT> *d_assignment = nullptr)
+                                                          const device_vector<FieldT> *d_assignment = nullptr, const HashPolicy &hash = HashPolicy())
 {
-    return detail::run_aurora_prover<FieldT>(constraint_system, primary_input, auxiliary_input, parameters, d_assignment,
+    return detail::run_aurora_prover<FieldT>(constraint_system, primary_input, auxiliary_input, parameters, d_assignment, hash,
                                              [](bcs_prover<FieldT> &IOP) { return IOP.get_transcript(); });
 }
 
 // ... returning aurora_snark_prover(...).serialize() without building the structured transcript (bcs_prover::get_transcript_bytes): what the C ABI hands out
-template<typename FieldT>
+template<typename FieldT, typename HashPolicy = blake2b>
 std::string aurora_snark_prover_serialized(const r1cs_constraint_system<FieldT> &constraint_system, const r1cs_primary_input<FieldT> &primary_input,
                                            const r1cs_auxiliary_input<FieldT> &auxiliary_input, const aurora_snark_parameters<FieldT> &parameters,
-                                           const device_vector<FieldT> *d_assignment = nullptr)
+                                           const device_vector<FieldT> *d_assignment = nullptr, const HashPolicy &hash = HashPolicy())
 {
-    return detail::run_aurora_prover<FieldT>(constraint_system, primary_input, auxiliary_input, parameters, d_assignment,
+    return detail::run_aurora_prover<FieldT>(constraint_system, primary_input, auxiliary_input, parameters, d_assignment, hash,
                                              [](bcs_prover<FieldT> &IOP) { return IOP.get_transcript_bytes(); });
 }
 

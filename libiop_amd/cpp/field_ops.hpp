@@ -28,7 +28,7 @@ struct prime_field_ops : vector_ops {
     decltype(&iopx_fp3_from_uint) from_uint; decltype(&iopx_fp3_host_add) host_add; decltype(&iopx_fp3_host_sub) host_sub; decltype(&iopx_fp3_host_pow) host_pow;
     decltype(&iopx_fp3_modulus) modulus; decltype(&iopx_fp3_subgroup_generator) subgroup_generator; decltype(&iopx_fp3_multiplicative_generator) multiplicative_generator;
     decltype(&iopx_mul_fft_fp3) mul_fft_host; decltype(&iopx_mul_ifft_fp3) mul_ifft_host; decltype(&iopx_fri_fold_mul_fp3) fri_fold_mul_host;
-    decltype(&iopx_mul_fft_fp3_dev) mul_fft; decltype(&iopx_mul_fft_fp3_windows_dev) mul_fft_windows /* edwards Fr only */; decltype(&iopx_mul_ifft_fp3_dev) mul_ifft;
+    decltype(&iopx_mul_fft_fp3_dev) mul_fft; decltype(&iopx_mul_fft_fp3_windows_dev) mul_fft_windows; decltype(&iopx_mul_ifft_fp3_dev) mul_ifft;
     decltype(&iopx_mul_ifft_known_degree_fp3_dev) mul_ifft_known_degree; decltype(&iopx_fri_fold_mul_fp3_dev) fri_fold_mul;
     decltype(&iopx_ldt_combine_fp3_dev) ldt_combine; decltype(&iopx_rowcheck_fp3_dev) rowcheck; decltype(&iopx_fz_fp3_dev) fz; decltype(&iopx_sumcheck_g_fp3_dev) sumcheck_g;
     decltype(&iopx_poly_div_vanishing_fp3_dev) poly_div_vanishing; decltype(&iopx_domain_offsets_fp3_dev) domain_offsets; decltype(&iopx_vanishing_evals_fp3_dev) vanishing_evals;
@@ -64,7 +64,7 @@ inline constexpr prime_field_ops alt_bn128_Fr = {
     iopx_bn128_from_uint, iopx_bn128_host_add, iopx_bn128_host_sub, iopx_bn128_host_pow,
     iopx_bn128_modulus, iopx_bn128_subgroup_generator, iopx_bn128_multiplicative_generator,
     iopx_mul_fft_bn128, iopx_mul_ifft_bn128, iopx_fri_fold_mul_bn128,
-    iopx_mul_fft_bn128_dev, nullptr, iopx_mul_ifft_bn128_dev,
+    iopx_mul_fft_bn128_dev, iopx_mul_fft_bn128_windows_dev, iopx_mul_ifft_bn128_dev,
     iopx_mul_ifft_known_degree_bn128_dev, iopx_fri_fold_mul_bn128_dev,
     iopx_ldt_combine_bn128_dev, iopx_rowcheck_bn128_dev, iopx_fz_bn128_dev, iopx_sumcheck_g_bn128_dev,
     iopx_poly_div_vanishing_bn128_dev, iopx_domain_offsets_bn128_dev, iopx_vanishing_evals_bn128_dev,

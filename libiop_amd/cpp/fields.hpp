@@ -35,6 +35,7 @@ struct alt_bn128_Fr_element {
     explicit alt_bn128_Fr_element(uint64_t v) { check(ops::alt_bn128_Fr.from_uint(v, w)); }
     bool operator==(const alt_bn128_Fr_element &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
     bool operator!=(const alt_bn128_Fr_element &o) const { return !(*this == o); }
+    alt_bn128_Fr_element operator+(const alt_bn128_Fr_element &o) const { alt_bn128_Fr_element r; check(ops::alt_bn128_Fr.host_add(w, o.w, r.w)); return r; }
 };
 template<> struct field_kind<alt_bn128_Fr_element> { static const field_subset_type type = multiplicative_coset_type; };
 

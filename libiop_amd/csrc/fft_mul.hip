@@ -350,6 +350,9 @@ __device__ __forceinline__ void bn_mfft_step(uint64_t *s, int E, const MfParams 
     }
 }
 
+// WIN: as for k_mfft_pass, the last pass of a transform that also writes windows of its output — a separate instantiation, so the passes without
+// windows keep their registers.  A window takes the four canonical words the pass stores (after scaling, if any), not a second conversion.
+template<bool WIN>
 __global__ void __launch_bounds__(256) k_bn_mfft_pass(MfParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
@@ -386,6 +389,23 @@ __global__ void __launch_bounds__(256) k_bn_mfft_pass(MfParams p)
     for (int li = tid; li < E; li += nt) {
         const size_t gi = base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask);
         const bn9 v = blds_get(s, E, li);
+        if (WIN) {                                      // only ever the last pass (p.final)
+            uint64_t q[4];
+            if (p.scale == 1) bn9_store_canonical(q, bn9_mul(v, bnw_load(p.sc_hi, 0)));
+            else if (p.scale == 2) bn9_store_canonical(q, bn9_mul(v, bn9_mul(bnw_load(p.sc_hi, gi >> 12), bnw_load(p.sc_lo, gi & 4095))));
+            else bn9_store_canonical(q, bn9_mul(v, bn9_const(BN9_C261)));
+            uint64_t *d = p.dst + 4 * gi;
+            d[0] = q[0]; d[1] = q[1]; d[2] = q[2]; d[3] = q[3];
+            if (p.win0_dst && (gi & ((((size_t)1) << p.win0_log_stride) - 1)) == p.win0_first) {
+                uint64_t *w = p.win0_dst + 4 * (gi >> p.win0_log_stride);
+                w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; w[3] = q[3];
+            }
+            if (p.win1_dst && (gi & ((((size_t)1) << p.win1_log_stride) - 1)) == p.win1_first) {
+                uint64_t *w = p.win1_dst + 4 * (gi >> p.win1_log_stride);
+                w[0] = q[0]; w[1] = q[1]; w[2] = q[2]; w[3] = q[3];
+            }
+            continue;
+        }
         if (p.scale == 1) bnw_store_product(p.dst, gi, bn9_mul(v, bnw_load(p.sc_hi, 0)));
         else if (p.scale == 2) bnw_store_product(p.dst, gi, bn9_mul(v, bn9_mul(bnw_load(p.sc_hi, gi >> 12), bnw_load(p.sc_lo, gi & 4095))));
         else if (p.final) bnw_store(p.dst, gi, v);
@@ -445,7 +465,7 @@ struct FpArm : FpField {
     IOPX_MUL_KERNEL(scale_pow, k_fp_scale_pow)
     IOPX_MUL_KERNEL(gather_stride, k_fp_gather_stride)
     IOPX_MUL_KERNEL(fold2, k_fri_fold2_mul)
-    static constexpr const char *mfft_pass_label = "k_mfft_pass";
+    static constexpr const char *mfft_pass_label = "k_mfft_pass", *mfft_pass_win_label = "k_mfft_pass";
     static void (*mfft_pass(bool win))(MfParams) { return win ? k_mfft_pass<true> : k_mfft_pass<false>; }
     static constexpr void (*fold_fused[3])(MfoldParams) = { k_fri_fold_fused_mul<1>, k_fri_fold_fused_mul<2>, k_fri_fold_fused_mul<3> };
     static constexpr const char *fold_fused_label[3] = { "k_fri_fold_fused_mul_eta1", "k_fri_fold_fused_mul_eta2", "k_fri_fold_fused_mul_eta3" };
@@ -458,8 +478,8 @@ struct BnArm : BnField {
     IOPX_MUL_KERNEL(scale_pow, k_bn_scale_pow)
     IOPX_MUL_KERNEL(gather_stride, k_bn_gather_stride)
     IOPX_MUL_KERNEL(fold2, k_bn_fri_fold2)
-    static constexpr const char *mfft_pass_label = "k_bn_mfft_pass";
-    static void (*mfft_pass(bool))(MfParams) { return k_bn_mfft_pass; }     // no windowed variant
+    static constexpr const char *mfft_pass_label = "k_bn_mfft_pass", *mfft_pass_win_label = "k_bn_mfft_pass_win";     // the windowed last pass has a profile row of its own
+    static void (*mfft_pass(bool win))(MfParams) { return win ? k_bn_mfft_pass<true> : k_bn_mfft_pass<false>; }
     static constexpr void (*fold_fused[3])(MfoldParams) = { k_bn_fri_fold_fused<1>, k_bn_fri_fold_fused<2>, k_bn_fri_fold_fused<3> };
     static constexpr const char *fold_fused_label[3] = { "k_bn_fri_fold_fused_eta1", "k_bn_fri_fold_fused_eta2", "k_bn_fri_fold_fused_eta3" };
 };
@@ -655,13 +675,11 @@ int build_two_level(const hbn &base, const hbn &init, int logc, TmpBuf &hi, TmpB
 // runs the radix-2 levels on index bits [logrho, logn) (first pass gathers src bit-reversed), natural-order dst
 struct MfWindows { int num = 0; uint64_t *dst[2] = { nullptr, nullptr }; uint32_t first[2] = { 0, 0 }; int log_stride[2] = { 0, 0 }; };
 
-template<class Arm>
-static int run_mfft(const uint64_t *cache, const uint64_t *src, size_t n_src, uint64_t *dst, int logn, int logrho,
-                    int scale, const uint64_t *sc_hi, const uint64_t *sc_lo, const MfWindows *windows = nullptr)
+// the tiles and butterfly bits of each pass over index bits [logrho, logn)
+struct MfPass { int c, h, A, b_lo, b_hi; };
+static std::vector<MfPass> mfft_passes(int logn, int logrho)
 {
-    static_assert((Arm::BYTES << MF_TILE_BITS) <= 64 * 1024, "a tile fits the default LDS allocation");
-    struct Pass { int c, h, A, b_lo, b_hi; };
-    std::vector<Pass> passes;
+    std::vector<MfPass> passes;
     int b = logrho;
     if (logn <= MF_TILE_BITS) {
         passes.push_back({0, 0, logn, b, logn - 1});
@@ -679,8 +697,17 @@ static int run_mfft(const uint64_t *cache, const uint64_t *src, size_t n_src, ui
         b += A;
     }
     if (passes.empty()) passes.push_back({0, 0, logn < MF_TILE_BITS ? logn : MF_TILE_BITS, 1, 0});     // replication only
+    return passes;
+}
+
+template<class Arm>
+static int run_mfft(const uint64_t *cache, const uint64_t *src, size_t n_src, uint64_t *dst, int logn, int logrho,
+                    int scale, const uint64_t *sc_hi, const uint64_t *sc_lo, const MfWindows *windows = nullptr)
+{
+    static_assert((Arm::BYTES << MF_TILE_BITS) <= 64 * 1024, "a tile fits the default LDS allocation");
+    const std::vector<MfPass> passes = mfft_passes(logn, logrho);
     for (size_t i = 0; i < passes.size(); ++i) {
-        const Pass &ps = passes[i];
+        const MfPass &ps = passes[i];
         MfParams p;
         memset(&p, 0, sizeof(p));
         p.src = i == 0 ? src : dst;
@@ -700,7 +727,7 @@ static int run_mfft(const uint64_t *cache, const uint64_t *src, size_t n_src, ui
         const size_t blocks = (size_t)1 << (logn - tbits);
         const int threads = (1 << tbits) >= 512 ? (1 << tbits) / 8 : 64;          // one radix-8 group per lane and step
         // algorithmic bytes: the pass reads and writes the 2^logn-element vector once; products: one per radix-2 butterfly of its levels
-        { ProfScope ps_(Arm::mfft_pass_label, (2 * Arm::BYTES) << logn, (((size_t)1 << logn) >> 1) * (size_t)(ps.b_hi >= ps.b_lo ? ps.b_hi - ps.b_lo + 1 : 0));
+        { ProfScope ps_(p.win0_dst ? Arm::mfft_pass_win_label : Arm::mfft_pass_label, (2 * Arm::BYTES) << logn, (((size_t)1 << logn) >> 1) * (size_t)(ps.b_hi >= ps.b_lo ? ps.b_hi - ps.b_lo + 1 : 0));
           hipLaunchKernelGGL(Arm::mfft_pass(p.win0_dst != nullptr), dim3((unsigned)blocks), dim3(threads), lds, stream(), p); }
     }
     IOPX_HIP(hipGetLastError());
@@ -989,6 +1016,15 @@ int iopx_mul_fft_bn128_dev(const uint64_t *d_coeffs, size_t n_coeffs, size_t log
 int iopx_mul_fft_fp3_windows_dev(const uint64_t *d_coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out,
                                  size_t num_windows, const size_t *window_first, const size_t *window_log_stride, uint64_t *const *d_windows)
 { return mul_fft_dev<FpArm>(d_coeffs, n_coeffs, log_n, gen, shift, d_out, num_windows, window_first, window_log_stride, d_windows); }
+int iopx_mul_fft_pass_count(size_t log_n, size_t n_coeffs, size_t *num_passes)
+{
+    if (!num_passes || log_n > 40 || n_coeffs == 0 || n_coeffs > ((size_t)1 << log_n)) return fail(IOPX_ERR_INVALID_ARGUMENT, "iopx_mul_fft_pass_count: 1 <= n_coeffs <= 2^log_n, log_n <= 40");
+    *num_passes = mfft_passes((int)log_n, (int)log_n - (int)ceil_log2(n_coeffs)).size();
+    return IOPX_OK;
+}
+int iopx_mul_fft_bn128_windows_dev(const uint64_t *d_coeffs, size_t n_coeffs, size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out,
+                                   size_t num_windows, const size_t *window_first, const size_t *window_log_stride, uint64_t *const *d_windows)
+{ return mul_fft_dev<BnArm>(d_coeffs, n_coeffs, log_n, gen, shift, d_out, num_windows, window_first, window_log_stride, d_windows); }
 
 int iopx_mul_ifft_fp3_dev(const uint64_t *d_evals, size_t log_n, const uint64_t *gen, const uint64_t *shift, uint64_t *d_out)
 { return mul_ifft_dev<FpArm>(d_evals, log_n, gen, shift, d_out); }

@@ -1,7 +1,7 @@
 // The Aurora, Fractal and FRI-only provers behind the C ABI: iopx_aurora_* / iopx_fractal_* / iopx_fri_snark_* (include/libiop_amd.h).
 //
 // The orchestration is the C++ surface of libiop_amd/cpp/aurora.hpp — aurora_snark_prover<FieldT>(cs, primary, auxiliary, params),
-// the signature of libiop/snark/aurora_snark.tcc:120-146 — instantiated for the two accelerated fields and wrapped in plain C types, so
+// the signature of libiop/snark/aurora_snark.tcc:120-146 — instantiated for the three accelerated fields and wrapped in plain C types, so
 // that a caller without a C++ toolchain (the ctypes binding, bench.py) reaches the native prover too.  Host-only code: no kernels here.
 #include <cstring>
 #include <memory>
@@ -31,7 +31,7 @@ void require_supported_security(size_t security_parameter)
 struct InstanceBase {
     virtual ~InstanceBase() {}
     // comm: the communicator the codeword-domain vectors are distributed over (libiop_amd/cpp/dist.hpp); null = one GPU
-    virtual std::string prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) = 0;
+    virtual std::string prove(iopx_comm *comm, int bcs_hash_type, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) = 0;
     virtual size_t num_constraints() const = 0;
     virtual std::vector<std::string> fractal_index(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) = 0;
     virtual std::string fractal_prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) = 0;
@@ -57,7 +57,18 @@ struct Instance : InstanceBase {
     iopx_comm *index_comm = nullptr;        // the index holds this rank's part of the twelve index oracles: it belongs to one communicator
 
     size_t num_constraints() const override { return cs.num_constraints(); }
+    static constexpr bool bn128 = sizeof(F) == 32;                // alt_bn128 Fr: Aurora only, on one GPU
     std::vector<std::string> fractal_index(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
+    {
+        if constexpr (bn128) throw std::invalid_argument("iopx_fractal_index: there is no Fractal prover over alt_bn128 Fr");
+        else return fractal_index_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
+    }
+    std::string fractal_prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
+    {
+        if constexpr (bn128) throw std::invalid_argument("iopx_fractal_prove: there is no Fractal prover over alt_bn128 Fr");
+        else return fractal_prove_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
+    }
+    std::vector<std::string> fractal_index_(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter)
     {
         require_supported_security(security_parameter);
         const dist::scope bound(comm);
@@ -70,7 +81,7 @@ struct Instance : InstanceBase {
         index_params[0] = security_parameter; index_params[1] = RS_extra_dimensions; index_params[2] = FRI_localization_parameter;
         return made.second.index_MT_roots_;
     }
-    std::string fractal_prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
+    std::string fractal_prove_(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter)
     {
         require_supported_security(security_parameter);
         if (index && index_comm != comm) throw std::logic_error("iopx_fractal_prove: the index was built for another communicator");
@@ -80,12 +91,21 @@ struct Instance : InstanceBase {
         const fractal_snark_parameters<F> params(cs, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
         return fractal_snark_prover_serialized<F>(*index, cs, primary, auxiliary, params, &d_assignment);
     }
-    std::string prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
+    std::string prove(iopx_comm *comm, int bcs_hash_type, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
+        if (bcs_hash_type != IOPX_HASH_BLAKE2B && bcs_hash_type != IOPX_HASH_POSEIDON_STARKWARE && bcs_hash_type != IOPX_HASH_POSEIDON_HIGH_ALPHA)
+            throw std::invalid_argument("bcs_hash_type unknown");
+        if (bcs_hash_type != IOPX_HASH_BLAKE2B && !bn128) throw std::invalid_argument("Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
+        if (bn128 && comm) throw std::invalid_argument("alt_bn128 Fr has no distributed prover: pass no communicator");
         require_supported_security(security_parameter);
         const dist::scope bound(comm);
         const aurora_snark_parameters<F> params(cs.num_constraints(), cs.num_variables(), cs.num_inputs(), security_parameter, RS_extra_dimensions,
                                                 FRI_localization_parameter);
+        if (bn128 && params.codeword_domain_dim_ > 28)
+            throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": alt_bn128 Fr has subgroups of order up to 2^28");
+        if constexpr (bn128) {
+            if (bcs_hash_type != IOPX_HASH_BLAKE2B) return aurora_snark_prover_serialized<F, poseidon>(cs, primary, auxiliary, params, &d_assignment, poseidon(bcs_hash_type));
+        }
         return aurora_snark_prover_serialized<F>(cs, primary, auxiliary, params, &d_assignment);
     }
 };
@@ -110,13 +130,14 @@ InstanceBase *make_from_csr(const iopx_r1cs *r, const uint64_t *assignment)
         const size_t nnz = (size_t)r->row_ptr[q][r->num_constraints];
         M[q]->col.assign(r->col[q], r->col[q] + nnz);
         M[q]->coeff.resize(nnz);
-        if (nnz) std::memcpy((void *)M[q]->coeff.data(), r->coeff[q], nnz * 24);
+        if (nnz) std::memcpy((void *)M[q]->coeff.data(), r->coeff[q], nnz * sizeof(F));
         for (uint32_t c : M[q]->col) if (c > r->num_variables) throw std::invalid_argument("iopx_aurora_instance_create: column index exceeds the number of variables");
     }
     inst->primary.resize(r->num_inputs);
     inst->auxiliary.resize(r->num_variables - r->num_inputs);
-    if (r->num_inputs) std::memcpy((void *)inst->primary.data(), assignment, r->num_inputs * 24);
-    if (r->num_variables > r->num_inputs) std::memcpy((void *)inst->auxiliary.data(), assignment + 3 * r->num_inputs, (r->num_variables - r->num_inputs) * 24);
+    if (r->num_inputs) std::memcpy((void *)inst->primary.data(), assignment, r->num_inputs * sizeof(F));
+    if (r->num_variables > r->num_inputs)
+        std::memcpy((void *)inst->auxiliary.data(), assignment + sizeof(F) / 8 * r->num_inputs, (r->num_variables - r->num_inputs) * sizeof(F));
     inst->finish();
     return holder.release();
 }
@@ -206,6 +227,7 @@ int iopx_aurora_instance_create(const iopx_r1cs *r1cs, const uint64_t *assignmen
     return guarded([&] {
         if (field == IOPX_FIELD_GF192) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<gf192_element>(r1cs, assignment));
         else if (field == IOPX_FIELD_EDWARDS_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<edwards_Fr_element>(r1cs, assignment));
+        else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<alt_bn128_Fr_element>(r1cs, assignment));
         else throw std::invalid_argument("unknown field");
     });
 }
@@ -218,12 +240,13 @@ int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_
     return guarded([&] {
         if (field == IOPX_FIELD_GF192) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<gf192_element>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_EDWARDS_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<edwards_Fr_element>(num_constraints, num_inputs, num_variables, seed));
+        else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<alt_bn128_Fr_element>(num_constraints, num_inputs, num_variables, seed));
         else throw std::invalid_argument("unknown field");
     });
 }
 
 static int prove_entry(iopx_aurora_instance *instance, iopx_comm *comm, bool fractal, size_t security_parameter, size_t RS_extra_dimensions,
-                       size_t FRI_localization_parameter, uint8_t **transcript, size_t *transcript_bytes)
+                       size_t FRI_localization_parameter, uint8_t **transcript, size_t *transcript_bytes, int bcs_hash_type = IOPX_HASH_BLAKE2B)
 {
     int rc = iopx::ensure_device();
     if (rc != IOPX_OK) return rc;
@@ -231,7 +254,7 @@ static int prove_entry(iopx_aurora_instance *instance, iopx_comm *comm, bool fra
     return guarded([&] {
         InstanceBase *inst = reinterpret_cast<InstanceBase *>(instance);
         const std::string t = fractal ? inst->fractal_prove(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter)
-                                      : inst->prove(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
+                                      : inst->prove(comm, bcs_hash_type, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
         uint8_t *buf = static_cast<uint8_t *>(std::malloc(t.size() ? t.size() : 1));
         if (!buf) throw std::bad_alloc();
         std::memcpy(buf, t.data(), t.size());
@@ -274,6 +297,12 @@ int iopx_aurora_prove(iopx_aurora_instance *instance, size_t security_parameter,
                       uint8_t **transcript, size_t *transcript_bytes)
 {
     return prove_entry(instance, nullptr, false, security_parameter, RS_extra_dimensions, FRI_localization_parameter, transcript, transcript_bytes);
+}
+
+int iopx_aurora_prove_hashed(iopx_aurora_instance *instance, int bcs_hash_type, size_t security_parameter, size_t RS_extra_dimensions,
+                             size_t FRI_localization_parameter, uint8_t **transcript, size_t *transcript_bytes)
+{
+    return prove_entry(instance, nullptr, false, security_parameter, RS_extra_dimensions, FRI_localization_parameter, transcript, transcript_bytes, bcs_hash_type);
 }
 
 int iopx_aurora_prove_dist(iopx_aurora_instance *instance, iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions,

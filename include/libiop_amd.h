@@ -72,7 +72,8 @@ int         iopx_side_stream_join(void);
 int         iopx_memcpy_d2h_deferrable(void *dst_host, const void *src_dev, size_t bytes);
 /* Transcript extraction reads back two small results per Merkle tree (iopx_query_responses_dev, iopx_merkle_membership_proof_dev).  Between
  * _begin and _end those calls only queue their read-backs; _end drains the stream once and fills every host buffer handed to them in
- * between (the buffers must stay alive until then).  Everything else behaves as usual inside the window. */
+ * between (the buffers must stay alive until then).  Everything else behaves as usual inside the window.  A read-back may be queued inside a
+ * side-stream section; _end itself joins the side stream and is refused (IOPX_ERR_LOGIC, the window stays open) inside one. */
 int         iopx_defer_downloads_begin(void);
 int         iopx_defer_downloads_end(void);
 /* Drop every cached per-domain plan (twist-power tables, twiddle tables). */

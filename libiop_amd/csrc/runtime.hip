@@ -440,9 +440,12 @@ int defer_downloads_end()
 {
     std::lock_guard<std::mutex> lk(g_stage_mu);
     if (!g_defer_on) return fail(IOPX_ERR_LOGIC, "iopx_defer_downloads_end without begin");
+    // inside a side-stream section the join below is impossible, and the arena's copy on the main stream would overtake the pieces queued on the
+    // side stream: refused, with the window left open (end the section, then call again)
+    if (side_stream_current() >= 0) return fail(IOPX_ERR_LOGIC, "iopx_defer_downloads_end inside a side-stream section");
     g_defer_on = false;
     // a deferrable read-back may have been queued inside a side-stream section: the main stream waits for the side streams, draining it covers both
-    for (int k = 0; k < IOPX_SIDE_STREAMS; ++k) if (side_stream_current() < 0) (void)side_stream_join(k);
+    for (int k = 0; k < IOPX_SIDE_STREAMS; ++k) (void)side_stream_join(k);
     hipError_t e = hipSuccess;
     if (g_defer_used) e = copy_d2h(g_defer_host, g_defer_dev, g_defer_used, g_stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g_stream);

@@ -1,5 +1,22 @@
 // TEST INFRASTRUCTURE ONLY — see fakehip/hip/hip_runtime.h
+//
+// Besides running kernels one workgroup at a time, this file models HIP's streams and events so that a missing ordering edge between two
+// streams shows as a deterministic difference in bytes ("Emulated streams").
+//   eager (default)   every call acts at once: one implicit stream, the behaviour the suite has always had
+//   all late          every stream is a queue of operations (launches, asynchronous copies and fills, event records, event waits) that runs
+//                     only where the host synchronises: hipStreamSynchronize (that stream, and what its waits need, up to the awaited records
+//                     and no further), hipDeviceSynchronize / hipFree / hipHostFree / hipSetDevice / unload (everything)
+//   one stream late   the stream with the given creation index is such a queue; the others run each operation when it is enqueued (pulling
+//                     the late one up to a record they wait for)
+// Together: for any two streams, both extreme legal interleavings.  The legacy stream 0 (and any handle this file did not create) is a queue
+// of its own; it does not synchronise with the others, which is right for hipStreamNonBlocking streams, the only kind the product creates.
 #include <hip/hip_runtime.h>
+#include <atomic>
+#include <deque>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <vector>
 
 thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
 namespace iopx { alignas(16) uint64_t iopx_smem[160 * 1024 / 8]; }
@@ -22,3 +39,391 @@ void emu_launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<voi
                 body();
             }
 }
+
+namespace {
+
+enum { SCHED_EAGER = 0, SCHED_ALL_LATE = 1, SCHED_ONE_LATE = 2 };
+const int QUERY_BOUND = 64;             // not-ready answers one record gives before a query executes its stream (a loop that polls must end)
+const unsigned char FRESH = 0xC7;       // what new device memory holds on a deferred schedule
+
+struct Stream;
+struct Marker { bool done = false; Stream *stream = nullptr; int queries = 0; };      // one hipEventRecord
+struct Op {
+    enum Kind { RUN, RECORD, WAIT } kind;
+    std::function<void()> fn;
+    std::shared_ptr<Marker> m;
+};
+struct Stream { std::deque<Op> q; int index = -1; };           // index: creation order among live created streams; -1: a handle from outside (0 = legacy)
+struct Event { std::shared_ptr<Marker> last; };
+
+struct State {
+    std::recursive_mutex mu;
+    std::map<hipStream_t, Stream *> streams;
+    std::map<uintptr_t, size_t> pinned;                         // hipHostMalloc blocks: base -> bytes
+    int late_index = -1;
+    int drop_nth = -1, drop_stream = -1, waits_seen = 0;        // fault injection: see iopx_emu_drop_waits
+    bool query_complete = false;
+    int depth = 0;
+};
+State &st() { static State *s = new State; return *s; }        // never destroyed: the unload hook below still needs it
+std::atomic<int> g_sched{ SCHED_EAGER };
+
+Stream *lookup(hipStream_t h)
+{
+    State &S = st();
+    auto it = S.streams.find(h);
+    if (it == S.streams.end()) it = S.streams.emplace(h, new Stream).first;
+    return it->second;
+}
+
+bool is_late(const Stream *s)
+{
+    const int sched = g_sched.load();
+    return sched == SCHED_ALL_LATE || (sched == SCHED_ONE_LATE && s->index == st().late_index);
+}
+
+void run_until(Stream *s, const Marker *m);
+
+void exec_front(Stream *s)
+{
+    Op op = std::move(s->q.front());
+    s->q.pop_front();
+    switch (op.kind) {
+    case Op::RUN: op.fn(); break;
+    case Op::RECORD: op.m->done = true; break;
+    case Op::WAIT:
+        if (!op.m->done) run_until(op.m->stream, op.m.get());
+        if (!op.m->done) { fprintf(stderr, "emu: a stream waits for an event record that can never execute\n"); abort(); }
+        break;
+    }
+}
+
+// m = null: to the stream's end
+void run_until(Stream *s, const Marker *m)
+{
+    State &S = st();
+    if (++S.depth > 256) { fprintf(stderr, "emu: streams wait for each other in a cycle\n"); abort(); }
+    while (!s->q.empty() && !(m && m->done)) exec_front(s);
+    --S.depth;
+}
+
+void drain_all()
+{
+    State &S = st();
+    for (bool again = true; again;) {
+        again = false;
+        for (auto &kv : S.streams) if (!kv.second->q.empty()) { run_until(kv.second, nullptr); again = true; }
+    }
+}
+
+void enqueue(Stream *s, Op op)
+{
+    s->q.push_back(std::move(op));
+    if (!is_late(s)) run_until(s, nullptr);
+}
+
+bool is_pinned(const void *p)
+{
+    State &S = st();
+    auto it = S.pinned.upper_bound((uintptr_t)p);
+    if (it == S.pinned.begin()) return false;
+    --it;
+    return (uintptr_t)p < it->first + it->second;
+}
+
+typedef std::lock_guard<std::recursive_mutex> Lock;
+
+struct AtUnload { ~AtUnload() { Lock lk(st().mu); drain_all(); } } g_at_unload;
+
+} // namespace
+
+void emu_enqueue_launch(hipStream_t stream, dim3 grid, dim3 block, size_t lds_bytes, std::function<void()> body)
+{
+    if (g_sched.load() == SCHED_EAGER) { emu_launch(grid, block, lds_bytes, body); return; }
+    Lock lk(st().mu);
+    enqueue(lookup(stream), { Op::RUN, [grid, block, lds_bytes, body = std::move(body)]() { emu_launch(grid, block, lds_bytes, body); }, nullptr });
+}
+
+hipError_t hipSetDevice(int) { Lock lk(st().mu); drain_all(); return hipSuccess; }
+hipError_t hipDeviceSynchronize() { Lock lk(st().mu); drain_all(); return hipSuccess; }
+
+hipError_t hipStreamCreateWithFlags(hipStream_t *out, unsigned)
+{
+    State &S = st();
+    Lock lk(S.mu);
+    Stream *s = new Stream;
+    for (s->index = 0;; ++s->index) {           // the lowest creation index no live stream holds
+        bool taken = false;
+        for (auto &kv : S.streams) taken = taken || kv.second->index == s->index;
+        if (!taken) break;
+    }
+    S.streams[(hipStream_t)s] = s;
+    *out = (hipStream_t)s;
+    return hipSuccess;
+}
+
+hipError_t hipStreamDestroy(hipStream_t h)
+{
+    State &S = st();
+    Lock lk(S.mu);
+    auto it = S.streams.find(h);
+    if (it == S.streams.end()) return hipSuccess;
+    run_until(it->second, nullptr);
+    delete it->second;
+    S.streams.erase(it);
+    return hipSuccess;
+}
+
+hipError_t hipStreamSynchronize(hipStream_t h)
+{
+    if (g_sched.load() == SCHED_EAGER) return hipSuccess;
+    Lock lk(st().mu);
+    run_until(lookup(h), nullptr);
+    return hipSuccess;
+}
+
+hipError_t hipMalloc(void **p, size_t n)
+{
+    *p = malloc(n ? n : 8);
+    if (!*p) return hipErrorUnknown;
+    if (g_sched.load() != SCHED_EAGER) memset(*p, FRESH, n ? n : 8);     // a read of never-written memory gives the same wrong bytes every run
+    return hipSuccess;
+}
+hipError_t hipFree(void *p) { { Lock lk(st().mu); drain_all(); } free(p); return hipSuccess; }
+hipError_t hipMallocAsync(void **p, size_t n, hipStream_t) { return hipMalloc(p, n); }
+hipError_t hipFreeAsync(void *p, hipStream_t) { return hipFree(p); }
+
+hipError_t hipHostMalloc(void **p, size_t n, unsigned)
+{
+    *p = malloc(n ? n : 8);
+    if (!*p) return hipErrorUnknown;
+    Lock lk(st().mu);
+    st().pinned[(uintptr_t)*p] = n ? n : 8;
+    return hipSuccess;
+}
+hipError_t hipHostFree(void *p)
+{
+    { Lock lk(st().mu); drain_all(); st().pinned.erase((uintptr_t)p); }
+    free(p);
+    return hipSuccess;
+}
+
+// As the real runtime: a copy to or from pinned host memory is queued and touches that memory when it executes; a pageable source is
+// staged at the call; a pageable destination makes the call wait for the stream and copy then.
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind kind, hipStream_t stream)
+{
+    if (g_sched.load() == SCHED_EAGER) { memmove(d, s, n); return hipSuccess; }
+    Lock lk(st().mu);
+    Stream *q = lookup(stream);
+    if (kind == hipMemcpyDeviceToDevice || (kind == hipMemcpyHostToDevice && is_pinned(s)) || (kind == hipMemcpyDeviceToHost && is_pinned(d))) {
+        enqueue(q, { Op::RUN, [d, s, n]() { memmove(d, s, n); }, nullptr });
+    } else if (kind == hipMemcpyHostToDevice) {
+        auto staged = std::make_shared<std::vector<unsigned char>>((const unsigned char *)s, (const unsigned char *)s + n);
+        enqueue(q, { Op::RUN, [d, staged, n]() { memcpy(d, staged->data(), n); }, nullptr });
+    } else {
+        run_until(q, nullptr);
+        memmove(d, s, n);
+    }
+    return hipSuccess;
+}
+
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t stream)
+{
+    if (g_sched.load() == SCHED_EAGER) { memset(d, v, n); return hipSuccess; }
+    Lock lk(st().mu);
+    enqueue(lookup(stream), { Op::RUN, [d, v, n]() { memset(d, v, n); }, nullptr });
+    return hipSuccess;
+}
+
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = (hipEvent_t) new Event; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
+hipError_t hipEventDestroy(hipEvent_t e) { Lock lk(st().mu); delete (Event *)e; return hipSuccess; }      // queued records and waits hold their Marker
+
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t stream)
+{
+    if (!e) return hipErrorUnknown;
+    Lock lk(st().mu);
+    Stream *s = lookup(stream);
+    auto m = std::make_shared<Marker>();
+    m->stream = s;
+    ((Event *)e)->last = m;
+    enqueue(s, { Op::RECORD, nullptr, m });
+    return hipSuccess;
+}
+
+// waits for the record that is the event's most recent one NOW; an event never recorded holds nothing back
+hipError_t hipStreamWaitEvent(hipStream_t stream, hipEvent_t e, unsigned)
+{
+    if (!e) return hipErrorUnknown;
+    State &S = st();
+    Lock lk(S.mu);
+    Stream *s = lookup(stream);
+    if (S.drop_nth >= 0 && (S.drop_stream < 0 || S.drop_stream == s->index)) {
+        ++S.waits_seen;
+        if (S.drop_nth == 0 || S.drop_nth == S.waits_seen) return hipSuccess;       // injected fault: the edge is lost
+    }
+    std::shared_ptr<Marker> m = ((Event *)e)->last;
+    if (m && !m->done) enqueue(s, { Op::WAIT, nullptr, m });
+    return hipSuccess;
+}
+
+static hipError_t marker_ready(const std::shared_ptr<Marker> &m, bool poll)
+{
+    if (!m || m->done || st().query_complete) return hipSuccess;
+    if (poll && ++m->queries > QUERY_BOUND) { run_until(m->stream, m.get()); return hipSuccess; }
+    return hipErrorNotReady;            // a query makes no progress by itself
+}
+
+hipError_t hipEventQuery(hipEvent_t e)
+{
+    if (!e) return hipErrorUnknown;
+    Lock lk(st().mu);
+    return marker_ready(((Event *)e)->last, true);
+}
+
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b)
+{
+    *ms = 0.f;
+    if (!a || !b) return hipErrorUnknown;
+    Lock lk(st().mu);
+    const hipError_t ea = marker_ready(((Event *)a)->last, false), eb = marker_ready(((Event *)b)->last, false);
+    return ea != hipSuccess ? ea : eb;
+}
+
+// ---- test-only entries -------------------------------------------------------------------------------------------------------------
+static void k_emu_set(uint64_t *p, uint64_t v) { if (blockIdx.x == 0) *p = v; }
+static void k_emu_copy(uint64_t *d, const uint64_t *s) { if (blockIdx.x == 0) *d = *s; }
+
+extern "C" {
+
+// schedule: 0 eager, 1 all streams late, 2 the stream with creation index `late_stream` late.  Drains everything first.
+int iopx_emu_set_schedule(int schedule, int late_stream)
+{
+    if (schedule < SCHED_EAGER || schedule > SCHED_ONE_LATE) return -1;
+    Lock lk(st().mu);
+    drain_all();
+    st().late_index = late_stream;
+    g_sched.store(schedule);
+    return 0;
+}
+
+// created streams alive (the library's own is the first, its side stream the second)
+int iopx_emu_live_streams(void)
+{
+    Lock lk(st().mu);
+    int n = 0;
+    for (auto &kv : st().streams) n += kv.second->index >= 0;
+    return n;
+}
+
+// Fault injection.  nth < 0: off; 0: every hipStreamWaitEvent from now on is a no-op; n > 0: the n-th one from now on.  on_stream >= 0: only
+// waits enqueued on the stream with that creation index are counted and dropped.
+void iopx_emu_drop_waits(int nth, int on_stream)
+{
+    Lock lk(st().mu);
+    st().drop_nth = nth; st().drop_stream = on_stream; st().waits_seen = 0;
+}
+
+// Fault injection: hipEventQuery and hipEventElapsedTime report completion whatever the record's state
+void iopx_emu_force_query_complete(int on)
+{
+    Lock lk(st().mu);
+    st().query_complete = on != 0;
+}
+
+// The scheduler's self-tests, written against the fake API alone.  Each returns what it observed, packed in decimal digits; the expected
+// value per schedule is in tests/stream_schedule_cases.py.  Device memory is host memory here, so a test may look at it without a copy.
+long iopx_emu_selftest(int which)
+{
+    hipStream_t A = nullptr, B = nullptr;
+    hipEvent_t e = nullptr;
+    uint64_t *x = nullptr, *y = nullptr, *z = nullptr, *pin = nullptr, *spare = nullptr;
+    uint64_t *page = (uint64_t *)malloc(8);
+    (void)hipStreamCreateWithFlags(&A, hipStreamNonBlocking);
+    (void)hipStreamCreateWithFlags(&B, hipStreamNonBlocking);
+    (void)hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    (void)hipMalloc(&x, 8); (void)hipMalloc(&y, 8); (void)hipMalloc(&z, 8); (void)hipMalloc(&spare, 8);
+    (void)hipHostMalloc((void **)&pin, 8, 0);
+    hipLaunchKernelGGL(k_emu_set, dim3(2), dim3(64), 0, A, x, 1);
+    hipLaunchKernelGGL(k_emu_set, dim3(2), dim3(64), 0, A, y, 2);
+    hipLaunchKernelGGL(k_emu_set, dim3(2), dim3(64), 0, A, z, 3);
+    (void)hipStreamSynchronize(A);
+    long r = -1;
+    switch (which) {
+    case 0: case 1: {           // A writes x, B reads it into y: without (0) and with (1) an event between them.  Returns y.
+        uint64_t v = 5;
+        hipLaunchKernelGGL(k_emu_set, dim3(2), dim3(64), 0, A, x, v);
+        v = 6;                  // the launch took its copy
+        if (which == 1) { (void)hipEventRecord(e, A); (void)hipStreamWaitEvent(B, e, 0); }
+        hipLaunchKernelGGL(k_emu_copy, dim3(1), dim3(64), 0, B, y, x);
+        (void)hipStreamSynchronize(B);
+        (void)hipStreamSynchronize(A);
+        r = (long)*y;
+        break;
+    }
+    case 2: {                   // a wait holds the record current at the call, and pulls the other stream up to it and no further.  Returns y * 100 + x.
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, A, x, 5);
+        (void)hipEventRecord(e, A);
+        (void)hipStreamWaitEvent(B, e, 0);
+        hipLaunchKernelGGL(k_emu_copy, dim3(1), dim3(64), 0, B, y, x);
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, A, x, 7);
+        (void)hipEventRecord(e, A);
+        (void)hipStreamSynchronize(B);
+        r = (long)*y * 100 + (long)*x;
+        break;
+    }
+    case 3: {                   // hipStreamSynchronize(B) leaves A's work pending.  Returns x before A is synchronised * 10000 + z * 100 + x after.
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, A, x, 5);
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, B, z, 9);
+        (void)hipStreamSynchronize(B);
+        r = (long)*x * 10000 + (long)*z * 100;
+        (void)hipStreamSynchronize(A);
+        r += (long)*x;
+        break;
+    }
+    case 4: {                   // host memory in asynchronous copies.  Returns (pageable read-back, seen at once) * 100 + (x from pinned) * 10 + (z from pageable).
+        *pin = 1; *page = 1;
+        (void)hipMemcpyAsync(x, pin, 8, hipMemcpyHostToDevice, A);
+        (void)hipMemcpyAsync(z, page, 8, hipMemcpyHostToDevice, A);
+        *pin = 2; *page = 2;
+        (void)hipStreamSynchronize(A);
+        r = (long)*x * 10 + (long)*z;
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, A, y, 5);
+        (void)hipMemcpyAsync(page, y, 8, hipMemcpyDeviceToHost, A);
+        r += (long)*page * 100;
+        break;
+    }
+    case 5: {                   // hipFree drains every stream.  Returns x * 10 + z right after the call.
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, A, x, 5);
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, B, z, 9);
+        (void)hipFree(spare);
+        spare = nullptr;
+        r = (long)*x * 10 + (long)*z;
+        break;
+    }
+    case 6: {                   // queries: not ready while the record is pending, no progress by a few of them, and a polling loop ends.
+        hipLaunchKernelGGL(k_emu_set, dim3(1), dim3(64), 0, A, x, 5);    // Returns (first answer not ready) * 1000000 + x after 3 queries * 100000 + polls needed * 100 + x at the end
+        (void)hipEventRecord(e, A);
+        const bool pending = hipEventQuery(e) == hipErrorNotReady;
+        (void)hipEventQuery(e); (void)hipEventQuery(e);
+        r = (pending ? 1000000 : 0) + (long)*x * 100000;
+        int polls = 0;
+        while (hipEventQuery(e) != hipSuccess && polls < 999) ++polls;
+        r += polls * 100 + (long)*x;
+        break;
+    }
+    default: break;
+    }
+    (void)hipStreamSynchronize(A);
+    (void)hipStreamSynchronize(B);
+    (void)hipEventDestroy(e);
+    (void)hipStreamDestroy(A);
+    (void)hipStreamDestroy(B);
+    (void)hipFree(x); (void)hipFree(y); (void)hipFree(z);
+    if (spare) (void)hipFree(spare);
+    (void)hipHostFree(pin);
+    free(page);
+    return r;
+}
+
+} // extern "C"

@@ -13,6 +13,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <tuple>
+#include <type_traits>
+#include <utility>
 
 #define __global__
 #define __device__
@@ -90,44 +93,59 @@ static inline unsigned long long __brevll(unsigned long long x)
 
 typedef int hipError_t;
 typedef void *hipStream_t;
-enum { hipSuccess = 0, hipErrorUnknown = 999 };
+enum { hipSuccess = 0, hipErrorNotReady = 600, hipErrorUnknown = 999 };
 enum hipMemcpyKind { hipMemcpyHostToHost, hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice, hipMemcpyDefault };
 enum { hipStreamNonBlocking = 1 };
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 
-static inline const char *hipGetErrorString(hipError_t) { return "emu"; }
+static inline const char *hipGetErrorString(hipError_t e) { return e == hipErrorNotReady ? "emu: not ready" : "emu"; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
 static inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
-static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDevice(int *d) { *d = 0; return hipSuccess; }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = (hipStream_t)(uintptr_t)1; return hipSuccess; }
-static inline hipError_t hipStreamDestroy(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipMalloc(void **p, size_t n) { *p = malloc(n ? n : 8); return *p ? hipSuccess : hipErrorUnknown; }
-template<typename T> static inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void **)p, n); }
-static inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
-static inline hipError_t hipMallocAsync(void **p, size_t n, hipStream_t) { return hipMalloc(p, n); }
-static inline hipError_t hipFreeAsync(void *p, hipStream_t) { free(p); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t) { memmove(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t) { memset(d, v, n); return hipSuccess; }
 static inline hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
+
+// Streams, events and memory live in emu_runtime.cpp.  On the default ("eager") schedule every call below acts at once, as a single
+// implicit stream would; on a deferred schedule (iopx_emu_set_schedule) each stream is a queue of operations that executes only where the
+// host synchronises, so that a missing ordering edge between two streams changes the bytes a test sees.
+hipError_t hipSetDevice(int);
+hipError_t hipDeviceSynchronize();
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned flags);
+hipError_t hipStreamDestroy(hipStream_t s);
+hipError_t hipStreamSynchronize(hipStream_t s);
+hipError_t hipMalloc(void **p, size_t n);
+template<typename T> static inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void **)p, n); }
+hipError_t hipFree(void *p);
+hipError_t hipMallocAsync(void **p, size_t n, hipStream_t s);
+hipError_t hipFreeAsync(void *p, hipStream_t s);
+hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind kind, hipStream_t stream);
+hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t stream);
 
 typedef void *hipEvent_t;
 enum { hipEventDisableTiming = 2 };
-static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { *p = malloc(n ? n : 8); return *p ? hipSuccess : hipErrorUnknown; }
-static inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
-static inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = nullptr; return hipSuccess; }
-static inline hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t *e) { *e = nullptr; return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
-static inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
+hipError_t hipHostMalloc(void **p, size_t n, unsigned flags);
+hipError_t hipHostFree(void *p);
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned flags);
+hipError_t hipEventQuery(hipEvent_t e);
+hipError_t hipEventCreate(hipEvent_t *e);
+hipError_t hipEventDestroy(hipEvent_t e);
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t s);
+hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags);
+hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b);
 
 // LDS: one static buffer, the size of a CU's LDS
 namespace iopx { extern uint64_t iopx_smem[]; }
+// runs every workgroup of the grid now, on the calling thread
 void emu_launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()> &body);
+// eager schedule: emu_launch at once; deferred: the closure joins the stream's queue and emu_launch runs it when the stream executes
+void emu_enqueue_launch(hipStream_t stream, dim3 grid, dim3 block, size_t lds_bytes, std::function<void()> body);
+
+// A launch copies its arguments when it is enqueued, converted to the kernel's parameter types as the real launch does: the caller's
+// variables may change or die before the kernel runs.
+template<typename... P, typename... A>
+static inline std::function<void()> emu_bind(void (*kernel)(P...), A &&...args)
+{
+    return [kernel, held = std::tuple<typename std::decay<P>::type...>(std::forward<A>(args)...)]() { std::apply(kernel, held); };
+}
 
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) \
-    emu_launch((grid), (block), (lds), [&]() { kernel(__VA_ARGS__); })
+    emu_enqueue_launch((hipStream_t)(stream), (grid), (block), (lds), emu_bind(kernel, ##__VA_ARGS__))

@@ -253,6 +253,38 @@ int iopx_fri_fold_add_gf192(const uint64_t *f_i, const uint64_t *basis, size_t m
 int iopx_fri_domains_gf192(const uint64_t *basis, size_t m, const uint64_t *shift, const size_t *localization, size_t num_reductions,
                            uint64_t *out_bases, uint64_t *out_shifts);
 
+/* ---- GF(2^64): additive FFT / IFFT, FRI fold, LDT combination ----------------------------------- */
+/* The same operators for FieldT = libff::gf64 (x^64 + x^4 + x^3 + x + 1): a field element is ONE little-endian uint64 word (8 bytes),
+ * libff::gf64's in-memory layout.  Every entry takes the arguments of its _gf192 twin above / below, with one word per element, and cites
+ * the same reference lines: additive_FFT / additive_IFFT fft.tcc:39-204, evaluate_next_f_i_over_entire_domain fri_aux.tcc:5-103,
+ * FRI_protocol::compute_domains fri_ldt.tcc:310-338, combined_LDT_virtual_oracle::evaluated_contents ldt_reducer_aux.tcc:39-131.
+ * Merkle trees, query responses, membership proofs and the proof of work take elem_bytes = 8. */
+int iopx_add_fft_gf64_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
+                          const uint64_t *shift, uint64_t *d_out);
+int iopx_add_fft_gf64(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
+                      const uint64_t *shift, uint64_t *out);
+int iopx_add_lde_gf64_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
+                          const uint64_t *shift, size_t coset_begin, size_t coset_count, uint64_t *d_out);
+/* In place allowed (d_evals == d_out). */
+int iopx_add_ifft_gf64_dev(const uint64_t *d_evals, const uint64_t *basis, size_t m, const uint64_t *shift,
+                           uint64_t *d_out);
+int iopx_add_ifft_gf64(const uint64_t *evals, const uint64_t *basis, size_t m, const uint64_t *shift,
+                       uint64_t *out);
+int iopx_fri_fold_add_gf64_dev(const uint64_t *d_f_i, const uint64_t *basis, size_t m, const uint64_t *shift,
+                               size_t coset_size, const uint64_t *x_i, uint64_t *d_next);
+int iopx_fri_fold_add_gf64(const uint64_t *f_i, const uint64_t *basis, size_t m, const uint64_t *shift,
+                           size_t coset_size, const uint64_t *x_i, uint64_t *next);
+int iopx_fri_domains_gf64(const uint64_t *basis, size_t m, const uint64_t *shift, const size_t *localization, size_t num_reductions,
+                          uint64_t *out_bases, uint64_t *out_shifts);
+int iopx_ldt_combine_gf64_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees,
+                              const uint64_t *random_coefficients, const uint64_t *basis, size_t m, const uint64_t *shift,
+                              uint64_t *d_out);
+/* d_out[i] = d_a[i] * d_b[i];  d_out[i] = d_a[i]^-1 (zero maps to zero);  the host scalars (the inverse of zero is refused) */
+int iopx_gf64_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
+int iopx_gf64_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
+int iopx_gf64_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
+int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out);
+
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
  * libiop/bcs/merkle_tree.tcc:92-151, 200-229 with blake2b_leafhash / blake2b_two_to_one_hash

@@ -71,6 +71,9 @@ EXPORTED_SYMBOLS = [
     "iopx_poly_div_vanishing_bn128_dev", "iopx_lincomb_bn128_dev", "iopx_bn128_mul_dev", "iopx_bn128_sub_dev", "iopx_bn128_inv_dev",
     "iopx_bn128_pow_table_dev", "iopx_lincomb_affine_bn128_dev", "iopx_bn128_div_dev", "iopx_domain_offsets_bn128_dev",
     "iopx_vanishing_evals_bn128_dev", "iopx_rational_combine_bn128_dev", "iopx_rational_sumcheck_constraint_bn128_dev",
+    "iopx_add_fft_gf64_dev", "iopx_add_fft_gf64", "iopx_add_lde_gf64_dev", "iopx_add_ifft_gf64_dev", "iopx_add_ifft_gf64",
+    "iopx_fri_fold_add_gf64_dev", "iopx_fri_fold_add_gf64", "iopx_fri_domains_gf64", "iopx_ldt_combine_gf64_dev",
+    "iopx_gf64_mul_dev", "iopx_gf64_inv_dev", "iopx_gf64_host_mul", "iopx_gf64_inverse_host",
 ]
 
 
@@ -274,6 +277,18 @@ class Library:
         c.iopx_bn128_host_add.argtypes = [_u64p, _u64p, _u64p]
         c.iopx_bn128_host_sub.argtypes = [_u64p, _u64p, _u64p]
         c.iopx_bn128_modulus.argtypes = [_u64p]
+        # GF(2^64): the prototypes of the gf192 twins, one word per element
+        for name, twin in (("iopx_add_fft_gf64_dev", "iopx_add_fft_gf192_dev"), ("iopx_add_fft_gf64", "iopx_add_fft_gf192"),
+                           ("iopx_add_lde_gf64_dev", "iopx_add_lde_gf192_dev"), ("iopx_add_ifft_gf64_dev", "iopx_add_ifft_gf192_dev"),
+                           ("iopx_add_ifft_gf64", "iopx_add_ifft_gf192"), ("iopx_fri_fold_add_gf64_dev", "iopx_fri_fold_add_gf192_dev"),
+                           ("iopx_fri_fold_add_gf64", "iopx_fri_fold_add_gf192")):
+            getattr(c, name).argtypes = list(getattr(c, twin).argtypes)
+        c.iopx_fri_domains_gf64.argtypes = [_u64p, _sz, _u64p, ctypes.POINTER(_sz), _sz, _u64p, _u64p]
+        c.iopx_ldt_combine_gf64_dev.argtypes = [ctypes.POINTER(_vp), _sz, ctypes.POINTER(_sz), _u64p, _u64p, _sz, _u64p, _vp]
+        c.iopx_gf64_mul_dev.argtypes = [_vp, _vp, _vp, _sz]
+        c.iopx_gf64_inv_dev.argtypes = [_vp, _vp, _sz]
+        c.iopx_gf64_host_mul.argtypes = [_u64p, _u64p, _u64p]
+        c.iopx_gf64_inverse_host.argtypes = [_u64p, _u64p]
 
     # ---- error translation (the exception types the reference throws) ----
     def _check(self, rc):
@@ -1452,6 +1467,152 @@ class Library:
         for i, dm in enumerate(dims):
             out.append((ob[off:off + dm].copy(), osh[i].copy()))
             off += dm
+        return out
+
+    # ---- GF(2^64): one uint64 word per element, arrays of shape (n, 1); methods named after the gf192 ones ----
+    def additive_FFT_gf64_dev(self, d_coeffs, n_coeffs, basis, shift, d_out):
+        basis, shift = _as_u64(basis, 1), _as_u64(shift, 1)
+        self._check(self.c.iopx_add_fft_gf64_dev(_vp(d_coeffs), n_coeffs, basis.ctypes.data_as(_u64p), basis.shape[0],
+                                                 shift.ctypes.data_as(_u64p), _vp(d_out)))
+
+    def additive_LDE_gf64_dev(self, d_coeffs, n_coeffs, basis, shift, coset_begin, coset_count, d_out):
+        """Cosets [coset_begin, +coset_count) of span(basis[0..d)), d = ceil(log2 n_coeffs), of the transform."""
+        basis, shift = _as_u64(basis, 1), _as_u64(shift, 1)
+        self._check(self.c.iopx_add_lde_gf64_dev(_vp(d_coeffs), n_coeffs, basis.ctypes.data_as(_u64p), basis.shape[0],
+                                                 shift.ctypes.data_as(_u64p), coset_begin, coset_count, _vp(d_out)))
+
+    def additive_IFFT_gf64_dev(self, d_evals, basis, shift, d_out):
+        basis, shift = _as_u64(basis, 1), _as_u64(shift, 1)
+        self._check(self.c.iopx_add_ifft_gf64_dev(_vp(d_evals), basis.ctypes.data_as(_u64p), basis.shape[0],
+                                                  shift.ctypes.data_as(_u64p), _vp(d_out)))
+
+    def evaluate_next_f_i_over_entire_domain_gf64_dev(self, d_f_i, basis, shift, coset_size, x_i, d_next):
+        basis, shift, x = _as_u64(basis, 1), _as_u64(shift, 1), _as_u64(x_i, 1)
+        self._check(self.c.iopx_fri_fold_add_gf64_dev(_vp(d_f_i), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
+                                                      int(coset_size), x.ctypes.data_as(_u64p), _vp(d_next)))
+
+    def additive_FFT_gf64(self, poly_coeffs, basis, shift):
+        """additive_FFT(poly_coeffs, affine_subspace(basis, shift)) over gf64 — fft.tcc:39-124."""
+        coeffs, basis, shift = _as_u64(poly_coeffs, 1), _as_u64(basis, 1), _as_u64(shift, 1)
+        m = basis.shape[0]
+        out = np.empty((1 << m, 1), dtype=np.uint64)
+        self._check(self.c.iopx_add_fft_gf64(coeffs.ctypes.data_as(_u64p), coeffs.shape[0], basis.ctypes.data_as(_u64p), m,
+                                             shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def additive_IFFT_gf64(self, evals, basis, shift):
+        """additive_IFFT(evals, affine_subspace(basis, shift)) over gf64 — fft.tcc:126-204."""
+        evals, basis, shift = _as_u64(evals, 1), _as_u64(basis, 1), _as_u64(shift, 1)
+        m = basis.shape[0]
+        if evals.shape[0] != 1 << m:
+            raise ValueError("additive IFFT: %d evaluations for a domain of size %d" % (evals.shape[0], 1 << m))
+        out = np.empty((1 << m, 1), dtype=np.uint64)
+        self._check(self.c.iopx_add_ifft_gf64(evals.ctypes.data_as(_u64p), basis.ctypes.data_as(_u64p), m,
+                                              shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def IFFT_of_known_degree_gf64(self, evals, degree, basis, shift):
+        """IFFT_of_known_degree_over_field_subset, additive overload — fft.tcc:458-475."""
+        evals, basis = _as_u64(evals, 1), _as_u64(basis, 1)
+        k = max(int(degree) - 1, 0).bit_length()
+        return self.additive_IFFT_gf64(evals[: 1 << k], basis[:k], shift)
+
+    def evaluate_next_f_i_over_entire_domain_gf64(self, f_i_evals, basis, shift, coset_size, x_i):
+        """fri_aux.tcc:5-34 -> additive_evaluate_next_f_i_over_entire_domain (:36-103) over gf64."""
+        f, basis, shift, x = _as_u64(f_i_evals, 1), _as_u64(basis, 1), _as_u64(shift, 1), _as_u64(x_i, 1)
+        m = basis.shape[0]
+        if f.shape[0] != 1 << m:
+            raise ValueError("f_i has %d evaluations for a domain of size %d" % (f.shape[0], 1 << m))
+        out = np.empty(((1 << m) // max(int(coset_size), 1), 1), dtype=np.uint64)
+        self._check(self.c.iopx_fri_fold_add_gf64(f.ctypes.data_as(_u64p), basis.ctypes.data_as(_u64p), m,
+                                                  shift.ctypes.data_as(_u64p), int(coset_size), x.ctypes.data_as(_u64p),
+                                                  out.ctypes.data_as(_u64p)))
+        return out
+
+    def fri_additive_domains_gf64(self, basis, shift, localization):
+        """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338) over gf64: [(basis_i, shift_i)] for L^(0), L^(1), ..."""
+        basis, shift = _as_u64(basis, 1), _as_u64(shift, 1)
+        m = basis.shape[0]
+        dims, d = [], m
+        for eta in localization:
+            d -= int(eta)
+            dims.append(d)
+        ob = np.zeros((max(sum(dims), 1), 1), dtype=np.uint64)
+        osh = np.zeros((max(len(dims), 1), 1), dtype=np.uint64)
+        loc = (_sz * max(len(localization), 1))(*[int(e) for e in localization])
+        self._check(self.c.iopx_fri_domains_gf64(basis.ctypes.data_as(_u64p), m, shift.ctypes.data_as(_u64p), loc, len(localization),
+                                                 ob.ctypes.data_as(_u64p), osh.ctypes.data_as(_u64p)))
+        out, off = [(basis, shift.reshape(1))], 0
+        for i, dm in enumerate(dims):
+            out.append((ob[off:off + dm].copy(), osh[i].copy()))
+            off += dm
+        return out
+
+    def ldt_combine_gf64_dev(self, d_oracles, degrees, random_coefficients, basis, shift, d_out):
+        """combined_LDT_virtual_oracle::evaluated_contents over the affine subspace (basis, shift) over gf64; device pointers."""
+        basis, shift, rc = _as_u64(basis, 1), _as_u64(shift, 1), _as_u64(random_coefficients, 1)
+        if rc.shape[0] != 2 * len(d_oracles):
+            raise ValueError("Expected the nunmber of random coefficients to be twice the number of oracles.")
+        ptrs = (_vp * len(d_oracles))(*d_oracles)
+        deg = (_sz * len(degrees))(*[int(d) for d in degrees])
+        self._check(self.c.iopx_ldt_combine_gf64_dev(ptrs, len(d_oracles), deg, rc.ctypes.data_as(_u64p), basis.ctypes.data_as(_u64p),
+                                                     basis.shape[0], shift.ctypes.data_as(_u64p), _vp(d_out)))
+
+    def ldt_combine_gf64(self, evals, degrees, random_coefficients, basis, shift):
+        """Host-array form of ldt_combine_gf64_dev: evals is a list of (2^m, 1) arrays."""
+        evals = [_as_u64(e, 1) for e in evals]
+        n = evals[0].shape[0]
+        ptrs = [self.malloc(8 * n) for _ in range(len(evals) + 1)]
+        try:
+            for p, e in zip(ptrs, evals):
+                self.h2d(p, e)
+            self.ldt_combine_gf64_dev(ptrs[:-1], degrees, random_coefficients, basis, shift, ptrs[-1])
+            out = np.empty((n, 1), dtype=np.uint64)
+            self.d2h(out, ptrs[-1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        return out
+
+    def gf64_mul_dev(self, d_a, d_b, d_out, count):
+        self._check(self.c.iopx_gf64_mul_dev(_vp(d_a), _vp(d_b), _vp(d_out), count))
+
+    def gf64_inv_dev(self, d_a, d_out, count):
+        self._check(self.c.iopx_gf64_inv_dev(_vp(d_a), _vp(d_out), count))
+
+    def _gf64_elementwise(self, arrays, call):
+        arrays = [_as_u64(a, 1) for a in arrays]
+        n = arrays[0].shape[0]
+        ptrs = [self.malloc(8 * max(n, 1)) for _ in range(len(arrays) + 1)]
+        try:
+            for p, a in zip(ptrs, arrays):
+                self.h2d(p, a)
+            call(*ptrs, n)
+            out = np.empty((n, 1), dtype=np.uint64)
+            self.d2h(out, ptrs[-1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        return out
+
+    def gf64_mul(self, a, b):
+        """Elementwise a[i] * b[i] over gf64 (host arrays)."""
+        return self._gf64_elementwise([a, b], self.gf64_mul_dev)
+
+    def gf64_inv(self, a):
+        """Elementwise inverse over gf64 (host arrays); zero maps to zero."""
+        return self._gf64_elementwise([a], self.gf64_inv_dev)
+
+    def gf64_host_mul(self, a, b):
+        a, b = _as_u64(a, 1), _as_u64(b, 1)
+        out = np.zeros(1, dtype=np.uint64)
+        self._check(self.c.iopx_gf64_host_mul(a.ctypes.data_as(_u64p), b.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def gf64_inverse_host(self, x):
+        x = _as_u64(x, 1)
+        out = np.zeros(1, dtype=np.uint64)
+        self._check(self.c.iopx_gf64_inverse_host(x.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
         return out
 
     def set_option(self, name, value):

@@ -1,4 +1,4 @@
-// Plain field-element types for C++ callers that do not link libff: 24 raw bytes with the layout of libff::gf192 (three
+// Plain field-element types for C++ callers that do not link libff: 8 raw bytes with the layout of libff::gf64, 24 raw bytes with the layout of libff::gf192 (three
 // little-endian words, polynomial basis) / libff::edwards_Fr (three Montgomery limbs), 32 with that of libff::alt_bn128_Fr (four).
 // They provide what the mirror asks of a FieldT — construction from an integer, ==, + — through the library's host helpers; a libiop
 // integration uses libff's own types instead.
@@ -17,6 +17,18 @@ struct gf192_element {
     gf192_element &operator+=(const gf192_element &o) { for (int i = 0; i < 3; ++i) w[i] ^= o.w[i]; return *this; }
 };
 template<> struct field_kind<gf192_element> { static const field_subset_type type = affine_subspace_type; };
+
+// 8 raw bytes with the layout of libff::gf64 (one little-endian word, polynomial basis, x^64 + x^4 + x^3 + x + 1)
+struct gf64 {
+    uint64_t w[1];
+    gf64() : w{ 0 } {}
+    explicit gf64(uint64_t v) : w{ v } {}
+    bool operator==(const gf64 &o) const { return w[0] == o.w[0]; }
+    bool operator!=(const gf64 &o) const { return !(*this == o); }
+    gf64 operator+(const gf64 &o) const { return gf64(w[0] ^ o.w[0]); }
+    gf64 &operator+=(const gf64 &o) { w[0] ^= o.w[0]; return *this; }
+};
+template<> struct field_kind<gf64> { static const field_subset_type type = affine_subspace_type; };
 
 struct edwards_Fr_element {
     uint64_t w[3];

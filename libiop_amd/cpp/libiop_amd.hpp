@@ -106,8 +106,11 @@ template<typename FieldT>
 class multiplicative_coset {
     std::size_t order_;
     FieldT g_, shift_;
-    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32, "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
-    typedef ops::layout<sizeof(FieldT)> F;                                                  // by size: the mirror asks nothing of FieldT beyond its bytes
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32 || sizeof(FieldT) == 8, "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
+    // by size: the mirror asks nothing of FieldT beyond its bytes.  An 8-byte field (gf64) is binary: field_subset<FieldT> names this class, but no
+    // coset of it can be built (the constructors refuse), so F is never used for it
+    typedef ops::layout<sizeof(FieldT) == 8 ? 24 : sizeof(FieldT)> F;
+    static void refuse_binary() { if constexpr (sizeof(FieldT) == 8) throw std::invalid_argument("gf64: affine subspaces only"); }
     typedef ops::prime_field_ops P;
     static FieldT host_mul(const FieldT &a, const FieldT &b)
     {
@@ -119,10 +122,12 @@ public:
     multiplicative_coset() : order_(1) {}
     multiplicative_coset(std::size_t order, const FieldT &generator, const FieldT &shift) : order_(order), g_(generator), shift_(shift)
     {
+        refuse_binary();
         if (order == 0 || (order & (order - 1))) throw std::invalid_argument("The order of the subgroup must be a power of two.");
     }
     multiplicative_coset(std::size_t order, const FieldT &shift) : order_(order), shift_(shift)        // subgroup.tcc:33-75, 199-215
     {
+        refuse_binary();
         if (order == 0 || (order & (order - 1))) throw std::invalid_argument("The order of the subgroup must be a power of two.");
         check(ops::entry<F>(&P::subgroup_generator, "multiplicative_coset")(detail::log2_ceil(order), detail::words(&g_)));
     }
@@ -280,6 +285,7 @@ template<typename FieldT>
 std::vector<FieldT> FFT_over_field_subset(const std::vector<FieldT> coeffs, field_subset<FieldT> domain)
 {
     if constexpr (sizeof(FieldT) == 32) return multiplicative_FFT<FieldT>(coeffs, domain.coset());     // alt_bn128_Fr: cosets only
+    else if constexpr (sizeof(FieldT) == 8) return additive_FFT<FieldT>(coeffs, domain.subspace());    // gf64: subspaces only
     else {
         if (domain.type() == multiplicative_coset_type) return multiplicative_FFT<FieldT>(coeffs, domain.coset());
         return additive_FFT<FieldT>(coeffs, domain.subspace());
@@ -290,6 +296,7 @@ template<typename FieldT>
 std::vector<FieldT> IFFT_over_field_subset(const std::vector<FieldT> evals, field_subset<FieldT> domain)
 {
     if constexpr (sizeof(FieldT) == 32) return multiplicative_IFFT<FieldT>(evals, domain.coset());
+    else if constexpr (sizeof(FieldT) == 8) return additive_IFFT<FieldT>(evals, domain.subspace());
     else {
         if (domain.type() == multiplicative_coset_type) return multiplicative_IFFT<FieldT>(evals, domain.coset());
         return additive_IFFT<FieldT>(evals, domain.subspace());
@@ -303,6 +310,10 @@ std::vector<FieldT> IFFT_of_known_degree_over_field_subset(const std::vector<Fie
 {
     const std::size_t pow2 = (std::size_t)1 << detail::log2_ceil(degree);
     const field_subset<FieldT> minimal = domain.get_subset_of_order(pow2);
+    if constexpr (sizeof(FieldT) == 8) {                                                    // gf64: subspaces only
+        const std::vector<FieldT> head(evals.begin(), evals.begin() + pow2);
+        return additive_IFFT<FieldT>(head, minimal.subspace());
+    } else
     if (domain.type() == multiplicative_coset_type) {
         std::vector<FieldT> sub;
         const std::size_t freq = domain.num_elements() / pow2;
@@ -342,6 +353,7 @@ std::shared_ptr<std::vector<FieldT>> evaluate_next_f_i_over_entire_domain(
     if constexpr (sizeof(FieldT) != 32) {
         if (f_i_domain.type() == affine_subspace_type) return additive_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
     }
+    if constexpr (sizeof(FieldT) != 8)
     if (f_i_domain.type() == multiplicative_coset_type) return multiplicative_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
     throw std::invalid_argument("f_i_domain is of unsupported domain type");               // fri_aux.tcc:33
 }

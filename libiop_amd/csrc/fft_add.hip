@@ -1542,6 +1542,7 @@ int iopx_clear_plans(void)
     clear_mul_plans();
     clear_dist_plans();
     clear_poseidon_sets();
+    clear_gf64_plans();
     clear_domain_tables();
     tmp_trim();
     return IOPX_OK;

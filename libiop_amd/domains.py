@@ -26,8 +26,9 @@ class Domain:
     def __init__(self, field, kind, basis=None, shift=None, log_n=None):
         self.field, self.kind = field, kind
         if kind == ADDITIVE:
-            self.basis = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, 3)
-            self.shift = np.ascontiguousarray(shift, dtype=np.uint64).reshape(3)
+            w = getattr(field, "words", 3)                               # GF(2^192): three words; GF(2^64): one
+            self.basis = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, w)
+            self.shift = np.ascontiguousarray(shift, dtype=np.uint64).reshape(w)
             self.dim = self.basis.shape[0]
         elif getattr(field, "words", 3) == 4:                            # alt_bn128 Fr: the same coset, four-word elements
             self.dim = int(log_n)
@@ -69,6 +70,10 @@ class Domain:
 
     def element_outside_of_subset(self):
         """subspace.tcc:219-227 (standard basis): shift + FieldT(1 << dim); subgroup.tcc:311-315: shift * multiplicative_generator."""
+        if self.additive and getattr(self.field, "words", 3) == 1:
+            if not np.array_equal(self.basis, self.field.standard_basis(self.dim)):
+                raise ValueError("subspace.element_outside_of_subset() is only supported for standard basis")
+            return np.array([int(self.shift[0]) ^ (1 << self.dim)], dtype=np.uint64)
         if self.additive:
             if not np.array_equal(self.basis, la.standard_basis(self.dim)):
                 raise ValueError("subspace.element_outside_of_subset() is only supported for standard basis")
@@ -160,6 +165,109 @@ class GF192:
     def fri_domains(self, domain, localization, lib):
         """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338), by the library's host-side helper."""
         chain = lib.fri_additive_domains(domain.basis, domain.shift, localization)
+        return [domain] + [Domain(self, ADDITIVE, basis=b, shift=s) for b, s in chain[1:]]
+
+
+class GF64:
+    """libff::gf64 (x^64 + x^4 + x^3 + x + 1, one word), additive arm.  Host scalars are (1,) uint64 arrays; the handful of host-side
+    products run on Python integers."""
+    name, additive, elem_bytes, words, soundness_bits = "gf64", True, 8, 1, 64
+
+    @staticmethod
+    def standard_basis(m):
+        """subspace.tcc:93-108 — basis element i is FieldT(1 << i)."""
+        return (np.uint64(1) << np.arange(m, dtype=np.uint64)).reshape(m, 1)
+
+    def domain(self, num_elements, shift=None):
+        d = _log2(num_elements)
+        return Domain(self, ADDITIVE, basis=self.standard_basis(d), shift=np.zeros(1, dtype=np.uint64) if shift is None else shift)
+
+    @staticmethod
+    def _int(a):
+        return int(np.asarray(a, dtype=np.uint64).reshape(-1)[0])
+
+    @staticmethod
+    def _elem(v):
+        return np.array([v], dtype=np.uint64)
+
+    @staticmethod
+    def _mul(a, b):
+        r = 0
+        while b:
+            if b & 1:
+                r ^= a
+            b >>= 1
+            a <<= 1
+            if a >> 64:
+                a ^= (1 << 64) | 0x1B
+        return r
+
+    def zero(self):
+        return np.zeros(1, dtype=np.uint64)
+
+    def one(self):
+        return self._elem(1)
+
+    def mul(self, a, b):
+        return self._elem(self._mul(self._int(a), self._int(b)))
+
+    def add(self, a, b):
+        return np.bitwise_xor(np.asarray(a, dtype=np.uint64), np.asarray(b, dtype=np.uint64))
+
+    def sub(self, a, b):
+        return self.add(a, b)
+
+    def neg(self, a):
+        return np.asarray(a, dtype=np.uint64)
+
+    def inv(self, a, lib):
+        return lib.gf64_inverse_host(a)
+
+    def _subspace_poly(self, domain):
+        """coefficients c_i of prod_{v in span(basis)} (X - v) = sum_i c_i X^(2^i) (vanishing_polynomial.tcc:373-395)"""
+        def ev(c, x):
+            r = 0
+            for ci in c:
+                r ^= self._mul(ci, x)
+                x = self._mul(x, x)
+            return r
+        c = [1]
+        for b in domain.basis[:, 0]:
+            zb = ev(c, int(b))
+            nxt = [0] * (len(c) + 1)
+            for i, ci in enumerate(c):
+                nxt[i + 1] ^= self._mul(ci, ci)
+                nxt[i] ^= self._mul(ci, zb)
+            c = nxt
+        return c, ev
+
+    def vanishing_eval(self, domain, x, lib=None):
+        """Z_S(x) for the affine subspace S: the subspace polynomial at x plus at the shift."""
+        c, ev = self._subspace_poly(domain)
+        return self._elem(ev(c, self._int(x)) ^ ev(c, self._int(domain.shift)))
+
+    def vanishing_derivative(self, domain, x, lib=None):
+        """(DZ_S)(x): the linear coefficient (vanishing_polynomial.tcc:63-72)."""
+        return self._elem(self._subspace_poly(domain)[0][0])
+
+    def element_in_domain(self, domain, x):
+        if not np.array_equal(domain.basis, self.standard_basis(domain.dim)):
+            raise NotImplementedError("membership test for a non-standard basis")
+        return (self._int(x) ^ self._int(domain.shift)) < (1 << domain.dim)
+
+    def squeeze(self, hashchain, n):
+        """blake2b_FieldT_randomness_extractor for a binary field of 8 bytes (blake2b.tcc:162-185, 231-257): element i = keyed
+        BLAKE2b(state || index, key = i, 8 bytes), the raw word."""
+        hashchain.squeeze_index += 1
+        msg = hashchain.state + hashchain.squeeze_index.to_bytes(8, "little")
+        out = np.zeros((n, 1), dtype=np.uint64)
+        for i in range(n):
+            out[i, 0] = int.from_bytes(hashlib.blake2b(msg, digest_size=8, key=i.to_bytes(8, "little")).digest(), "little")
+        return out
+
+    def fri_domains(self, domain, localization, lib):
+        """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338), by the library's host-side helper."""
+        chain = lib.fri_additive_domains_gf64(domain.basis, domain.shift, localization)
         return [domain] + [Domain(self, ADDITIVE, basis=b, shift=s) for b, s in chain[1:]]
 
 
@@ -288,12 +396,16 @@ class DeviceOps:
         # redirected: a subclass (the sharded operators of libiop_amd/dist.py) is built as asked, and __init__ refuses the field there
         if cls is DeviceOps and getattr(field, "words", 3) == 4:
             cls = AltBn128DeviceOps
+        if cls is DeviceOps and getattr(field, "words", 3) == 1:        # GF(2^64): one-word vectors, the iopx_*_gf64 entries
+            cls = GF64DeviceOps
         return object.__new__(cls)
 
     def __init__(self, lib, torch, device, field):
         self.lib, self.torch, self.device, self.field = lib, torch, device, field
         if getattr(field, "words", 3) == 4 and not isinstance(self, AltBn128DeviceOps):
             raise NotImplementedError("%s: no operators over a four-word field (alt_bn128 Fr runs on one GPU, through DeviceOps)" % type(self).__name__)
+        if getattr(field, "words", 3) == 1 and not isinstance(self, GF64DeviceOps):
+            raise NotImplementedError("%s: no operators over a one-word field (gf64 runs on one GPU, through DeviceOps)" % type(self).__name__)
         # The provers interleave torch ops (copies, index assignments, torch.cat, buffers recycled by the caching allocator) with
         # library kernels WITHOUT host synchronisation: that is only ordered when both enqueue on the same stream.  Refuse the
         # unshared configuration instead of racing (libiop_amd/dist.py's collectives have their own host-synchronised fallback).
@@ -778,6 +890,75 @@ class AltBn128DeviceOps(DeviceOps):
         if n_coeffs > domain.size:
             self.lib.bn128_poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.dim, domain.shift, out.data_ptr())
         return out
+
+
+class GF64DeviceOps(DeviceOps):
+    """DeviceOps over GF64: (count, 1) int64 vectors, the iopx_*_gf64 entries.  It has what the FRI-only SNARK (libiop_amd/fri.py) calls;
+    every other operator of DeviceOps raises NotImplementedError — nothing falls through to a gf192 entry."""
+    W = 1
+
+    def query_responses(self, d_oracles, domain, positions):
+        return self.lib.query_responses_dev([t.data_ptr() for t in d_oracles], 8, domain.size, positions)
+
+    def empty(self, n):
+        return self.torch.empty((max(int(n), 1), 1), dtype=self.torch.int64, device=self.device)[: int(n)]
+
+    def upload(self, host_words):
+        a = np.ascontiguousarray(host_words, dtype=np.uint64).reshape(-1, 1)
+        t = self.empty(a.shape[0])
+        if a.shape[0]:
+            self.lib.h2d(t.data_ptr(), a)
+        return t
+
+    def download(self, t, count=None):
+        n = t.shape[0] if count is None else count
+        out = np.empty((n, 1), dtype=np.uint64)
+        if n:
+            self.lib.d2h(out, t.data_ptr())
+        return out
+
+    def FFT(self, d_coeffs, n_coeffs, domain):
+        out = self.empty(domain.size)
+        self.lib.additive_FFT_gf64_dev(d_coeffs.data_ptr(), int(n_coeffs), domain.basis, domain.shift, out.data_ptr())
+        return out
+
+    def IFFT(self, d_evals, domain):
+        out = self.empty(domain.size)
+        self.lib.additive_IFFT_gf64_dev(d_evals.data_ptr(), domain.basis, domain.shift, out.data_ptr())
+        return out
+
+    def IFFT_of_known_degree(self, d_evals, degree, domain):
+        k = _log2(degree)
+        return self.IFFT(d_evals[: 1 << k], domain.get_subset_of_order(1 << k))
+
+    def fold(self, d_f, domain, coset_size, x_i, next_domain=None):
+        out = self.empty(domain.size // coset_size)
+        self.lib.evaluate_next_f_i_over_entire_domain_gf64_dev(d_f.data_ptr(), domain.basis, domain.shift, coset_size, x_i, out.data_ptr())
+        return out
+
+    def merkle_tree(self, d_oracles, domain, coset_size):
+        leaves = domain.size // coset_size
+        nodes = self.torch.empty((2 * leaves - 1, 32), dtype=self.torch.uint8, device=self.device)
+        self.lib.merkle_tree_dev([t.data_ptr() for t in d_oracles], 8, domain.size, coset_size, nodes.data_ptr(), domain_type=domain.domain_type)
+        return MerkleTree(self.lib, nodes, leaves)
+
+    def ldt_combine(self, d_oracles, degrees, random_coefficients, domain):
+        out = self.empty(domain.size)
+        self.lib.ldt_combine_gf64_dev([t.data_ptr() for t in d_oracles], degrees, random_coefficients, domain.basis, domain.shift, out.data_ptr())
+        return out
+
+
+def _gf64_not_implemented(name):
+    def op(self, *args, **kwargs):
+        raise NotImplementedError("gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK is the only prover over this field)" % name)
+    op.__name__ = name
+    return op
+
+
+for _name in ("FFT_batch", "IFFT_batch", "IFFT_batch_packed", "reextend_packed", "_coset_range", "rowcheck", "fz", "sumcheck_g", "lincheck", "lincomb",
+              "sub", "mul", "inv", "pow_table", "spmv", "div", "domain_offsets", "domain_elements", "vanishing_evals", "lagrange_evals",
+              "lincomb_affine", "rational_combine", "rational_sumcheck_constraint", "poly_div_vanishing", "upload_raw"):
+    setattr(GF64DeviceOps, _name, _gf64_not_implemented(_name))
 
 
 def _p(words):

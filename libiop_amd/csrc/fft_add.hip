@@ -41,7 +41,7 @@ static const Tuning &tuning()
 {
     static const Tuning t = [] {
         Tuning u;
-        u.tile_bits = env_int("IOPX_TILE_BITS", 11, 4, 12);   // 2048-element tiles: two comb workgroups per CU overlap their load / compute phases
+        u.tile_bits = env_int("IOPX_TILE_BITS", 11, 4, 12);   // 2048-element tiles: three comb workgroups per CU (48 KiB of LDS each, 6 waves per SIMD)
         u.p1_tile_bits = (u.tile_bits < 10 ? u.tile_bits : 10);   // phase 1 is latency-bound: smaller tiles, more workgroups per CU
         u.p1_cols = env_int("IOPX_P1_COLS", 3, 0, u.p1_tile_bits - 3);  // strided phase-1 tiles: 2^c contiguous columns
         // the last phase-1 pass runs every remaining level inside its tile (multiplier-bound): it may use a larger, narrower tile
@@ -491,8 +491,9 @@ __device__ __forceinline__ void bf_apply_small1(uint64_t *s, int E, int ia, int 
     lds_put(s, E, ib, b);
 }
 
-template<bool INV, bool COMB>
-__global__ void __launch_bounds__(COMB ? 512 : 1024, COMB ? 6 : 1) k_bfly_upper(BfParams p)
+// (tiles narrower than 64 columns, or IOPX_COMB=0: the general product; the comb form is k_bfly_upper_comb)
+template<bool INV>
+__global__ void __launch_bounds__(1024, 1) k_bfly_upper(BfParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
     uint64_t *s = iopx_smem;
@@ -518,23 +519,10 @@ __global__ void __launch_bounds__(COMB ? 512 : 1024, COMB ? 6 : 1) k_bfly_upper(
     for (int t = 0; t < nlev; ++t) {
         const int pbit = INV ? p.p_lo + t : p.p_hi - t;
         const int pl = pbit - p.h + p.c;
-        if (COMB) {
-            // launched only for tiles with >= 64 columns (p.c >= 6), so pl >= 6 at every level: 64 consecutive butterflies share a block and the
-            // twiddle is wave-uniform.  One butterfly per trip, nothing hoisted: the kernel must fit 80 VGPRs (6 waves per SIMD hide the comb
-            // product's branch latency); the twiddle is fetched through a uniform index
-#pragma unroll 1
-            for (int bf = tid; bf < (E >> 1); bf += nt) {          // (requesting the next trip's twiddle ahead of the product changed nothing: 22.0 vs 22.1 ms)
-                const int ia = ((bf >> pl) << (pl + 1)) | (bf & ((1 << pl) - 1));
-                const uint32_t ia_u = __builtin_amdgcn_readfirstlane((uint32_t)(ia & ~63));
-                const gf192 tw = bf_twiddle_uniform(p, coset, base | ((size_t)(ia_u >> p.c) << p.h) | (size_t)(ia_u & cmask), pbit);
-                bf_apply<INV, true>(s, E, ia, ia | (1 << pl), tw, true);
-            }
-        } else {
-            for (int bf = tid; bf < (E >> 1); bf += nt) {
-                const int ia = ((bf >> pl) << (pl + 1)) | (bf & ((1 << pl) - 1));
-                const gf192 tw = bf_twiddle(p, coset, base | ((size_t)(ia >> p.c) << p.h) | (size_t)(ia & cmask), pbit);
-                bf_apply<INV, false>(s, E, ia, ia | (1 << pl), tw, false);
-            }
+        for (int bf = tid; bf < (E >> 1); bf += nt) {
+            const int ia = ((bf >> pl) << (pl + 1)) | (bf & ((1 << pl) - 1));
+            const gf192 tw = bf_twiddle(p, coset, base | ((size_t)(ia >> p.c) << p.h) | (size_t)(ia & cmask), pbit);
+            bf_apply<INV, false>(s, E, ia, ia | (1 << pl), tw, false);
         }
         __syncthreads();
     }
@@ -542,6 +530,98 @@ __global__ void __launch_bounds__(COMB ? 512 : 1024, COMB ? 6 : 1) k_bfly_upper(
     for (int li = tid; li < E; li += nt) {
         const size_t u = base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask);
         gf_store(dst, u, lds_get(s, E, li));
+    }
+}
+
+// The comb butterfly with either end of it in global memory: the first level of a tile reads its two elements from `src`, the last one writes
+// them to `dst` (ua, ub: their in-coset indices); the levels between go through the LDS tile (slots ia, ib)
+template<bool INV>
+__device__ __forceinline__ void bf_apply_io(uint64_t *s, int E, int ia, int ib, const uint64_t *src, uint64_t *dst, size_t ua, size_t ub,
+                                            const gf192 &tw, bool from_global, bool to_global)
+{
+    gf192 a, b;
+    if (from_global) { a = gf_load(src, ua); b = gf_load(src, ub); }
+    else { a = lds_get(s, E, ia); b = lds_get(s, E, ib); }
+    if (!INV) {
+        gf_add_to(a, gf_mul_uniform(b, tw));
+        gf_add_to(b, a);
+    } else {
+        gf_add_to(b, a);
+        gf_add_to(a, gf_mul_uniform(b, tw));
+    }
+    if (to_global) { gf_store(dst, ua, a); gf_store(dst, ub, b); }
+    else { lds_put(s, E, ia, a); lds_put(s, E, ib, b); }
+}
+
+// Which rows of a comb tile a wavefront owns.  A tile is 2^A rows of 2^c >= 64 columns and a lane only ever touches its own column, so the
+// elements a butterfly level exchanges differ in one row bit.  Levels are taken two at a time (t = 0, 1 | 2, 3 | ...; forward from the top
+// row bit down, inverse from row bit 0 up): during both levels of a pair, wave task `rowset` holds the four rows that differ in the pair's two
+// row bits, q and q + 1, so each of its lanes reads back only LDS words it wrote itself and the pair needs no barrier inside.  A last level
+// left alone (A odd) keeps its bit and the bit of the level before it.  The map depends on (level, task) and nothing else: ownership changes
+// exactly where t crosses an even number, and that is where k_bfly_upper_comb has its barriers.
+struct UpperOwn { int q, row0; };           // rows row0 | (k << q), k < 4
+__device__ __forceinline__ UpperOwn upper_own(bool inv, int A, int t, int rowset)
+{
+    if (A == 1) return UpperOwn{0, 0};                          // two rows, one level: nothing to share out
+    const int te = t & ~1;
+    const int r0 = inv ? te : A - 1 - te;                       // row bit of level te
+    const bool paired = te + 1 < A;
+    UpperOwn o;
+    o.q = (inv == paired) ? r0 : r0 - 1;                        // paired: the next level's bit is r0 + 1 (inverse) or r0 - 1; alone: the one before
+    o.row0 = ((rowset >> o.q) << (o.q + 2)) | (rowset & ((1 << o.q) - 1));
+    return o;
+}
+
+// The upper pass on the comb product: tiles of 2^A rows by 2^c >= 64 columns, so that at every level 64 consecutive butterflies share a block and
+// the twiddle is wave-uniform.  The first level of a tile reads its elements straight from global memory and the last one writes them straight
+// back: no load or store loop, five LDS round trips per element in a five-level tile instead of seven, and a one-level tile touches no LDS
+// (both ends of its only level are global).
+// Between them the rows are wave-owned (upper_own): one barrier per two levels, two in a five-level tile.  One butterfly per trip, nothing
+// hoisted: the kernel must fit 80 VGPRs (6 waves per SIMD hide the comb product's branch latency).
+template<bool INV>
+__global__ void __launch_bounds__(512, 6) k_bfly_upper_comb(BfParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
+    uint64_t *s = iopx_smem;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int E = 1 << (p.c + p.A);
+    const int tpc_bits = p.d - p.c - p.A;
+    const size_t unit = blockIdx.x;
+    const size_t coset = unit >> tpc_bits, o = unit & (((size_t)1 << tpc_bits) - 1);
+    const int midbits = p.h - p.c;
+    const size_t mid = o & (((size_t)1 << midbits) - 1), hi = o >> midbits;
+    const size_t base = (hi << (p.h + p.A)) | (mid << p.c);
+    const int cmask = (1 << p.c) - 1;
+    const uint64_t *src = p.src_shared ? p.src : p.src + 3 * (coset << p.d);
+    uint64_t *dst = p.dst + 3 * (coset << p.d);
+    const int nlev = p.A;
+
+    // item = (wave task, lane): E / 256 tasks of four rows by 64 columns, one per wavefront (the host launches E / 4 threads).  A one-level tile has
+    // two rows only: its tasks are the E / 128 column chunks, one butterfly per lane, from global memory to global memory
+    const int cbits = p.c - 6;
+    const int nitems = nlev == 1 ? (E >> 1) : (E >> 2);
+    for (int t0 = 0; t0 < nlev; t0 += 2) {
+        const int steps = nlev == 1 ? 1 : 2 * (t0 + 2 <= nlev ? 2 : 1);     // two butterflies per lane and level
+        if (t0 > 0) __syncthreads();                                // the rows change hands
+#pragma unroll 1
+        for (int it = tid; it < nitems; it += nt) {
+            const int task = (int)__builtin_amdgcn_readfirstlane((uint32_t)(it >> 6));       // blockDim is a multiple of 64
+            const int col = ((task & ((1 << cbits) - 1)) << 6) | (it & 63);
+            const UpperOwn own = upper_own(INV, nlev, t0, task >> cbits);
+            gf192 tw = gf_zero();
+#pragma unroll 1
+            for (int step = 0; step < steps; ++step) {
+                const int t = t0 + (step >> 1), k = step & 1;
+                const int r = INV ? t : nlev - 1 - t, pbit = p.h + r;
+                const int other = (r == own.q) ? own.q + 1 : own.q;
+                const int ra = own.row0 | (k << other);
+                // the two butterflies of the level on the upper bit lie in one block: one twiddle
+                if (k == 0 || other > r) tw = bf_twiddle_uniform(p, coset, base | ((size_t)ra << p.h), pbit);
+                const int ia = (ra << p.c) | col;
+                const size_t ua = base | ((size_t)ra << p.h) | (size_t)col;
+                bf_apply_io<INV>(s, E, ia, ia | (1 << (r + p.c)), src, dst, ua, ua | ((size_t)1 << pbit), tw, t == 0, t == nlev - 1);
+            }
+        }
     }
 }
 
@@ -1393,11 +1473,13 @@ static int run_phase2(AddPlan &pl, const uint64_t *src, uint64_t *dst, int nhi, 
         int threads = (1 << tbits) >= 2 * maxt ? maxt : ((1 << tbits) >= 128 ? (1 << tbits) / 2 : 64);
         int rc;
         if (tuning().comb && u.c >= 6) {
-            if ((rc = set_lds(k_bfly_upper<INV, true>, lds)) != IOPX_OK) return rc;
-            { ProfScope ps_(INV ? "k_bfly_upper_inv" : "k_bfly_upper_fwd", (ncos << d) * 48, ((ncos << d) >> 1) * (size_t)u.A); hipLaunchKernelGGL((k_bfly_upper<INV, true>), dim3((unsigned)blocks), dim3(threads), lds, stream(), p); }
+            // wave-owned rows: a wavefront takes four rows (two butterflies per lane and level), so a tile of E elements keeps E / 4 threads busy
+            if (u.A >= 2) threads = std::max(64, std::min(512, (1 << tbits) / 4));
+            if ((rc = set_lds(k_bfly_upper_comb<INV>, lds)) != IOPX_OK) return rc;
+            { ProfScope ps_(INV ? "k_bfly_upper_inv" : "k_bfly_upper_fwd", (ncos << d) * 48, ((ncos << d) >> 1) * (size_t)u.A); hipLaunchKernelGGL((k_bfly_upper_comb<INV>), dim3((unsigned)blocks), dim3(threads), lds, stream(), p); }
         } else {
-            if ((rc = set_lds(k_bfly_upper<INV, false>, lds)) != IOPX_OK) return rc;
-            { ProfScope ps_(INV ? "k_bfly_upper_inv" : "k_bfly_upper_fwd", (ncos << d) * 48, ((ncos << d) >> 1) * (size_t)u.A); hipLaunchKernelGGL((k_bfly_upper<INV, false>), dim3((unsigned)blocks), dim3(threads), lds, stream(), p); }
+            if ((rc = set_lds(k_bfly_upper<INV>, lds)) != IOPX_OK) return rc;
+            { ProfScope ps_(INV ? "k_bfly_upper_inv" : "k_bfly_upper_fwd", (ncos << d) * 48, ((ncos << d) >> 1) * (size_t)u.A); hipLaunchKernelGGL((k_bfly_upper<INV>), dim3((unsigned)blocks), dim3(threads), lds, stream(), p); }
         }
         return IOPX_OK;
     };

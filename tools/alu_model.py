@@ -9,7 +9,7 @@ per-class issue cost measured by tools/ubench/valu_rates (profiles/r05_valu_rate
     ceiling [products/s] = SIMDs x clock / sum_class(count_class x cycles_class) x 64 lanes
 
 bench.py divides the rate it measures live (field products per launch / HIP-event time) by this ceiling: roofline.alu_ceiling_frac.
-Writes profiles/r06_alu_model.json.  Needs hipcc (cross-compiles without a GPU)."""
+Writes profiles/r07_alu_model.json (bench.py --full still reads round 6's file, whose k_bfly_upper entry is the loop before the tile rewrite).  Needs hipcc (cross-compiles without a GPU)."""
 import json
 import os
 import re
@@ -18,6 +18,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIMDS, CLOCK = 1024, 2.4e9
+TILE_LEVELS = 5                           # the tile height the upper pass is priced at (1404 of the proof's 2106 forward launches)
 RATES_FILE = "r05_valu_rates.txt"          # tools/ubench/valu_rates on the MI355X (the newest collection)
 
 # mnemonic -> micro-benchmark line it is priced by (profiles/r05_valu_rates.txt); anything else that starts with v_ is priced as the
@@ -63,7 +64,7 @@ def kernel_body(asm, mangled_prefix):
     return m.group(1), m.group(2).split("\n")
 
 
-def hot_loop(lines, want_asm, mads=(250, 10 ** 9)):
+def hot_loop(lines, want_asm, mads=(250, 10 ** 9), whole=False):
     """The butterfly loop: the shortest loop (label ... backward branch to it) that contains the field product — the inline-asm block of
     the comb product (want_asm) or a number of v_mad_u64_u32 in `mads`: >= 250 for the general product (288), 90-120 for the one-word
     numerator product of the last level (6 word products = 96), 130-200 for the two-word one (9 word products = 144)."""
@@ -79,6 +80,11 @@ def hot_loop(lines, want_asm, mads=(250, 10 ** 9)):
             tgt = m.group(1) or m.group(2)
             if tgt in labels and labels[tgt] < i:
                 loops.append((labels[tgt], i))
+    if whole:                               # several backward branches to one header (alternative tails of the body): one loop, up to the last —
+        ends = {}                           # the tile loop's global-store tail lies behind its LDS-write tail's branch
+        for a, b in loops:
+            ends[a] = max(b, ends.get(a, b))
+        loops = list(ends.items())
     best = None
     for a, b in loops:
         body = lines[a:b + 1]
@@ -138,6 +144,57 @@ def classify(body, rates):
     return counts, other, unmeasured, cycles
 
 
+def basic_blocks(body):
+    """The loop body cut at labels and after branches."""
+    blocks, cur = [], []
+    for l in body:
+        if re.match(r"^\.LBB\d+_\d+:", l) and cur:
+            blocks.append(cur)
+            cur = []
+        cur.append(l)
+        if re.match(r"\s+s_(cbranch_\w+|branch)\s", l):
+            blocks.append(cur)
+            cur = []
+    if cur:
+        blocks.append(cur)
+    return blocks
+
+
+def classify_tile_loop(body, rates, levels):
+    """k_bfly_upper_comb's step loop holds both forms of either end of a butterfly: the blocks with global loads / stores run at a tile's first /
+    last level only, the blocks with LDS reads / writes at the others.  Prices the loop for each kind of level and for the mean butterfly
+    of a tile of `levels` levels (one level of the first kind, one of the last, levels - 2 between; every other block counts once)."""
+    def kind(block):
+        ops = [m.group(1) for m in (re.match(r"\s+([a-z_0-9]+)", l) for l in block) if m]
+        if any(o.startswith("global_load") for o in ops): return "global_load"
+        if any(o.startswith("global_store") for o in ops): return "global_store"
+        if any(o.startswith("ds_read") for o in ops): return "lds_read"
+        if any(o.startswith("ds_write") for o in ops): return "lds_write"
+        return "common"
+    parts = {}
+    for b in basic_blocks(body):
+        parts.setdefault(kind(b), []).extend(b)
+    missing = [k for k in ("global_load", "global_store", "lds_read", "lds_write") if k not in parts]
+    if missing:
+        raise SystemExit("tile loop: no block with %s" % ", ".join(missing))
+    priced = {k: classify(v, rates) for k, v in parts.items()}
+    def level(load, store):
+        counts, other = {}, {}
+        for k in ("common", load, store):
+            for c, n in priced[k][0].items():
+                counts[c] = counts.get(c, 0) + n
+            for c, n in priced[k][1].items():
+                other[c] = other.get(c, 0) + n
+        return counts, other, sum(priced[k][3] for k in ("common", load, store))
+    first, mid, last = level("global_load", "lds_write"), level("lds_read", "lds_write"), level("lds_read", "global_store")
+    mean = (first[2] + last[2] + (levels - 2) * mid[2]) / levels
+    unmeasured = {}
+    for k in priced:
+        for c, n in priced[k][2].items():
+            unmeasured[c] = unmeasured.get(c, 0) + n
+    return {"first level (global -> LDS)": first, "middle level (LDS -> LDS)": mid, "last level (LDS -> global)": last}, unmeasured, mean
+
+
 def comb_dynamic(rates):
     """Expected instruction counts of one comb_clmul_192_uniform call (tools/gen_comb_asm.py), window nibbles uniform over 0..15."""
     fast, slow = "v_xor_b32 (VOP2)", "v_alignbit_b32"
@@ -164,12 +221,23 @@ def main():
            "class_cycles_per_wave_instruction": {k: round(cycles_of(v), 3) for k, v in rates.items()},
            "rates_file": "profiles/" + RATES_FILE, "kernels": {}}
     comb = comb_dynamic(rates)
-    for name, prefix, want_asm in (("k_bfly_upper", "_ZN4iopx12k_bfly_upperILb0ELb1EEE", True), ("k_bfly_edge", "_ZN4iopx11k_bfly_edgeILb0ELb0EEE", False)):
+    for name, prefix, want_asm in (("k_bfly_upper", "_ZN4iopx17k_bfly_upper_combILb0EEE", True), ("k_bfly_edge", "_ZN4iopx11k_bfly_edgeILb0ELb0EEE", False)):
         sym, lines = kernel_body(asm, prefix)
-        body = hot_loop(lines, want_asm)
-        counts, other, unmeasured, cycles = classify(body, rates)
-        entry = {"symbol": sym, "unit": "butterfly (one field product)", "loop_valu_by_class_outside_asm": counts, "loop_other": other,
-                 "unmeasured_opcodes_priced_as_slow": unmeasured, "loop_cycles_outside_asm": round(cycles, 1)}
+        body = hot_loop(lines, want_asm, whole=(name == "k_bfly_upper"))
+        if name == "k_bfly_upper":
+            by_level, unmeasured, cycles = classify_tile_loop(body, rates, TILE_LEVELS)
+            counts, other = by_level["middle level (LDS -> LDS)"][:2]
+            entry = {"symbol": sym, "unit": "butterfly (one field product), mean over a tile of %d levels" % TILE_LEVELS,
+                     "loop_valu_by_class_outside_asm": counts, "loop_other": other, "unmeasured_opcodes_priced_as_slow": unmeasured,
+                     "loop_cycles_outside_asm": round(cycles, 1),
+                     "loop_cycles_outside_asm_by_level": {k: round(v[2], 1) for k, v in by_level.items()},
+                     "loop_other_by_level": {k: v[1] for k, v in by_level.items()},
+                     "note": "loop_valu_by_class_outside_asm / loop_other are the middle level's; blocks outside the two ends of the butterfly "
+                             "(index arithmetic, the twiddle fetch, which one butterfly in four of a paired level skips) count once"}
+        else:
+            counts, other, unmeasured, cycles = classify(body, rates)
+            entry = {"symbol": sym, "unit": "butterfly (one field product)", "loop_valu_by_class_outside_asm": counts, "loop_other": other,
+                     "unmeasured_opcodes_priced_as_slow": unmeasured, "loop_cycles_outside_asm": round(cycles, 1)}
         total_cycles = cycles
         if want_asm:
             entry["comb_product_dynamic"] = {k: (round(v, 1) if isinstance(v, float) else v) for k, v in comb.items()}
@@ -192,7 +260,7 @@ def main():
         entry["alu_ceiling_products_per_s"] = SIMDS * CLOCK / total_cycles * 64
         out["kernels"][name] = entry
         print(name, "cycles per wave-butterfly %.0f" % total_cycles, "ceiling %.3e products/s" % entry["alu_ceiling_products_per_s"], "unmeasured:", unmeasured)
-    json.dump(out, open(os.path.join(ROOT, "profiles", "r06_alu_model.json"), "w"), indent=1)
+    json.dump(out, open(os.path.join(ROOT, "profiles", "r07_alu_model.json"), "w"), indent=1)
 
 
 if __name__ == "__main__":

@@ -63,6 +63,8 @@ def profile_name(symbol):
         name = m.group(1)
         targ = (m.group(2) or "").split(",")[0].strip()
         first = "1" if targ in ("true", "1", "(bool)1") else ("0" if targ in ("false", "0", "(bool)0") else None)
+    if name == "k_bfly_upper_comb":                                            # the comb form of the upper pass: profiled under k_bfly_upper's names
+        name = "k_bfly_upper"
     if name == "k_bfly_edge_multi":                                            # the edge pass with several cosets per workgroup: the library's profiler names it like k_bfly_edge
         name = "k_bfly_edge"
     if name in ("k_bfly_upper", "k_bfly_edge", "k_phase1"):

@@ -39,7 +39,7 @@ EMU_SRCS := $(wildcard $(REPO)/libiop_amd/csrc/*.hip)
 EMU_HDRS := $(wildcard $(REPO)/libiop_amd/csrc/*.h) $(wildcard $(REPO)/libiop_amd/cpp/*.hpp) $(REPO)/tests/emu/fakehip/hip/hip_runtime.h \
             $(REPO)/tests/emu/fakehip/iopx/gfx950_comb.h $(REPO)/include/libiop_amd.h
 EMU_OBJS := $(patsubst $(REPO)/libiop_amd/csrc/%.hip,$(EMU)/obj/%.o,$(EMU_SRCS)) $(EMU)/obj/emu_runtime.o
-EMU_FLAGS := -O2 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unknown-pragmas -I$(REPO)/tests/emu/fakehip
+EMU_FLAGS := -O2 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unknown-pragmas -fno-extern-tls-init -I$(REPO)/tests/emu/fakehip
 
 $(EMU)/libiopx_emu.so: $(EMU_OBJS)
 	$(CXX) -shared -o $@ $^

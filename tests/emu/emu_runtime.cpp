@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY — see fakehip/hip/hip_runtime.h
 //
-// Besides running kernels one workgroup at a time, this file models HIP's streams and events so that a missing ordering edge between two
+// Besides running kernels one workgroup at a time (with one thread each or, in the threaded mode below, one fiber per thread), this file models HIP's streams and events so that a missing ordering edge between two
 // streams shows as a deterministic difference in bytes ("Emulated streams").
 //   eager (default)   every call acts at once: one implicit stream, the behaviour the suite has always had
 //   all late          every stream is a queue of operations (launches, asynchronous copies and fills, event records, event waits) that runs
@@ -17,27 +17,238 @@
 #include <memory>
 #include <mutex>
 #include <vector>
+#include <sys/mman.h>
+#include <ucontext.h>
+#if defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/common_interface_defs.h>
+#endif
 
 thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
-namespace iopx { alignas(16) uint64_t iopx_smem[160 * 1024 / 8]; }
+// thread_local like every __shared__ declaration (fakehip/hip/hip_runtime.h): the kernels' block-scope `extern __shared__ ... iopx_smem[]` names this
+namespace iopx { alignas(16) thread_local uint64_t iopx_smem[160 * 1024 / 8]; }
 
 thread_local int iopx_emu_lane = 0;
 
+// ---- threaded mode: one fiber per thread of a workgroup --------------------------------------------------------------------------------
+// order & 3: 0 one thread per workgroup (blockDim = 1, the default), 1 ascending thread index, 2 descending, 3 a permutation drawn from the seed
+// and the workgroup's index; order & 4: workgroups in descending order.  A fiber runs alone until its next __syncthreads() or its return, and the
+// next phase starts when every live fiber has arrived: a value that one thread writes and another reads inside one barrier interval is read
+// stale under ascending or under descending order, whichever runs the reader first.
+namespace {
+
+enum { THREADS_ONE = 0, THREADS_ASC = 1, THREADS_DESC = 2, THREADS_SEEDED = 3, THREADS_GROUPS_DESC = 4 };
+std::atomic<int> g_thread_order{ 0 };
+std::atomic<uint64_t> g_thread_seed{ 0 };
+std::atomic<long> g_barrier_mismatches{ 0 };
+
+// Fiber stacks.  The deepest a fiber got in the whole of tests/test_thread_orders_emu.py (every kernel with a barrier, the Poseidon and prime-field
+// ones among them), measured as the high-water mark of stacks filled with a pattern: 3944 bytes at -O2 and 32640 bytes with the sources built at
+// -O0, as the sanitizer libraries are.  256 KiB leaves eight times the larger figure for the sanitizers' red zones; only touched pages are ever
+// resident.  Below each stack lies one PROT_NONE guard page, so an overflow faults at once instead of reaching a neighbour.  Stacks are mapped
+// once per OS thread, on first use, and reused by every later launch.
+const size_t STACK_BYTES = 256 * 1024, GUARD_BYTES = 4096;
+
+// The switch between a fiber and the scheduler.  On x86-64 it is twelve instructions of our own (the callee-saved registers, the two floating-point
+// control words and the stack pointer): swapcontext makes a system call for the signal mask at every switch, which tripled the time of a transform
+// under the threaded mode.  Anywhere else, and in the AddressSanitizer builds (which know swapcontext and are told of every switch below), ucontext.
+#if defined(__x86_64__) && !defined(__SANITIZE_ADDRESS__)
+#define EMU_OWN_SWITCH 1
+typedef void *Context;              // the saved stack pointer
+extern "C" void emu_switch(Context *save, Context load);
+asm(R"(
+    .pushsection .text
+    .type emu_switch, @function
+emu_switch:
+    pushq %rbp
+    pushq %rbx
+    pushq %r12
+    pushq %r13
+    pushq %r14
+    pushq %r15
+    subq $8, %rsp
+    stmxcsr (%rsp)
+    fnstcw 4(%rsp)
+    movq %rsp, (%rdi)
+    movq %rsi, %rsp
+    ldmxcsr (%rsp)
+    fldcw 4(%rsp)
+    addq $8, %rsp
+    popq %r15
+    popq %r14
+    popq %r13
+    popq %r12
+    popq %rbx
+    popq %rbp
+    ret
+    .size emu_switch, . - emu_switch
+    .popsection
+)");
+static inline void switch_context(Context *from, Context *to) { emu_switch(from, *to); }
+#else
+typedef ucontext_t Context;
+static inline void switch_context(Context *from, Context *to) { swapcontext(from, to); }
+#endif
+
+struct Fiber {
+    Context ctx;
+    char *stack = nullptr;          // lowest usable byte (the guard page lies below)
+    bool done = true;
+    void *asan_fake = nullptr;
+};
+
+struct Group {
+    std::vector<Fiber *> fibers;    // grows to the largest block seen on this OS thread
+    Context scheduler;
+    const std::function<void()> *body = nullptr;
+    Fiber *current = nullptr;       // the fiber that runs now; null: the scheduler (or no threaded launch at all)
+    const void *sched_stack = nullptr;
+    size_t sched_size = 0;
+    ~Group()
+    {
+        for (Fiber *f : fibers) { munmap(f->stack - GUARD_BYTES, STACK_BYTES + GUARD_BYTES); delete f; }
+    }
+};
+thread_local Group t_group;
+
+#if defined(__SANITIZE_ADDRESS__)
+#define EMU_ASAN_START(save, bottom, size) __sanitizer_start_switch_fiber(save, bottom, size)
+#define EMU_ASAN_FINISH(save, bottom, size) __sanitizer_finish_switch_fiber(save, bottom, size)
+#else
+#define EMU_ASAN_START(save, bottom, size) ((void)0)
+#define EMU_ASAN_FINISH(save, bottom, size) ((void)0)
+#endif
+
+void fiber_main()
+{
+    Group &g = t_group;
+    EMU_ASAN_FINISH(nullptr, &g.sched_stack, &g.sched_size);
+    (*g.body)();
+    Fiber *f = g.current;
+    f->done = true;
+    EMU_ASAN_START(nullptr, g.sched_stack, g.sched_size);       // null: this fiber's frames are dead, its fake stack goes
+    switch_context(&f->ctx, &g.scheduler);
+    abort();                                                    // a finished fiber is never resumed: its context is made anew
+}
+
+void resume(Group &g, Fiber *f)
+{
+    g.current = f;
+    void *fake = nullptr;
+    EMU_ASAN_START(&fake, f->stack, STACK_BYTES);
+    switch_context(&g.scheduler, &f->ctx);
+    EMU_ASAN_FINISH(fake, nullptr, nullptr);
+    (void)fake;
+    g.current = nullptr;
+}
+
+// the first switch to f enters fiber_main on f's stack
+void start_at_fiber_main(Fiber *f)
+{
+#ifdef EMU_OWN_SWITCH
+    // what emu_switch pops, from the saved stack pointer up: the control words of the scheduler, six registers, fiber_main as the return address
+    // (at a multiple of 16, so that fiber_main starts with the alignment of a called function), and a null return address that is never used
+    uint64_t *top = (uint64_t *)(f->stack + STACK_BYTES);
+    top[-1] = 0;
+    top[-2] = (uint64_t)(uintptr_t)&fiber_main;
+    for (int i = 3; i <= 8; ++i) top[-i] = 0;
+    uint32_t *words = (uint32_t *)(top - 9);
+    uint16_t fpcw;
+    asm volatile("stmxcsr %0" : "=m"(words[0]));
+    asm volatile("fnstcw %0" : "=m"(fpcw));
+    words[1] = fpcw;
+    f->ctx = (Context)(top - 9);
+#else
+    getcontext(&f->ctx);
+    f->ctx.uc_stack.ss_sp = f->stack;
+    f->ctx.uc_stack.ss_size = STACK_BYTES;
+    f->ctx.uc_link = nullptr;
+    makecontext(&f->ctx, fiber_main, 0);
+#endif
+}
+
+Fiber *new_fiber()
+{
+    void *m = mmap(nullptr, STACK_BYTES + GUARD_BYTES, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+    if (m == MAP_FAILED || mprotect(m, GUARD_BYTES, PROT_NONE) != 0) { fprintf(stderr, "emu: cannot map a fiber stack\n"); abort(); }
+    Fiber *f = new Fiber;
+    f->stack = (char *)m + GUARD_BYTES;
+    return f;
+}
+
+uint64_t splitmix(uint64_t &x)
+{
+    uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// One workgroup, every thread of it.  Returns false when the fibers did not all meet at the same barriers.
+bool run_group_threaded(dim3 block, int order, uint64_t seed, const std::function<void()> &body)
+{
+    Group &g = t_group;
+    const unsigned n = block.x * block.y * block.z;
+    while (g.fibers.size() < n) g.fibers.push_back(new_fiber());
+    g.body = &body;
+    std::vector<unsigned> turn(n);
+    for (unsigned i = 0; i < n; ++i) turn[i] = order == THREADS_DESC ? n - 1 - i : i;
+    if (order == THREADS_SEEDED)
+        for (unsigned i = n; i > 1; --i) std::swap(turn[i - 1], turn[splitmix(seed) % i]);
+    for (unsigned i = 0; i < n; ++i) {
+        Fiber *f = g.fibers[i];
+        start_at_fiber_main(f);
+        f->done = false;
+    }
+    bool matched = true;
+    for (unsigned live = n; live > 0;) {
+        unsigned finished = 0;
+        for (unsigned i = 0; i < n; ++i) {
+            Fiber *f = g.fibers[turn[i]];
+            if (f->done) continue;
+            const unsigned t = turn[i];
+            threadIdx = dim3(t % block.x, (t / block.x) % block.y, t / (block.x * block.y));
+            resume(g, f);
+            finished += f->done;
+        }
+        // some threads returned while others wait at a barrier (which is also how threads that pass different numbers of barriers end up)
+        if (finished != 0 && finished != live) matched = false;
+        live -= finished;
+    }
+    g.body = nullptr;
+    return matched;
+}
+
+} // namespace
+
+void __syncthreads()
+{
+    Group &g = t_group;
+    Fiber *f = g.current;
+    if (!f) return;                 // one thread per workgroup: it is alone at every barrier
+    EMU_ASAN_START(&f->asan_fake, g.sched_stack, g.sched_size);
+    switch_context(&f->ctx, &g.scheduler);
+    EMU_ASAN_FINISH(f->asan_fake, &g.sched_stack, &g.sched_size);
+}
+
 void emu_launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()> &body)
 {
-    (void)block;
     if (lds_bytes > 160 * 1024) { fprintf(stderr, "emu: LDS request %zu exceeds 160 KiB\n", lds_bytes); abort(); }
+    const int order = g_thread_order.load(), threads = order & 3;
+    const uint64_t seed = g_thread_seed.load();
     gridDim = grid;
-    blockDim = dim3(1, 1, 1);
+    blockDim = threads == THREADS_ONE ? dim3(1, 1, 1) : block;
     threadIdx = dim3(0, 0, 0);
-    for (unsigned z = 0; z < grid.z; ++z)
-        for (unsigned y = 0; y < grid.y; ++y)
-            for (unsigned x = 0; x < grid.x; ++x) {
-                blockIdx = dim3(x, y, z);
-                // poison LDS so that reads of unwritten slots are visible as garbage, not stale data
-                memset(iopx::iopx_smem, 0xA5, lds_bytes);
-                body();
-            }
+    const size_t groups = (size_t)grid.x * grid.y * grid.z;
+    bool matched = true;
+    for (size_t i = 0; i < groups; ++i) {
+        const size_t id = (order & THREADS_GROUPS_DESC) ? groups - 1 - i : i;       // ascending: x fastest, as before
+        blockIdx = dim3((unsigned)(id % grid.x), (unsigned)((id / grid.x) % grid.y), (unsigned)(id / ((size_t)grid.x * grid.y)));
+        // poison LDS so that reads of unwritten slots are visible as garbage, not stale data
+        memset(iopx::iopx_smem, 0xA5, lds_bytes);
+        if (threads == THREADS_ONE) body();
+        else matched = run_group_threaded(block, threads, seed ^ (0xD1B54A32D192ED03ull * (id + 1)), body) && matched;
+    }
+    if (!matched) ++g_barrier_mismatches;
 }
 
 namespace {
@@ -305,6 +516,25 @@ int iopx_emu_set_schedule(int schedule, int late_stream)
     st().late_index = late_stream;
     g_sched.store(schedule);
     return 0;
+}
+
+// Thread order of every launch from now on (see the threaded mode above); returns the order that held before, or -1 for an order that does not
+// exist.  Drains everything first, so a launch already queued runs under the order that held when it was made.
+int iopx_emu_set_threads(int order, uint64_t seed)
+{
+    if (order < 0 || order > 7) return -1;
+    Lock lk(st().mu);
+    drain_all();
+    g_thread_seed.store(seed);
+    return g_thread_order.exchange(order);
+}
+
+// launches since the last call in which the threads of some workgroup did not all meet at the same barriers; clears the count
+long iopx_emu_barrier_mismatches(void)
+{
+    Lock lk(st().mu);
+    drain_all();
+    return g_barrier_mismatches.exchange(0);
 }
 
 // created streams alive (the library's own is the first, its side stream the second)

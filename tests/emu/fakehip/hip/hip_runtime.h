@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY — a single-thread-per-workgroup stand-in for the HIP runtime.
+// TEST INFRASTRUCTURE ONLY — a stand-in for the HIP runtime that runs kernels on the CPU.
 //
 // There is no GPU in the development container, so the CPU test-suite compiles the PRODUCT kernel
 // sources (libiop_amd/csrc/*.hip, unmodified, no #ifdefs in them) with g++ against this header and runs
@@ -7,6 +7,11 @@
 // arithmetic, tile schedules and field arithmetic as the GPU does.  This validates kernel LOGIC before
 // GPU time is spent; it is not shipped, not loaded by libiop_amd, and not a fallback (the product
 // library links the real HIP runtime and fails without a device).
+//
+// That single thread cannot see a missing barrier or two wavefronts that own the same LDS row.  iopx_emu_set_threads (emu_runtime.cpp)
+// switches to the threaded mode: every workgroup runs with the blockDim of its launch, one fiber per thread, each fiber alone up to its next
+// __syncthreads(), in ascending, descending or a seeded order of thread index.  __shared__ is thread_local for it: all fibers of a workgroup
+// run on the OS thread that launches, so a block-scope __shared__ array is storage they share (and it stays off the small fiber stacks).
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -21,18 +26,19 @@
 #define __device__
 #define __host__
 #define __forceinline__ inline __attribute__((always_inline))
-#define __shared__
+#define __shared__ thread_local
 #define __launch_bounds__(...)
 
 struct dim3 {
     unsigned x, y, z;
-    dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
+    constexpr dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}     // constexpr: the thread_local ones below are constant-initialised
 };
 extern thread_local dim3 threadIdx, blockIdx, blockDim, gridDim;
 struct uint4 { unsigned x, y, z, w; };
 static inline uint4 make_uint4(unsigned x, unsigned y, unsigned z, unsigned w) { uint4 v = { x, y, z, w }; return v; }
 
-static inline void __syncthreads() {}
+// threaded mode: the calling fiber yields until every live fiber of its workgroup has arrived; one thread per workgroup: nothing
+void __syncthreads();
 // one thread at a time: a ballot sees the calling lane only
 static inline unsigned long long __ballot(int pred) { return pred ? ~0ull : 0ull; }      // (the emulated thread stands for every lane of its wavefront)
 static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
@@ -133,8 +139,8 @@ hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags);
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b);
 
 // LDS: one static buffer, the size of a CU's LDS
-namespace iopx { extern uint64_t iopx_smem[]; }
-// runs every workgroup of the grid now, on the calling thread
+namespace iopx { extern thread_local uint64_t iopx_smem[]; }
+// runs every workgroup of the grid now, on the calling thread (with one thread each, or in the threaded mode one fiber per thread of `block`)
 void emu_launch(dim3 grid, dim3 block, size_t lds_bytes, const std::function<void()> &body);
 // eager schedule: emu_launch at once; deferred: the closure joins the stream's queue and emu_launch runs it when the stream executes
 void emu_enqueue_launch(hipStream_t stream, dim3 grid, dim3 block, size_t lds_bytes, std::function<void()> body);

@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE ONLY: builds and loads tests/emu/libiopx_emu.so — the product kernel sources compiled
-for the CPU with one thread per workgroup (see tests/emu/fakehip/hip/hip_runtime.h).  Wrapped by the
+for the CPU, by default with one thread per workgroup (see tests/emu/fakehip/hip/hip_runtime.h; tests/thread_order_cases.py for the
+threaded mode).  Wrapped by the
 same ctypes binding class as the product library so the tests call the C ABI exactly as on the GPU."""
 import os
 import subprocess

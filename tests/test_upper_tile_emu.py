@@ -11,6 +11,8 @@ tests/emu/fakehip/hip/hip_runtime.h), so within a workgroup there is one order o
   * between two ownerships every task has finished before the next loop starts, barrier or not: a MISSING barrier does not show here.  The
     barriers sit where upper_own's level pair changes (one place in the source); on the GPU their absence is a race that
     tests/test_gpu_upper_tile.py runs over whole tiles of eight wavefronts.
+The same cases with every thread of the launch, in ascending, descending and seeded order, where a missing barrier and a row that two
+wavefronts share do show: tests/test_thread_orders_emu.py.
 """
 import numpy as np
 import pytest

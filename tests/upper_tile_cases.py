@@ -33,12 +33,54 @@ PINS = {
 SCHEDULE_OPTIONS = {"IOPX_TILE_BITS": 11, "IOPX_P2_COLS": 6, "IOPX_P2_TOP": 4, "IOPX_COMB": 1}
 
 
-def assert_comb_schedule(lib):
+def assert_comb_schedule(lib, options=None):
     """The library exposes no plan, so the tests hold the schedule by its inputs: with any of these options overridden (the environment, an
     earlier test's set_option) the dimensions above would reach other tiles or the general product, and the tests would pass without
-    running k_bfly_upper_comb.  That is a failure here, not a skip."""
+    running k_bfly_upper_comb.  That is a failure here, not a skip.
+    options: the values the case assumes where they are not the defaults (a geometry of GEOMETRIES, set in a child process's environment);
+    the option table answers with the default it is asked with when nothing is set, so a value that was NOT set fails as well."""
     for name, dflt in SCHEDULE_OPTIONS.items():
-        assert lib.get_option(name, dflt) == dflt, "%s is overridden: these shapes no longer reach the comb upper pass" % name
+        want = dflt if options is None else options[name]
+        assert lib.get_option(name, dflt) == want, "%s is not %d: these shapes no longer reach the comb upper pass they are meant for" % (name, want)
+
+
+# The comb upper pass at geometries the defaults never reach (the options are read once per process, so each row runs in a child process with
+# them in its environment).  run_phase2 cuts the pair bits [a_low, d) from the top into tiles of at most A = TILE_BITS - P2_COLS levels, with
+# a_low = min(TILE_BITS, 10) - P2_TOP (phase2_geom) and 2^c columns, c = min(TILE_BITS - levels, a_low); IOPX_P1_COLS stays at 3.
+#   (TILE_BITS, P2_COLS, P2_TOP): dimensions, first dimension with two tiles        tiles (levels, c) per dimension
+GEOMETRIES = {
+    "six-levels": ((12, 6, 4), (12, 13, 16), 13),       # (6,6); (6,6)+(1,6); (6,6)+(4,6): three pairs, 96 KiB, 16 wave tasks on 8 waves (two per wave and pair)
+    "256-columns": ((12, 8, 2), (12, 13, 15), 13),      # (4,8); +(1,8); +(3,8): column chunks (cbits = 2), a one-level tile on 256 columns
+    "mixed-columns": ((11, 6, 3), (12, 13, 14, 15), 13),    # (5,6); +(1,7); +(2,7); +(3,7): two column widths in one transform
+    "one-wave": ((8, 6, 2), (8, 9, 11), 9),             # (2,6); +(1,6); (2,6)+(2,6)+(1,6): one wavefront per workgroup
+    "256-threads": ((10, 6, 4), (11, 13), 11),          # (4,6)+(1,6); (4,6)+(3,6): workgroups of 256 threads
+}
+
+
+def geometry_options(name):
+    (tile, cols, top), _, _ = GEOMETRIES[name]
+    return {"IOPX_TILE_BITS": tile, "IOPX_P2_COLS": cols, "IOPX_P2_TOP": top, "IOPX_COMB": 1}
+
+
+def geometry_env(name):
+    """what a child process needs in its environment to run the geometry `name`"""
+    env = {k: str(v) for k, v in geometry_options(name).items()}
+    env["IOPX_UPPER_GEOMETRY"] = name
+    return env
+
+
+def check_geometry(lib, on_gpu, name):
+    """Per dimension the transform and its inverse on the standard basis and on a random basis with a random shift; at the first dimension with
+    two tiles, cosets (1, 3) of the LDE (the first upper pass reads the shared phase-1 output) and one re-extension batch of 3 over 4 cosets:
+    2^(d + 2) <= 2^15 elements per vector there, so nothing exceeds the 2^16 elements of the largest transform."""
+    _, dims, two_tiles = GEOMETRIES[name]
+    options = geometry_options(name)
+    for d in dims:
+        for kind in ("standard", "random"):
+            check_fft_ifft(lib, d, kind, options=options)
+    for kind in ("standard", "random"):
+        check_lde(lib, on_gpu, two_tiles, kind, 1, 3, options=options)
+    check_reextend(lib, on_gpu, d=two_tiles, options=options)
 
 
 def digest(arr):
@@ -112,8 +154,8 @@ class Mem:
         self.held = {}
 
 
-def check_fft_ifft(lib, d, kind, pinned=False):
-    assert_comb_schedule(lib)
+def check_fft_ifft(lib, d, kind, pinned=False, options=None):
+    assert_comb_schedule(lib, options)
     basis, shift = domain(d, kind)
     got = lib.additive_FFT(coeffs(d), basis[:d], shift)
     if pinned:
@@ -124,10 +166,10 @@ def check_fft_ifft(lib, d, kind, pinned=False):
     assert np.array_equal(lib.additive_IFFT(got, basis[:d], shift), coeffs(d)), ("ifft", d, kind)
 
 
-def check_lde(lib, on_gpu, d, kind, cb, cc, pinned=False):
+def check_lde(lib, on_gpu, d, kind, cb, cc, pinned=False, options=None):
     """Cosets [cb, cb + cc) of the codeword over the whole domain: with more than one coset the first upper pass reads the shared phase-1
     output (src_shared) and writes one copy per coset."""
-    assert_comb_schedule(lib)
+    assert_comb_schedule(lib, options)
     basis, shift = domain(d, kind)
     mem = Mem(lib, on_gpu)
     try:
@@ -143,14 +185,27 @@ def check_lde(lib, on_gpu, d, kind, cb, cc, pinned=False):
         assert np.array_equal(got, ref_cosets(d, kind, cb, cc)), ("lde", d, kind, cb, cc)
 
 
-def check_reextend(lib, on_gpu, d=12, batch=3, cc=4):
-    """`batch` vectors of evaluations over span(basis[:d]) + eval_shift, re-extended onto the four cosets of the whole domain: the batched
-    inverse upper passes (the vectors of a batch in the place of cosets), then the forward ones per polynomial."""
-    assert_comb_schedule(lib)
+@functools.lru_cache(maxsize=None)
+def reextend_refs(d, batch):
+    """(the batch's evaluations over span(basis[:d]) + eval_shift, the oracle's codeword of each polynomial over the whole domain), computed once
+    and shared by every run of check_reextend on (d, batch)"""
     basis, shift = domain(d, "standard")
     eval_shift = rand_elems(800 + d, 1, W)[0]
     polys = [rand_elems(300 + k, 1 << d, W) for k in range(batch)]
     evals = np.concatenate([oracle.additive_fft(p, basis[:d], eval_shift) for p in polys])
+    want = [oracle.additive_fft(p, basis, shift) for p in polys]
+    for a in [evals] + want:
+        a.setflags(write=False)
+    return evals, want
+
+
+def check_reextend(lib, on_gpu, d=12, batch=3, cc=4, options=None):
+    """`batch` vectors of evaluations over span(basis[:d]) + eval_shift, re-extended onto the four cosets of the whole domain: the batched
+    inverse upper passes (the vectors of a batch in the place of cosets), then the forward ones per polynomial."""
+    assert_comb_schedule(lib, options)
+    basis, shift = domain(d, "standard")
+    eval_shift = rand_elems(800 + d, 1, W)[0]
+    evals, want = reextend_refs(d, batch)
     mem = Mem(lib, on_gpu)
     try:
         d_in = mem.up(evals)
@@ -160,4 +215,4 @@ def check_reextend(lib, on_gpu, d=12, batch=3, cc=4):
     finally:
         mem.close()
     for k in range(batch):
-        assert np.array_equal(got[k], oracle.additive_fft(polys[k], basis, shift)), ("reextend", k)
+        assert np.array_equal(got[k], want[k]), ("reextend", k)

@@ -964,38 +964,63 @@ class Library:
             dist.broadcast(uid, src=0)
         return self.comm_create_rccl(rank, world, bytes(uid.cpu().numpy().tobytes()))
 
-    def comm_create_torch_callbacks(self, dist, rank, world):
-        """A communicator whose collectives are forwarded to an initialised torch.distributed group through callbacks on HOST pointers:
-        what the CPU test-suite uses (gloo group, kernels compiled for the CPU).  The returned handle keeps the callbacks alive."""
+    def comm_create_torch_callbacks(self, dist, rank, world, staged=False):
+        """A communicator whose collectives are forwarded to an initialised torch.distributed group through callbacks.  By default the
+        pointers are HOST pointers: what the CPU test-suite uses (gloo group, kernels compiled for the CPU).  staged=True: the pointers
+        are DEVICE pointers and every collective goes through the host — the send buffer is read back with d2h, exchanged over the
+        group's host tensors, and the result written with h2d, both on the library's stream (the stream the callback is handed: the
+        read-back is ordered after the kernels that produced the buffer, the write before those that consume it).  A test vehicle that
+        lets the ranks of a host-memory group share ONE GPU, not a transport.  The returned handle keeps the callbacks alive."""
         import torch
         _i, _vp_, _szt = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
 
-        def view(ptr, nbytes):
-            return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(ptr)))
+        # the only two places that touch the buffers: read() returns a fresh host tensor, write() stores one; a collective reads all it
+        # sends before it writes anything (the library calls all_gather with d_send inside d_recv)
+        if staged:
+            def read(ptr, nbytes):
+                arr = np.empty(nbytes, dtype=np.uint8)
+                self.d2h(arr, ptr)
+                return torch.from_numpy(arr)
+
+            def write(ptr, t):
+                self.h2d(ptr, t.contiguous().numpy())
+        else:
+            def view(ptr, nbytes):
+                return torch.from_numpy(np.ctypeslib.as_array((ctypes.c_uint8 * nbytes).from_address(ptr)))
+
+            def read(ptr, nbytes):
+                return view(ptr, nbytes).clone()
+
+            def write(ptr, t):
+                view(ptr, t.numel()).copy_(t)
 
         def all_gather(user, send, recv, nbytes, stream):
             parts = [torch.empty(nbytes, dtype=torch.uint8) for _ in range(world)]
-            dist.all_gather(parts, view(send, nbytes).clone())
-            view(recv, nbytes * world).copy_(torch.cat(parts))
+            dist.all_gather(parts, read(send, nbytes))
+            write(recv, torch.cat(parts))
             return 0
 
         def all_reduce_u64(user, buf, count, op, stream):
-            t = view(buf, count * 8).view(torch.int64)
+            t = read(buf, count * 8).view(torch.int64)
             if op == 0:
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)                # wrapping int64 sum = wrapping uint64 sum
             else:                                                       # unsigned minimum through the order-preserving map x -> x ^ 2^63
-                flipped = t ^ torch.tensor(-(1 << 63), dtype=torch.int64)
-                dist.all_reduce(flipped, op=dist.ReduceOp.MIN)
-                t.copy_(flipped ^ torch.tensor(-(1 << 63), dtype=torch.int64))
+                t ^= torch.tensor(-(1 << 63), dtype=torch.int64)
+                dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                t ^= torch.tensor(-(1 << 63), dtype=torch.int64)
+            write(buf, t.view(torch.uint8))
             return 0
 
         def broadcast(user, buf, nbytes, root, stream):
-            dist.broadcast(view(buf, nbytes), src=root)
+            t = read(buf, nbytes) if rank == root else torch.empty(nbytes, dtype=torch.uint8)
+            dist.broadcast(t, src=root)
+            if rank != root:
+                write(buf, t)
             return 0
 
         def all_to_all(user, send, recv, nbytes, stream):
             out = [torch.empty(nbytes, dtype=torch.uint8) for _ in range(world)]
-            src = view(send, nbytes * world)
+            src = read(send, nbytes * world)
             ins = [src[q * nbytes:(q + 1) * nbytes].clone() for q in range(world)]
             if dist.get_backend() == "gloo":                            # gloo has no all_to_all for CPU tensors in every build: gather per destination
                 for q in range(world):
@@ -1005,15 +1030,15 @@ class Library:
                         out = got
             else:
                 dist.all_to_all(out, ins)
-            view(recv, nbytes * world).copy_(torch.cat(out))
+            write(recv, torch.cat(out))
             return 0
 
         def sendrecv(user, send, recv, nbytes, peer, stream):
             r = torch.empty(nbytes, dtype=torch.uint8)
-            ops = [dist.P2POp(dist.isend, view(send, nbytes).clone(), peer), dist.P2POp(dist.irecv, r, peer)]
+            ops = [dist.P2POp(dist.isend, read(send, nbytes), peer), dist.P2POp(dist.irecv, r, peer)]
             for w in dist.batch_isend_irecv(ops):
                 w.wait()
-            view(recv, nbytes).copy_(r)
+            write(recv, r)
             return 0
 
         def guard(fn):

@@ -35,7 +35,7 @@ def _bytes(seed, n):
     return np.random.Generator(np.random.PCG64(seed)).integers(0, 256, size=n, dtype=np.uint8)
 
 
-class _Guarded:
+class Guarded:
     """A device buffer of `span` bytes framed by PAD guard bytes; dst(off) is the address `off` bytes into the span."""
 
     def __init__(self, lib, span, seed):
@@ -66,7 +66,7 @@ class _Guarded:
 
 def check_upload(lib, sizes=UPLOAD_SIZES):
     for size in sizes:
-        g = _Guarded(lib, size + 16, size)
+        g = Guarded(lib, size + 16, size)
         try:
             for off in range(16):
                 host = _bytes(1000 * size + off, size)
@@ -84,7 +84,7 @@ def check_upload(lib, sizes=UPLOAD_SIZES):
 def check_upload_back_to_back(lib, count=64):
     """64 uploads of different patterns into distinct buffers before any read-back: a staging chunk is reused only after its copy has completed."""
     sizes = [(1 << 16) + 4099 * k if k % 3 else 100 + 37 * k for k in range(count)]       # staging chunks and kernel-argument uploads, interleaved
-    bufs = [_Guarded(lib, s + 8, 7000 + k) for k, s in enumerate(sizes)]
+    bufs = [Guarded(lib, s + 8, 7000 + k) for k, s in enumerate(sizes)]
     try:
         for k, (s, g) in enumerate(zip(sizes, bufs)):
             host = _bytes(9000 + k, s)
@@ -102,7 +102,7 @@ def check_copy(lib, sizes=COPY_SIZES, offsets=range(16)):
     for size in sizes:
         src = lib.malloc(size + 32)
         data = _bytes(size, size + 32)
-        g = _Guarded(lib, size + 16, size + 1)
+        g = Guarded(lib, size + 16, size + 1)
         try:
             lib.h2d(src, data)
             for so in offsets:
@@ -121,7 +121,7 @@ def check_big_copy(lib, size=BIG_COPY):
     """16-, 8- and 1-byte aligned copies past the 8192-block grid cap."""
     src = lib.malloc(size + 16)
     data = _bytes(77, size + 16)
-    g = _Guarded(lib, size + 16, 78)
+    g = Guarded(lib, size + 16, 78)
     try:
         lib.h2d(src, data)
         for so, do in ((0, 0), (8, 0), (3, 5)):
@@ -135,7 +135,7 @@ def check_big_copy(lib, size=BIG_COPY):
 
 def check_fill(lib, sizes=COPY_SIZES, values=FILL_VALUES):
     for size in sizes:
-        g = _Guarded(lib, size + 16, size + 2)
+        g = Guarded(lib, size + 16, size + 2)
         try:
             for off in range(16):
                 for value in values:

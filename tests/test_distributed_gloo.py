@@ -381,7 +381,7 @@ def test_membership_proof_node_indices_match_oracle():
 
 # ---- the NATIVE provers distributed over the ranks (libiop_amd/cpp/dist.hpp behind iopx_aurora_prove_dist / iopx_fractal_*_dist): the C++
 # prover inside the (CPU-compiled) library, its collectives forwarded to the gloo group through iopx_comm_create_callbacks ----
-def _native_worker(rank, world, port, ret, protocol, field_code, log_n, num_inputs, seed, rs_extra):
+def _native_worker(rank, world, port, ret, protocol, field_code, log_n, num_inputs, seed, rs_extra, staged=False):
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here)
@@ -390,31 +390,13 @@ def _native_worker(rank, world, port, ret, protocol, field_code, log_n, num_inpu
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        import sharded_native_cases as sn
         from emu_lib import emu
         lib = emu()
-        comm = lib.comm_create_torch_callbacks(dist, rank, world)
-        n = 1 << log_n
-        inst = lib.aurora_example_instance(field_code, n, num_inputs, n - 1, seed)
+        comm = lib.comm_create_torch_callbacks(dist, rank, world, staged=staged)
         try:
-            lib.comm_stats(reset=True)
-            if protocol == "fri":                          # log_n = the codeword domain dimension; the seeded polynomial of degree 2^(dim - rs_extra)
-                from libiop_amd import domains, r1cs
-                f = domains.GF192() if field_code == 0 else domains.EdwardsFr()
-                coeffs = np.ascontiguousarray(r1cs.seeded_elements(f, seed, 1 << (log_n - rs_extra)), dtype=np.uint64)
-                d = lib.malloc(coeffs.nbytes)
-                lib.h2d(d, coeffs)
-                t = lib.fri_snark_prove(field_code, d, coeffs.shape[0], log_n, rs_extra, 2, 1, num_inputs, comm=comm)      # num_inputs carries the query repetitions
-                lib.free(d)
-                roots = []
-            elif protocol == "aurora":
-                t = lib.aurora_prove_dist(inst, comm, 128, rs_extra, 2)
-                roots = []
-            else:
-                roots = lib.fractal_index_dist(inst, comm, 128, rs_extra, 2)
-                t = lib.fractal_prove_dist(inst, comm, 128, rs_extra, 2)
-            ret[rank] = (t, roots, lib.comm_stats())
+            ret[rank] = sn.native_prove(lib, comm, protocol, field_code, log_n, num_inputs, seed, rs_extra)
         finally:
-            lib.aurora_instance_free(inst)
             lib.comm_destroy(comm)
     finally:
         dist.destroy_process_group()
@@ -462,20 +444,6 @@ def test_native_sharded_fractal_prover_equals_oracle(world, field_code, log_n, n
             assert ret[r][2][0] <= 20, ret[r][2]                  # 33 before the query phase's collectives were merged into one
 
 
-def _bad_witness_instance(lib, field_code, log_n, k, seed):
-    """The seeded constraint system with one auxiliary variable changed (Az * Bz != Cz): an instance handle built through iopx_aurora_instance_create."""
-    import torch
-    import head_cases as hc
-    from libiop_amd import domains, r1cs
-    field = domains.GF192() if field_code == 0 else domains.EdwardsFr()
-    ops = domains.DeviceOps(lib, torch, torch.device("cpu"), field)
-    n = 1 << log_n
-    cs, primary, auxiliary = r1cs.generate_r1cs_example(ops, n, k, n - 1, seed)
-    z = np.concatenate([np.asarray(primary, dtype=np.uint64).reshape(-1, 3), np.asarray(auxiliary, dtype=np.uint64).reshape(-1, 3)])
-    z[k + 5] = z[k + 6]
-    return lib.aurora_instance(field_code, [hc.csr(ops, M) for M in (cs.A, cs.B, cs.C)], n - 1, k, z)
-
-
 def _bad_witness_worker(rank, world, port, ret, field_code, log_n):
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -485,17 +453,13 @@ def _bad_witness_worker(rank, world, port, ret, field_code, log_n):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
+        import sharded_native_cases as sn
         from emu_lib import emu
         lib = emu()
         comm = lib.comm_create_torch_callbacks(dist, rank, world)
-        inst = _bad_witness_instance(lib, field_code, log_n, 15, 0x2204)
         try:
-            lib.profile_begin()
-            t = lib.aurora_prove_dist(inst, comm, 128, 5, 2)
-            prof = lib.profile_report()
-            ret[rank] = (t, sum(v[0] for k, v in prof.items() if k.startswith("k_ldt_combine")))
+            ret[rank] = sn.bad_witness_prove(lib, comm, field_code, log_n)
         finally:
-            lib.aurora_instance_free(inst)
             lib.comm_destroy(comm)
     finally:
         dist.destroy_process_group()
@@ -508,15 +472,9 @@ def test_native_sharded_unsatisfied_witness_takes_the_reference_schedule_on_ever
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here)
+    import sharded_native_cases as sn
     from emu_lib import emu
-    lib = emu()
-    monkeypatch.setenv("IOPX_HEAD_EVAL", "0")
-    inst = _bad_witness_instance(lib, field_code, log_n, 15, 0x2204)
-    try:
-        expected = lib.aurora_prove(inst)
-    finally:
-        lib.aurora_instance_free(inst)
-    monkeypatch.delenv("IOPX_HEAD_EVAL")
+    expected = sn.bad_witness_expected(emu(), field_code, log_n, monkeypatch.setenv, monkeypatch.delenv)
     mgr = mp.Manager()
     ret = mgr.dict()
     mp.spawn(_bad_witness_worker, args=(world, _free_port(), ret, field_code, log_n), nprocs=world, join=True)
@@ -530,7 +488,10 @@ def test_native_sharded_unsatisfied_witness_takes_the_reference_schedule_on_ever
 P1_SHARD_ENV = {"IOPX_P1_SHARD_MIN_D": "6", "IOPX_TILE_BITS": "5", "IOPX_P1_COLS": "2", "IOPX_P2_COLS": "2", "IOPX_P2_TOP": "2"}
 
 
-def _phase1_worker(rank, world, port, ret):
+P1_SHAPES = ((8, "std"), (9, "general"), (11, "std"), (5, "std"))         # m = 5: below the threshold, stays whole
+
+
+def _phase1_worker(rank, world, port, ret, shapes):
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here)
@@ -539,32 +500,14 @@ def _phase1_worker(rank, world, port, ret):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        import ctypes
-        import oracle
+        import sharded_native_cases as sn
         from emu_lib import emu
-        from helpers import rand_elems
         lib = emu()
         comm = lib.comm_create_torch_callbacks(dist, rank, world)
-        lib.c.iopx_comm_bind_transforms.argtypes = [ctypes.c_void_p]
-        ok, calls = [], []
-        for m, kind in ((8, "std"), (9, "general"), (11, "std"), (5, "std")):         # m = 5: below the threshold, stays whole
-            basis = oracle.standard_basis(m, W) if kind == "std" else rand_elems(70 + m, m, W)
-            shift = rand_elems(71 + m, 1, W)[0]
-            coeffs = rand_elems(72 + m, 1 << m, W)
-            full = oracle.additive_fft(coeffs, basis, shift)
-            lib.comm_stats(reset=True)
-            lib._check(lib.c.iopx_comm_bind_transforms(comm))
-            try:
-                got = lib.additive_FFT(coeffs, basis, shift)
-                back = lib.additive_IFFT(full, basis, shift)
-                short = coeffs[: (1 << (m - 2)) - 3]                                  # a low-degree extension: phase 1 on 2^(m-2) coefficients
-                lde = lib.additive_FFT(short, basis, shift)
-            finally:
-                lib._check(lib.c.iopx_comm_bind_transforms(None))
-            calls.append(lib.comm_stats()[0])
-            ok.append(bool(np.array_equal(got, full) and np.array_equal(back, coeffs) and np.array_equal(lde, oracle.additive_fft(short, basis, shift))))
-        ret[rank] = (ok, calls)
-        lib.comm_destroy(comm)
+        try:
+            ret[rank] = sn.phase1_split(lib, comm, shapes)
+        finally:
+            lib.comm_destroy(comm)
     finally:
         dist.destroy_process_group()
 
@@ -577,9 +520,12 @@ def test_phase1_split_over_the_ranks(world, monkeypatch):
         monkeypatch.setenv(k, v)
     mgr = mp.Manager()
     ret = mgr.dict()
-    mp.spawn(_phase1_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    import sharded_native_cases as sn
+    mp.spawn(_phase1_worker, args=(world, _free_port(), ret, P1_SHAPES), nprocs=world, join=True)
     for r in range(world):
-        ok, calls = ret[r]
+        ok = [one["digests"] == sn.phase1_expected(m, kind) for (m, kind), one in zip(P1_SHAPES, ret[r])]
+        calls = [sum(one["collectives"]) for one in ret[r]]
+        assert len(ret[r]) == len(P1_SHAPES)
         assert ok == [True] * 4, (r, ok)
         assert calls[0] >= 2 and calls[1] >= 2 and calls[2] >= 3 and calls[3] == 0, (r, calls)
 
@@ -624,7 +570,7 @@ def test_native_sharded_fri_snark_equals_oracle(world, field_code, dim):
 
 
 # ---- ONE transform as long as its domain across the ranks, natively (libiop_amd/csrc/fft_add_dist.hip behind iopx_add_[i]fft_gf192_dist_dev) ----
-def _native_fft_worker(rank, world, port, ret):
+def _native_fft_worker(rank, world, port, ret, staged=False):
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sys.path.insert(0, here)
@@ -633,57 +579,14 @@ def _native_fft_worker(rank, world, port, ret):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        import oracle
+        import sharded_native_cases as sn
         from emu_lib import emu
-        from helpers import rand_elems
         lib = emu()
-        comm = lib.comm_create_torch_callbacks(dist, rank, world)
-        ok = []
-        for m, kind in ((6, "std"), (8, "general"), (11, "aurora")):
-            if kind == "std":
-                basis, shift = oracle.standard_basis(m, W), np.zeros(W, dtype=np.uint64)
-            elif kind == "aurora":
-                basis, shift = oracle.standard_basis(m, W), np.array([1 << m, 0, 0], dtype=np.uint64)
-            else:
-                basis, shift = rand_elems(70 + m, m, W), rand_elems(71 + m, 1, W)[0]
-            coeffs = rand_elems(72 + m, 1 << m, W)
-            full = oracle.additive_fft(coeffs, basis, shift)
-            per = (1 << m) // world
-            lo = rank * per
-            d_in, d_out, d_back = lib.malloc(per * 24), lib.malloc(per * 24), lib.malloc(per * 24)
-            try:
-                lib.h2d(d_in, np.ascontiguousarray(coeffs[lo:lo + per]))
-                lib.additive_FFT_dist_dev(comm, d_in, basis, shift, d_out)
-                got = np.empty((per, W), dtype=np.uint64)
-                lib.d2h(got, d_out)
-                ok.append(bool(np.array_equal(got, full[lo:lo + per])))
-                lib.additive_FFT_dist_dev(comm, d_out, basis, shift, d_back, inverse=True)           # back to the coefficients
-                lib.d2h(got, d_back)
-                ok.append(bool(np.array_equal(got, coeffs[lo:lo + per])))
-                evals = rand_elems(73 + m, 1 << m, W)                                               # independent evaluations against the oracle's IFFT
-                lib.h2d(d_in, np.ascontiguousarray(evals[lo:lo + per]))
-                lib.additive_FFT_dist_dev(comm, d_in, basis, shift, d_out, inverse=True)
-                lib.d2h(got, d_out)
-                ok.append(bool(np.array_equal(got, oracle.additive_ifft(evals, basis, shift)[lo:lo + per])))
-            finally:
-                for d in (d_in, d_out, d_back):
-                    lib.free(d)
-        before = lib.comm_stats()[0]
-        if world > 2:                                        # m = 2 log2(world) - 1: nothing to put in a transpose chunk — refused, no collective issued
-            m = 2 * (world.bit_length() - 1) - 1
-            per = max(1, (1 << m) // world)
-            d_a, d_b = lib.malloc(per * 24), lib.malloc(per * 24)
-            for inverse in (False, True):
-                try:
-                    lib.additive_FFT_dist_dev(comm, d_a, oracle.standard_basis(m, W), np.zeros(W, dtype=np.uint64), d_b, inverse=inverse)
-                    ok.append(False)
-                except ValueError:
-                    ok.append(True)
-            lib.free(d_a)
-            lib.free(d_b)
-            ok.append(lib.comm_stats()[0] == before)
-        ret[rank] = (ok, before)
-        lib.comm_destroy(comm)
+        comm = lib.comm_create_torch_callbacks(dist, rank, world, staged=staged)
+        try:
+            ret[rank] = sn.native_fft(lib, comm, rank, world)
+        finally:
+            lib.comm_destroy(comm)
     finally:
         dist.destroy_process_group()
 
@@ -694,7 +597,35 @@ def test_native_distributed_full_size_fft(world):
     transform, cross-block butterflies — equal to the oracle's single-process transform on every rank."""
     mgr = mp.Manager()
     ret = mgr.dict()
+    import sharded_native_cases as sn
     mp.spawn(_native_fft_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
     for r in range(world):
-        assert ret[r][0] == [True] * (9 if world == 2 else 12), (r, ret[r])
-        assert ret[r][1] > 0
+        assert sn.native_fft_verdicts(ret[r], r, world) == [True] * (9 if world == 2 else 12), (r, ret[r])
+        assert ret[r]["collectives"] > 0
+
+
+# ---- the staged form of the callback communicator (comm_create_torch_callbacks(staged=True): every buffer crosses iopx_memcpy_d2h / _h2d on the
+# library's stream — what lets N ranks share one GPU in tests/test_gpu_ranks_one_device.py), here over the CPU-compiled library ----
+def test_staged_callbacks_distributed_full_size_fft():
+    import sharded_native_cases as sn
+    world = 4
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_native_fft_worker, args=(world, _free_port(), ret, True), nprocs=world, join=True)
+    for r in range(world):
+        assert sn.native_fft_verdicts(ret[r], r, world) == [True] * 12, (r, ret[r])
+        assert ret[r]["collectives"] > 0
+
+
+@pytest.mark.parametrize("world,protocol,field_code,log_n,num_inputs,seed,rs_extra", [(2, "aurora", 1, 9, 15, 0x2204, 5), (4, "fractal", 0, 7, 15, 0x2205, 3)])
+def test_staged_callbacks_provers_equal_oracle(world, protocol, field_code, log_n, num_inputs, seed, rs_extra):
+    """All five collectives through the staged reads and writes: all-to-all + interleave (prime field), all-gather inside its own receive
+    buffer, all-reduce of the query arena, broadcast, peer exchanges."""
+    import sharded_native_cases as sn
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_native_worker, args=(world, _free_port(), ret, protocol, field_code, log_n, num_inputs, seed, rs_extra, True), nprocs=world, join=True)
+    ref, ref_roots = sn.prove_expected(protocol, field_code, log_n, num_inputs, seed, rs_extra)
+    for r in range(world):
+        assert ret[r][0] == ref and ret[r][1] == ref_roots, "rank %d" % r
+        assert ret[r][2][0] > 0

@@ -3,14 +3,13 @@ over the HEAD of the codeword domain only (default) and over the whole domain as
 oracle prover's bytes; an instance whose virtual oracles are not polynomials (an unsatisfied witness) is detected on the confirmation window
 and proved by the reference's schedule, so its (rejected) transcript is still the reference's.  Kernel sources compiled for the CPU
 (tests/emu); the same cases run on the MI355X in tests/test_gpu_head_eval.py."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import emu_lib
 import head_cases as hc
+import layout_cases as lc
 from libiop_amd import domains, r1cs
 
 CPU = torch.device("cpu")
@@ -67,44 +66,10 @@ def test_instance_create_argument_checks():
 
 @pytest.mark.parametrize("count,stride,words", [(1, 1, 3), (100, 8, 3), (4096, 3, 3), (257, 16, 1)])
 def test_gather_stride(count, stride, words):
-    lib = emu_lib.emu()
-    src = np.random.default_rng(count).integers(0, 2**63, size=(count * stride + 5, words), dtype=np.uint64)
-    d_src, d_dst = lib.malloc(src.nbytes), lib.malloc(count * words * 8)
-    lib.h2d(d_src, src)
-    lib.c.iopx_gather_stride_dev.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
-    lib._check(lib.c.iopx_gather_stride_dev(d_src, count, stride, words * 8, d_dst))
-    out = np.empty((count, words), dtype=np.uint64)
-    lib.d2h(out, d_dst)
-    assert np.array_equal(out, src[:count * stride:stride])
-    with pytest.raises(ValueError):
-        lib._check(lib.c.iopx_gather_stride_dev(d_src, count, 0, words * 8, d_dst))
-    with pytest.raises(ValueError):
-        lib._check(lib.c.iopx_gather_stride_dev(d_src, count, stride, 12, d_dst))
-    lib.free(d_src)
-    lib.free(d_dst)
+    """Through the shared cases (tests/layout_cases.py; more strides and the size past the grid cap: tests/test_layout_kernels_emu.py)."""
+    lc.check_gather_stride(emu_lib.emu(), count, stride, words)
 
 
 def test_count_mismatch():
-    lib = emu_lib.emu()
-    a = np.random.default_rng(3).integers(0, 2**63, size=(5000, 3), dtype=np.uint64)
-    b = a.copy()
-    b[17, 1] ^= np.uint64(1)
-    b[4999, 2] ^= np.uint64(1 << 40)
-    b[4999, 0] ^= np.uint64(2)
-    d_a, d_b, d_n = lib.malloc(a.nbytes), lib.malloc(b.nbytes), lib.malloc(8)
-    lib.h2d(d_a, a)
-    lib.h2d(d_b, b)
-    lib.h2d(d_n, np.zeros(1, dtype=np.uint64))
-    lib.c.iopx_count_mismatch_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib._check(lib.c.iopx_count_mismatch_dev(d_a, d_a, a.nbytes, d_n))
-    n = np.empty(1, dtype=np.uint64)
-    lib.d2h(n, d_n)
-    assert n[0] == 0
-    lib._check(lib.c.iopx_count_mismatch_dev(d_a, d_b, a.nbytes, d_n))
-    lib._check(lib.c.iopx_count_mismatch_dev(d_a, d_b, a.nbytes, d_n))        # accumulates
-    lib.d2h(n, d_n)
-    assert n[0] == 6
-    with pytest.raises(ValueError):
-        lib._check(lib.c.iopx_count_mismatch_dev(d_a, d_b, 12, d_n))
-    for d in (d_a, d_b, d_n):
-        lib.free(d)
+    lc.check_count_mismatch(emu_lib.emu(), 15000, [], 1)                                              # equal buffers: zero
+    lc.check_count_mismatch(emu_lib.emu(), 15000, [17 * 3 + 1, 4999 * 3 + 2, 4999 * 3], 2)            # three words differ, two calls accumulate; 12 bytes refused

@@ -45,51 +45,10 @@ def test_reextend_equals_ifft_then_fft(m, d, batch):
 
 # ---- the small device helpers of the multi-GPU layer (include/libiop_amd.h "multi-GPU"; libiop_amd/csrc/comm.hip) ----
 def test_interleave_and_gather_rows():
-    import ctypes
-    import numpy as np
-    lib = emu()
-    rng = np.random.default_rng(3)
-    parts, count = 4, 37
-    src = rng.integers(0, 2**63, size=(parts, count, 3), dtype=np.uint64)          # rank-major residue classes
-    d_src, d_dst = lib.malloc(src.nbytes), lib.malloc(src.nbytes)
-    try:
-        lib.h2d(d_src, src)
-        lib.c.iopx_interleave_dev.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
-        lib._check(lib.c.iopx_interleave_dev(d_src, parts, count, 24, d_dst))
-        out = np.empty((count * parts, 3), dtype=np.uint64)
-        lib.d2h(out, d_dst)
-        assert np.array_equal(out, src.transpose(1, 0, 2).reshape(-1, 3))            # element i * parts + r = class r's entry i
-        with pytest.raises(ValueError):
-            lib._check(lib.c.iopx_interleave_dev(d_src, parts, count, 24, d_src))    # in place is refused
-        with pytest.raises(ValueError):
-            lib._check(lib.c.iopx_interleave_dev(d_src, parts, count, 12, d_dst))    # element size must be a multiple of 8
-    finally:
-        lib.free(d_src); lib.free(d_dst)
-    # gather_rows: out[dst_row[i]][k] = srcs[k][src_index[i]], other rows untouched (zero)
-    n, num, rows = 50, 3, 9
-    srcs = [rng.integers(0, 2**63, size=(n, 4), dtype=np.uint64) for _ in range(num)]     # 32-byte elements (digests)
-    d_srcs = [lib.malloc(a.nbytes) for a in srcs]
-    d_out = lib.malloc(rows * num * 32)
-    try:
-        for d, a in zip(d_srcs, srcs):
-            lib.h2d(d, a)
-        lib.h2d(d_out, np.zeros((rows, num, 4), dtype=np.uint64))
-        src_index = np.array([49, 0, 7, 7], dtype=np.uint64)
-        dst_row = np.array([8, 2, 0, 5], dtype=np.uint64)
-        ptrs = (ctypes.c_void_p * num)(*d_srcs)
-        lib.c.iopx_gather_rows_dev.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        lib._check(lib.c.iopx_gather_rows_dev(ptrs, num, 32, src_index.ctypes.data, dst_row.ctypes.data, len(src_index), d_out))
-        out = np.empty((rows, num, 4), dtype=np.uint64)
-        lib.d2h(out, d_out)
-        want = np.zeros_like(out)
-        for i, r in zip(src_index, dst_row):
-            for k in range(num):
-                want[int(r), k] = srcs[k][int(i)]
-        assert np.array_equal(out, want)
-    finally:
-        for d in d_srcs:
-            lib.free(d)
-        lib.free(d_out)
+    """At the shapes this test always had, through the shared cases (tests/layout_cases.py; every other shape: tests/test_layout_kernels_emu.py)."""
+    import layout_cases as lc
+    lc.check_interleave(emu(), 4, 37, 3)                                             # with the in-place and element-size refusals
+    lc.check_gather_rows(emu(), 3, 4, 50, 9, 4, explicit=([49, 0, 7, 7], [8, 2, 0, 5]))    # 32-byte elements (digests); other rows untouched
 
 
 def test_communicator_argument_checks():

@@ -573,6 +573,15 @@ int iopx_get_option(const char *name, int dflt);
  * iopx_aurora_instance_warm / iopx_fractal_index the first proof adds (nearly) nothing to it. */
 int iopx_cold_stats(char *buf, size_t cap, int reset);
 int iopx_cold_add(const char *label, double ms);
+/* Memory-check mode: a TEST VEHICLE, off by default.  While the option IOPX_MEM_CHECK is non-zero, every device block the library hands out
+ * (per-call temporaries, iopx_pool_alloc, the plans' own buffers, iopx_malloc; not the deferred read-back arena) is  front guard | payload of
+ * exactly the requested bytes | back guard : guards of at least 4096 bytes filled with a pattern byte, the payload filled with the byte
+ * IOPX_MEM_CHECK_POISON (default 0xA5), both on the active stream before any use.  The release of such a block (iopx_pool_free, iopx_free,
+ * the end of the call that owned a temporary) waits for the stream that is active at the release (the pool's own contract: a block is released in the order of the stream it was used on), reads the guards back and counts a damaged block instead of failing.
+ * The option is looked up when a block is handed out; a block keeps its layout until it is released.  iopx_mem_check_stats: the blocks
+ * checked and the damaged ones since the last reset, and the first damaged one as text in first[0..cap) — "<allocator> block of <n> bytes:
+ * <front|back> guard damaged, first at payload offset <k>" (k < 0 in front of the payload, k >= n behind it). */
+int iopx_mem_check_stats(uint64_t *checked, uint64_t *violations, char *first, size_t cap, int reset);
 int iopx_profile_begin(void);
 int iopx_profile_report(char *buf, size_t cap);
 

@@ -74,6 +74,7 @@ EXPORTED_SYMBOLS = [
     "iopx_add_fft_gf64_dev", "iopx_add_fft_gf64", "iopx_add_lde_gf64_dev", "iopx_add_ifft_gf64_dev", "iopx_add_ifft_gf64",
     "iopx_fri_fold_add_gf64_dev", "iopx_fri_fold_add_gf64", "iopx_fri_domains_gf64", "iopx_ldt_combine_gf64_dev",
     "iopx_gf64_mul_dev", "iopx_gf64_inv_dev", "iopx_gf64_host_mul", "iopx_gf64_inverse_host",
+    "iopx_mem_check_stats",
 ]
 
 
@@ -1663,6 +1664,15 @@ class Library:
             f = line.split()
             out[f[0]] = (int(f[1]), float(f[2]))
         return out
+
+    def mem_check_stats(self, reset=False):
+        """(blocks checked at their release, blocks whose guards were damaged, the first damaged one as text) of the memory-check mode
+        (option IOPX_MEM_CHECK, a test vehicle: include/libiop_amd.h) since the last reset."""
+        checked, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        buf = ctypes.create_string_buffer(512)
+        self.c.iopx_mem_check_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_char_p, _sz, ctypes.c_int]
+        self._check(self.c.iopx_mem_check_stats(ctypes.byref(checked), ctypes.byref(bad), buf, len(buf), 1 if reset else 0))
+        return int(checked.value), int(bad.value), buf.value.decode()
 
     def profile_begin(self):
         self._check(self.c.iopx_profile_begin())

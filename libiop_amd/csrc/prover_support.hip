@@ -142,7 +142,7 @@ int iopx_pool_alloc(void **dptr, size_t bytes)
     if (rc != IOPX_OK) return rc;
     if (!dptr) return fail(IOPX_ERR_INVALID_ARGUMENT, "iopx_pool_alloc: null out pointer");
     size_t cap = 0;
-    void *p = tmp_alloc(bytes ? bytes : 8, &cap);
+    void *p = tmp_alloc(bytes ? bytes : 8, &cap, "iopx_pool_alloc");
     if (!p) return fail(IOPX_ERR_RUNTIME, "device allocation of %zu bytes failed", bytes);
     { std::lock_guard<std::mutex> lk(g_pool_mu); g_pool_caps[p] = cap; }
     *dptr = p;

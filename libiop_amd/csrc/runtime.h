@@ -44,6 +44,12 @@ static inline hipError_t copy_d2h(void *dst, const void *src, size_t bytes, hipS
     return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s);
 }
 
+// Memory-check mode (runtime.hip, option IOPX_MEM_CHECK; a test vehicle): a block between two guards with a poisoned payload, and its
+// release, which checks the guards.  mem_check_free returns false for a block the mode did not hand out (always, when it was never on).
+bool mem_check_enabled();
+void *mem_check_malloc(size_t bytes, const char *who);
+bool mem_check_free(void *p);
+
 // Device buffer owned by a plan / a call (freed in the destructor, stream-ordered use only).
 struct DevBuf {
     void *p = nullptr;
@@ -56,6 +62,12 @@ struct DevBuf {
     {
         release();
         if (n == 0) n = 8;
+        if (mem_check_enabled()) {
+            p = mem_check_malloc(n, "DevBuf");
+            if (!p) return fail(IOPX_ERR_RUNTIME, "hipMalloc(%zu) failed", n);
+            bytes = n;
+            return IOPX_OK;
+        }
         hipError_t e = hipMalloc(&p, n);
         if (e != hipSuccess) { p = nullptr; return fail(IOPX_ERR_RUNTIME, "hipMalloc(%zu) failed: %s", n, hipGetErrorString(e)); }
         bytes = n;
@@ -63,7 +75,7 @@ struct DevBuf {
     }
     void release()
     {
-        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        if (p) { if (!mem_check_free(p)) (void)hipFree(p); p = nullptr; bytes = 0; }
     }
     uint64_t *u64() const { return (uint64_t *)p; }
 };
@@ -84,7 +96,7 @@ int defer_downloads_end();
 // temporary released by one call may be handed to a later call without any synchronisation: the later call's
 // kernels run after the earlier call's kernels on that stream.  Blocks are cached in a free list (runtime.hip)
 // and returned to HIP by iopx_clear_plans(); iopx_set_stream() synchronises before switching streams.
-void *tmp_alloc(size_t bytes, size_t *cap);
+void *tmp_alloc(size_t bytes, size_t *cap, const char *who = "tmp_alloc");
 void tmp_free(void *p, size_t cap);
 void tmp_trim();
 

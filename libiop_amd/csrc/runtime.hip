@@ -56,7 +56,7 @@ static inline hipStream_t active_stream() { return g_cur_side >= 0 ? g_side_stre
 
 // cached device temporaries (single-stream reuse, see runtime.h): the free list, and what was freed while a side stream was current — reusable
 // once the main stream has joined it
-struct TmpBlock { void *p; size_t cap; };
+struct TmpBlock { void *p; size_t cap; bool guarded; };      // guarded: laid out by the memory-check mode (below), p is the block's base
 static std::vector<TmpBlock> g_tmp_free;
 static std::mutex g_tmp_mu;
 static std::vector<TmpBlock> g_tmp_quarantine[IOPX_SIDE_STREAMS];
@@ -127,26 +127,131 @@ int set_stream(void *s, bool own)
     return IOPX_OK;
 }
 
-// ---- cached device temporaries: allocation (the lists are declared with the streams above) ----------
+// ---- memory-check mode (IOPX_MEM_CHECK, a test vehicle: tests/memory_contract_cases.py) ---------------------------------------------
+// A block handed out while the option is on is  front guard | payload of exactly the requested bytes | back guard  inside ONE allocation:
+// the front guard is MC_GUARD bytes (a multiple of 256, so the payload keeps hipMalloc's alignment), the back guard starts at the payload's
+// last byte + 1, is at least MC_GUARD bytes and runs to the end of the allocation, a recycled block's slack included.  Both guards are filled
+// with MC_PATTERN and the payload with the poison byte (IOPX_MEM_CHECK_POISON, default 0xA5) by k_fill_bytes on the active stream, in stream
+// order before any use.  At release the host waits for the active stream, reads both guards back and compares; damage is counted and the
+// first case kept as text (iopx_mem_check_stats) — never an error return, destructors release blocks.  A block keeps the layout it was
+// handed out with: the live ones are in g_mc_live by payload address, and the pool recycles a guarded block only as a guarded block.
+// The mode's own read-backs bypass the transfer counters (iopx_transfer_stats counts the prover's bytes, not the checker's).
+static const size_t MC_GUARD = 4096;
+static const uint8_t MC_PATTERN = 0xC3;
+struct McLive { void *base; size_t cap, bytes; const char *who; };
+// (never destroyed: plan caches of other translation units release their buffers from static destructors, in an unspecified order)
+static std::mutex &g_mc_mu = *new std::mutex;
+static std::map<void *, McLive> &g_mc_live = *new std::map<void *, McLive>;          // payload address -> its block
+static std::atomic<size_t> g_mc_live_count{0};      // what a release looks at first: zero whenever the mode has not been used
+static uint64_t g_mc_checked = 0, g_mc_violations = 0;
+static std::string &g_mc_first = *new std::string;
 
-void *tmp_alloc(size_t bytes, size_t *cap)
+static inline bool mc_on() { return opt("IOPX_MEM_CHECK", 0) != 0; }
+static inline size_t mc_raw_bytes(size_t bytes) { return (bytes + 2 * MC_GUARD + 255) & ~(size_t)255; }
+
+// fills the guards and the payload of [base, base + cap) on the active stream and registers the block; returns the payload address
+static void *mc_hand_out(void *base, size_t cap, size_t bytes, const char *who)
 {
+    uint8_t *b = (uint8_t *)base;
+    const int poison = opt("IOPX_MEM_CHECK_POISON", 0xA5) & 0xFF;
+    (void)fill_bytes(b, MC_PATTERN, MC_GUARD);
+    (void)fill_bytes(b + MC_GUARD, poison, bytes);
+    (void)fill_bytes(b + MC_GUARD + bytes, MC_PATTERN, cap - MC_GUARD - bytes);
+    std::lock_guard<std::mutex> lk(g_mc_mu);
+    g_mc_live[b + MC_GUARD] = { base, cap, bytes, who };
+    g_mc_live_count = g_mc_live.size();
+    return b + MC_GUARD;
+}
+
+// the release half: false when p is not a guarded block; otherwise the block's guards have been checked and *out holds its base and capacity
+static bool mc_take_back(void *p, McLive *out)
+{
+    if (g_mc_live_count.load() == 0) return false;
+    McLive b;
+    {
+        std::lock_guard<std::mutex> lk(g_mc_mu);
+        auto it = g_mc_live.find(p);
+        if (it == g_mc_live.end()) return false;
+        b = it->second;
+        g_mc_live.erase(it);
+        g_mc_live_count = g_mc_live.size();
+    }
+    const hipStream_t s = stream();                 // the stream active NOW (the pool's contract: a block is released in the order of the stream that used it): the side stream inside a section
+    const size_t back = b.cap - MC_GUARD - b.bytes;
+    std::vector<uint8_t> host(MC_GUARD + back);
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), b.base, MC_GUARD, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data() + MC_GUARD, (uint8_t *)p + b.bytes, back, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    long long bad = -1;
+    if (e == hipSuccess) for (size_t i = 0; i < host.size(); ++i) if (host[i] != MC_PATTERN) { bad = (long long)i; break; }
+    {
+        std::lock_guard<std::mutex> lk(g_mc_mu);
+        g_mc_checked += 1;
+        if (e != hipSuccess || bad >= 0) {
+            g_mc_violations += 1;
+            if (g_mc_first.empty()) {
+                char line[256];
+                if (e != hipSuccess) snprintf(line, sizeof(line), "%s block of %zu bytes: guards unreadable (%s)", b.who, b.bytes, hipGetErrorString(e));
+                else {
+                    const bool front = (size_t)bad < MC_GUARD;
+                    const long long off = front ? bad - (long long)MC_GUARD : (long long)b.bytes + (bad - (long long)MC_GUARD);
+                    snprintf(line, sizeof(line), "%s block of %zu bytes: %s guard damaged, first at payload offset %lld", b.who, b.bytes, front ? "front" : "back", off);
+                }
+                g_mc_first = line;
+            }
+        }
+    }
+    *out = b;
+    return true;
+}
+
+void *mem_check_malloc(size_t bytes, const char *who)
+{
+    void *base = nullptr;
+    const size_t cap = mc_raw_bytes(bytes);
+    if (hipMalloc(&base, cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return mc_hand_out(base, cap, bytes, who);
+}
+
+bool mem_check_free(void *p)
+{
+    McLive b;
+    if (!mc_take_back(p, &b)) return false;
+    (void)hipFree(b.base);
+    return true;
+}
+
+bool mem_check_enabled() { return mc_on(); }
+
+// ---- cached device temporaries: allocation (the lists are declared with the streams above) ----------
+// With the memory-check mode on, the request grows by the two guards and only guarded blocks are recycled (the size-match rule then
+// applies to the payload capacity, cap - 2 MC_GUARD); with it off only plain ones are, and nothing else differs from the plain path.
+
+void *tmp_alloc(size_t bytes, size_t *cap, const char *who)
+{
+    const bool guarded = mc_on();
+    const size_t extra = guarded ? 2 * MC_GUARD : 0;
+    void *reuse = nullptr;
     {
         std::lock_guard<std::mutex> lk(g_tmp_mu);
         int best = -1;
         for (size_t i = 0; i < g_tmp_free.size(); ++i) {
-            const size_t c = g_tmp_free[i].cap;
-            if (c >= bytes && c <= 2 * bytes + (1u << 20) && (best < 0 || c < g_tmp_free[best].cap)) best = (int)i;
+            if (g_tmp_free[i].guarded != guarded) continue;
+            const size_t c = g_tmp_free[i].cap - extra;
+            if (c >= bytes && c <= 2 * bytes + (1u << 20) && (best < 0 || g_tmp_free[i].cap < g_tmp_free[best].cap)) best = (int)i;
         }
         if (best >= 0) {
             TmpBlock b = g_tmp_free[best];
             g_tmp_free.erase(g_tmp_free.begin() + best);
             *cap = b.cap;
-            return b.p;
+            if (!guarded) return b.p;
+            reuse = b.p;
         }
     }
+    if (reuse) return mc_hand_out(reuse, *cap, bytes, who);
     void *p = nullptr;
-    const size_t c = (bytes + 255) & ~(size_t)255;
+    const size_t c = (bytes + extra + 255) & ~(size_t)255;
     ColdScope cold_("hipMalloc (pool growth)");
     if (hipMalloc(&p, c) != hipSuccess) {
         // out of memory: drop the cache (after draining the streams: quarantined blocks become droppable too) and retry once
@@ -163,13 +268,15 @@ void *tmp_alloc(size_t bytes, size_t *cap)
         if (hipMalloc(&p, c) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     }
     *cap = c;
-    return p;
+    return guarded ? mc_hand_out(p, c, bytes, who) : p;
 }
 
 void tmp_free(void *p, size_t cap)
 {
+    McLive g;
+    const bool guarded = mc_take_back(p, &g);        // waits for the active stream and checks the guards; the block is recycled as usual
     std::lock_guard<std::mutex> lk(g_tmp_mu);
-    (g_cur_side >= 0 ? g_tmp_quarantine[g_cur_side] : g_tmp_free).push_back({p, cap});
+    (g_cur_side >= 0 ? g_tmp_quarantine[g_cur_side] : g_tmp_free).push_back(guarded ? TmpBlock{g.base, g.cap, true} : TmpBlock{p, cap, false});
 }
 
 int side_stream_fork(int k)
@@ -633,6 +740,21 @@ int iopx_cold_stats(char *buf, size_t cap, int reset)
 }
 int iopx_cold_add(const char *label, double ms) { if (label) iopx::cold_add(label, ms); return IOPX_OK; }
 
+// the memory-check mode's findings since the last reset: guarded blocks checked at their release, those found damaged, the first one as text
+int iopx_mem_check_stats(uint64_t *checked, uint64_t *violations, char *first, size_t cap, int reset)
+{
+    std::lock_guard<std::mutex> lk(iopx::g_mc_mu);
+    if (checked) *checked = iopx::g_mc_checked;
+    if (violations) *violations = iopx::g_mc_violations;
+    if (first && cap) {
+        const size_t n = iopx::g_mc_first.size() < cap - 1 ? iopx::g_mc_first.size() : cap - 1;
+        memcpy(first, iopx::g_mc_first.data(), n);
+        first[n] = 0;
+    }
+    if (reset) { iopx::g_mc_checked = iopx::g_mc_violations = 0; iopx::g_mc_first.clear(); }
+    return IOPX_OK;
+}
+
 int iopx_set_option(const char *name, int value)
 {
     if (!name || !*name) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "iopx_set_option: empty name");
@@ -720,6 +842,11 @@ int iopx_malloc(void **dptr, size_t bytes)
     int rc = iopx::ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!dptr) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "iopx_malloc: null out pointer");
+    if (iopx::mem_check_enabled()) {
+        *dptr = iopx::mem_check_malloc(bytes ? bytes : 8, "iopx_malloc");
+        if (!*dptr) return iopx::fail(IOPX_ERR_RUNTIME, "device allocation of %zu bytes failed", bytes);
+        return IOPX_OK;
+    }
     IOPX_HIP(hipMalloc(dptr, bytes ? bytes : 8));
     return IOPX_OK;
 }
@@ -729,6 +856,7 @@ int iopx_free(void *dptr)
     if (!dptr) return IOPX_OK;
     int rc = iopx::ensure_device();
     if (rc != IOPX_OK) return rc;
+    if (iopx::mem_check_free(dptr)) return IOPX_OK;
     IOPX_HIP(hipFree(dptr));
     return IOPX_OK;
 }

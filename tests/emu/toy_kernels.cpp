@@ -3,6 +3,7 @@
 // right bytes and which must not.  Neighbour indices are clamped, not wrapped, so that every dependence points one way in thread index: with a
 // wrap, thread 0 would depend on thread n - 1 and both orders would see the missing barrier of either direction.
 #include <hip/hip_runtime.h>
+#include "../../libiop_amd/csrc/runtime.h"
 
 // (namespace iopx: the block-scope `extern __shared__ ... iopx_smem[]` names the enclosing namespace's variable, as in the product sources)
 namespace iopx {
@@ -96,4 +97,21 @@ extern "C" int iopx_emu_toy(int which, int barrier, int n, uint64_t *out)
     }
     (void)hipDeviceSynchronize();
     return 0;
+}
+
+// The memory-check mode's self-check (tests/memory_contract_cases.py check_checker_checks_itself): a TmpBuf of n bytes and, as asked, a write
+// of n + 8 bytes into it (what = 0), a write of 8 bytes in front of it (1) or a read of its first word, which nobody wrote (2, into *word).
+// Both writes stay inside the block's own guards, so the entry refuses to run with the mode off.  The guards are checked when the TmpBuf
+// goes out of scope.
+extern "C" int iopx_emu_mem_check_toy(int what, size_t n, uint64_t *word)
+{
+    int rc = iopx::ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!iopx::mem_check_enabled() || n < 8 || what < 0 || what > 2) return -1;
+    iopx::TmpBuf t;
+    if ((rc = t.alloc(n)) != IOPX_OK) return rc;
+    uint8_t *p = (uint8_t *)t.p;
+    if (what == 0) return iopx::fill_bytes(p, 0x11, n + 8);
+    if (what == 1) return iopx::fill_bytes(p - 8, 0x11, 8);
+    return word ? iopx::download(word, p, 8) : -1;
 }

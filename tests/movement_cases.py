@@ -36,11 +36,11 @@ def _bytes(seed, n):
 
 
 class Guarded:
-    """A device buffer of `span` bytes framed by PAD guard bytes; dst(off) is the address `off` bytes into the span."""
+    """A device buffer of `span` bytes framed by `pad` (default PAD) guard bytes on each side; dst(off) is the address `off` bytes into the span."""
 
-    def __init__(self, lib, span, seed):
-        self.lib, self.span = lib, span
-        self.total = span + 2 * PAD
+    def __init__(self, lib, span, seed, pad=PAD):
+        self.lib, self.span, self.pad = lib, span, pad
+        self.total = span + 2 * pad
         self.d = lib.malloc(self.total)
         self.image = _bytes(seed, self.total)       # what the whole allocation should hold: guard pattern, then the expected writes
         self.reset()
@@ -49,16 +49,16 @@ class Guarded:
         self.lib.h2d(self.d, self.image)
 
     def dst(self, off):
-        return self.d + PAD + off
+        return self.d + self.pad + off
 
     def expect(self, off, data):
-        self.image[PAD + off:PAD + off + len(data)] = data
+        self.image[self.pad + off:self.pad + off + len(data)] = data
 
     def check(self, what):
         got = np.empty(self.total, dtype=np.uint8)
         self.lib.d2h(got, self.d)
         bad = np.flatnonzero(got != self.image)
-        assert bad.size == 0, "%s: %d bytes differ, the first at byte %d of the span" % (what, bad.size, bad[0] - PAD)
+        assert bad.size == 0, "%s: %d bytes differ, the first at byte %d of the span" % (what, bad.size, bad[0] - self.pad)
 
     def free(self):
         self.lib.free(self.d)

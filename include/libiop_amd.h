@@ -284,6 +284,35 @@ int iopx_gf64_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out,
 int iopx_gf64_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
 int iopx_gf64_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out);
+/* The protocol-layer steps of the encoded Aurora prover over gf64 (libiop_amd/csrc/gf64_ops.hip).  Each entry takes the argument list of
+ * its _gf192 twin further down with one word per element, makes the same argument checks with the same messages and cites the same
+ * reference lines: the synthetic-instance helpers and f_w' = z - f_1v (r1cs_examples.tcc:40-64), the powers of alpha
+ * (basic_lincheck_aux.tcc:37-45), random_linear_combination_oracle (random_linear_combination.tcc:27-57; at most 16 oracles) and its affine
+ * form (holographic_lincheck_aux.tcc:117-143), the CSR products (r1cs.tcc:236-268, basic_lincheck_aux.tcc:64-88), multi_lincheck_virtual_oracle
+ * (basic_lincheck_aux.tcc:102-144; at most 8 matrices), rowcheck_ABC_virtual_oracle (rowcheck.tcc:16-88), fz_virtual_oracle
+ * (r1cs_rs_iop.tcc:181-222), sumcheck_g_oracle (sumcheck.tcc:58-119; a zero domain element inverts to zero, utils.tcc:79-97) and
+ * polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371).  Codeword domains of dimension above 40 are refused.
+ * iopx_gf64_mul_dev and iopx_gf64_inv_dev above are the products and inverses.  Aurora over gf64 runs through these from the Python
+ * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); Fractal, a distributed prover, head
+ * evaluation and the fused re-extensions are not built over gf64. */
+int iopx_gf64_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
+int iopx_gf64_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init);
+int iopx_lincomb_gf64_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
+int iopx_lincomb_affine_gf64_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, const uint64_t *constant, size_t n,
+                                 uint64_t *d_out);
+int iopx_spmv_gf64_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_coeff, size_t rows, const uint64_t *d_vec,
+                       const uint64_t *scale, int accumulate, uint64_t *d_out);
+int iopx_lincheck_gf64_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t num_matrices, const uint64_t *r_Mz,
+                           const uint64_t *d_p_alpha_prime, const uint64_t *d_p_alpha_ABC, size_t n, uint64_t *d_out);
+int iopx_rowcheck_gf64_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, const uint64_t *basis, size_t m,
+                           const uint64_t *shift, size_t constraint_dim, const uint64_t *constraint_shift, uint64_t *d_out);
+int iopx_fz_gf64_dev(const uint64_t *d_fw, const uint64_t *d_f1v, const uint64_t *basis, size_t m, const uint64_t *shift,
+                     const uint64_t *input_basis, size_t input_dim, const uint64_t *input_shift, uint64_t *d_out);
+int iopx_sumcheck_g_gf64_dev(const uint64_t *d_f, const uint64_t *d_h, const uint64_t *basis, size_t m, const uint64_t *shift,
+                             const uint64_t *summation_basis, size_t summation_dim, const uint64_t *summation_shift,
+                             const uint64_t *claimed_sum, uint64_t *d_out);
+int iopx_poly_div_vanishing_gf64_dev(const uint64_t *d_poly, size_t n_coeffs, const uint64_t *basis, size_t dim, const uint64_t *shift,
+                                     uint64_t *d_quotient);
 
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
@@ -642,6 +671,12 @@ int iopx_fp3_modulus(uint64_t *out);
 #define IOPX_FIELD_GF192 0
 #define IOPX_FIELD_EDWARDS_FR 1
 #define IOPX_FIELD_ALT_BN128_FR 2   /* Aurora instances (BLAKE2b or Poseidon: iopx_aurora_prove_hashed) and the FRI-only SNARK; no Fractal, no distributed prover */
+/* libff::gf64 (3 stays unknown): Aurora instances and the FRI-only SNARK on one GPU with BLAKE2b, in the reference's schedule (no head evaluation, whatever
+ * IOPX_HEAD_EVAL says; no fused re-extension).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf64: a communicator (the _dist forms),
+ * iopx_fractal_index / iopx_fractal_prove, a Poseidon hash, and a codeword domain of more than 2^IOPX_GF64_MAX_DOMAIN_DIM points — the bound of the gf64
+ * transform entries — which is checked from the parameters before any device work. */
+#define IOPX_FIELD_GF64 4
+#define IOPX_GF64_MAX_DOMAIN_DIM 40
 /* bcs_hash_type (libiop/bcs/hashing/hash_enum.hpp:21-26), as iopx_poseidon_shipped_params takes it */
 #define IOPX_HASH_BLAKE2B 1
 #define IOPX_HASH_POSEIDON_STARKWARE 2
@@ -650,10 +685,10 @@ typedef struct iopx_r1cs {
     size_t num_constraints, num_variables, num_inputs;
     const uint64_t *row_ptr[3];   /* A, B, C: num_constraints + 1 offsets each */
     const uint32_t *col[3];       /* column of each entry */
-    const uint64_t *coeff[3];     /* 3 words per entry; 4 over IOPX_FIELD_ALT_BN128_FR */
+    const uint64_t *coeff[3];     /* 3 words per entry; 4 over IOPX_FIELD_ALT_BN128_FR; 1 over IOPX_FIELD_GF64 */
 } iopx_r1cs;
 typedef struct iopx_aurora_instance iopx_aurora_instance;
-/* assignment: num_variables elements (primary inputs first), host memory; 3 words per element, 4 over IOPX_FIELD_ALT_BN128_FR (mont_repr) */
+/* assignment: num_variables elements (primary inputs first), host memory; 3 words per element, 4 over IOPX_FIELD_ALT_BN128_FR (mont_repr), 1 over IOPX_FIELD_GF64 */
 int iopx_aurora_instance_create(const iopx_r1cs *r1cs, const uint64_t *assignment, int field, iopx_aurora_instance **out);
 /* generate_r1cs_example (libiop/relations/examples/r1cs_examples.tcc:23-78) seeded with SplitMix64 */
 int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_t num_inputs, size_t num_variables, uint64_t seed,
@@ -693,7 +728,8 @@ int iopx_fri_snark_prove(int field, const uint64_t *d_poly_coeffs, size_t n_coef
  * Poseidon families exist over IOPX_FIELD_ALT_BN128_FR only (hash_enum.tcc:12-24; IOPX_ERR_INVALID_ARGUMENT otherwise): Poseidon trees with digests that
  * are field elements (32 bytes of mont_repr in the transcript), the algebraic sponge hashchain — which absorbs every root, so no root is deferred — and
  * the Poseidon proof of work (work parameter dim + 3 + 7 at cost 128: the same dim + 3 bits).  Over IOPX_FIELD_ALT_BN128_FR coefficients are 4 words per
- * element (mont_repr) and codeword_domain_dim <= 28; the field has no distributed form (iopx_fri_snark_prove_dist with a communicator fails). */
+ * element (mont_repr) and codeword_domain_dim <= 28; the field has no distributed form (iopx_fri_snark_prove_dist with a communicator fails).  Over
+ * IOPX_FIELD_GF64 coefficients are 1 word per element and codeword_domain_dim <= IOPX_GF64_MAX_DOMAIN_DIM; BLAKE2b only, no distributed form. */
 int iopx_fri_snark_prove_hashed(int field, int bcs_hash_type, const uint64_t *d_poly_coeffs, size_t n_coeffs, size_t codeword_domain_dim, size_t RS_extra_dimensions,
                                 size_t FRI_localization_parameter, size_t num_interactive_repetitions, size_t num_query_repetitions, uint8_t **transcript,
                                 size_t *transcript_bytes);

@@ -74,6 +74,8 @@ EXPORTED_SYMBOLS = [
     "iopx_add_fft_gf64_dev", "iopx_add_fft_gf64", "iopx_add_lde_gf64_dev", "iopx_add_ifft_gf64_dev", "iopx_add_ifft_gf64",
     "iopx_fri_fold_add_gf64_dev", "iopx_fri_fold_add_gf64", "iopx_fri_domains_gf64", "iopx_ldt_combine_gf64_dev",
     "iopx_gf64_mul_dev", "iopx_gf64_inv_dev", "iopx_gf64_host_mul", "iopx_gf64_inverse_host",
+    "iopx_gf64_add_dev", "iopx_gf64_pow_table_dev", "iopx_lincomb_gf64_dev", "iopx_lincomb_affine_gf64_dev", "iopx_spmv_gf64_dev",
+    "iopx_lincheck_gf64_dev", "iopx_rowcheck_gf64_dev", "iopx_fz_gf64_dev", "iopx_sumcheck_g_gf64_dev", "iopx_poly_div_vanishing_gf64_dev",
     "iopx_mem_check_stats",
 ]
 
@@ -126,6 +128,7 @@ def _ints_to_words4(values):
 
 
 FIELD_GF192, FIELD_EDWARDS_FR, FIELD_ALT_BN128_FR = 0, 1, 2                 # IOPX_FIELD_*
+FIELD_GF64 = 4                                                              # libff::gf64 (3 stays unknown to the C ABI)
 HASH_BLAKE2B, HASH_POSEIDON_STARKWARE, HASH_POSEIDON_HIGH_ALPHA = 1, 2, 3   # IOPX_HASH_*: the reference's bcs_hash_type
 
 
@@ -290,6 +293,13 @@ class Library:
         c.iopx_gf64_inv_dev.argtypes = [_vp, _vp, _sz]
         c.iopx_gf64_host_mul.argtypes = [_u64p, _u64p, _u64p]
         c.iopx_gf64_inverse_host.argtypes = [_u64p, _u64p]
+        c.iopx_gf64_pow_table_dev.argtypes = [_vp, _sz, _u64p, _u64p]
+        for name, twin in (("iopx_gf64_add_dev", "iopx_gf192_add_dev"), ("iopx_lincomb_gf64_dev", "iopx_lincomb_gf192_dev"),
+                           ("iopx_lincomb_affine_gf64_dev", "iopx_lincomb_affine_gf192_dev"), ("iopx_spmv_gf64_dev", "iopx_spmv_gf192_dev"),
+                           ("iopx_lincheck_gf64_dev", "iopx_lincheck_gf192_dev"), ("iopx_rowcheck_gf64_dev", "iopx_rowcheck_gf192_dev"),
+                           ("iopx_fz_gf64_dev", "iopx_fz_gf192_dev"), ("iopx_sumcheck_g_gf64_dev", "iopx_sumcheck_g_gf192_dev"),
+                           ("iopx_poly_div_vanishing_gf64_dev", "iopx_poly_div_vanishing_gf192_dev")):
+            getattr(c, name).argtypes = list(getattr(c, twin).argtypes)
 
     # ---- error translation (the exception types the reference throws) ----
     def _check(self, rc):
@@ -715,9 +725,11 @@ class Library:
         return out
 
     # ---- R1CS row check (rowcheck.tcc:16-88) ----
-    def rowcheck_dev(self, d_az, d_bz, d_cz, basis, shift, constraint_dim, constraint_shift, d_out):
-        basis, shift, cs = _as_u64(basis), _as_u64(shift), _as_u64(constraint_shift)
-        self._check(self.c.iopx_rowcheck_gf192_dev(_vp(d_az), _vp(d_bz), _vp(d_cz), basis.ctypes.data_as(_u64p), basis.shape[0],
+    def rowcheck_dev(self, d_az, d_bz, d_cz, basis, shift, constraint_dim, constraint_shift, d_out, words=3):
+        """words: 3 over gf192, 1 over gf64 (iopx_rowcheck_gf64_dev) — here and in the other subspace-shaped and vector methods that take it"""
+        basis, shift, cs = _as_u64(basis, words), _as_u64(shift, words), _as_u64(constraint_shift, words)
+        fn = self.c.iopx_rowcheck_gf64_dev if words == 1 else self.c.iopx_rowcheck_gf192_dev
+        self._check(fn(_vp(d_az), _vp(d_bz), _vp(d_cz), basis.ctypes.data_as(_u64p), basis.shape[0],
                                                    shift.ctypes.data_as(_u64p), int(constraint_dim), cs.ctypes.data_as(_u64p), _vp(d_out)))
 
     def rowcheck_multiplicative_dev(self, d_az, d_bz, d_cz, log_n, gen, shift, constraint_log_order, constraint_shift, d_out):
@@ -734,10 +746,11 @@ class Library:
                                                                                                  constraint_log_order, constraint_shift, o))
 
     # ---- fz virtual oracle (r1cs_rs_iop.tcc:181-222) ----
-    def fz_dev(self, d_fw, d_f1v, basis, shift, input_basis, input_shift, d_out):
-        basis, shift, ish = _as_u64(basis), _as_u64(shift), _as_u64(input_shift)
-        ib = np.ascontiguousarray(input_basis, dtype=np.uint64).reshape(-1, 3)
-        self._check(self.c.iopx_fz_gf192_dev(_vp(d_fw), _vp(d_f1v), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
+    def fz_dev(self, d_fw, d_f1v, basis, shift, input_basis, input_shift, d_out, words=3):
+        basis, shift, ish = _as_u64(basis, words), _as_u64(shift, words), _as_u64(input_shift, words)
+        ib = np.ascontiguousarray(input_basis, dtype=np.uint64).reshape(-1, words)
+        fn = self.c.iopx_fz_gf64_dev if words == 1 else self.c.iopx_fz_gf192_dev
+        self._check(fn(_vp(d_fw), _vp(d_f1v), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
                                              ib.ctypes.data_as(_u64p), ib.shape[0], ish.ctypes.data_as(_u64p), _vp(d_out)))
 
     def fz_multiplicative_dev(self, d_fw, d_f1v, log_n, gen, shift, input_log_order, input_shift, d_out):
@@ -752,10 +765,11 @@ class Library:
         return self._ldt_combine_host([fw, f1v], lambda d, o: self.fz_multiplicative_dev(d[0], d[1], log_n, gen, shift, input_log_order, input_shift, o))
 
     # ---- sumcheck g oracle (sumcheck.tcc:58-119) ----
-    def sumcheck_g_dev(self, d_f, d_h, basis, shift, summation_basis, summation_shift, claimed_sum, d_out):
-        basis, shift, ssh, mu = _as_u64(basis), _as_u64(shift), _as_u64(summation_shift), _as_u64(claimed_sum)
-        sb = np.ascontiguousarray(summation_basis, dtype=np.uint64).reshape(-1, 3)
-        self._check(self.c.iopx_sumcheck_g_gf192_dev(_vp(d_f), _vp(d_h), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
+    def sumcheck_g_dev(self, d_f, d_h, basis, shift, summation_basis, summation_shift, claimed_sum, d_out, words=3):
+        basis, shift, ssh, mu = _as_u64(basis, words), _as_u64(shift, words), _as_u64(summation_shift, words), _as_u64(claimed_sum, words)
+        sb = np.ascontiguousarray(summation_basis, dtype=np.uint64).reshape(-1, words)
+        fn = self.c.iopx_sumcheck_g_gf64_dev if words == 1 else self.c.iopx_sumcheck_g_gf192_dev
+        self._check(fn(_vp(d_f), _vp(d_h), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
                                                      sb.ctypes.data_as(_u64p), sb.shape[0], ssh.ctypes.data_as(_u64p), mu.ctypes.data_as(_u64p), _vp(d_out)))
 
     def sumcheck_g_multiplicative_dev(self, d_f, d_h, log_n, gen, shift, summation_log_order, summation_shift, claimed_sum, d_out):
@@ -771,12 +785,12 @@ class Library:
                                                                                               summation_shift, claimed_sum, o))
 
     # ---- lincheck virtual oracle (basic_lincheck_aux.tcc:102-144) ----
-    def lincheck_dev(self, d_fz, d_mz, r_mz, d_p1, d_p2, n, d_out, prime_field=False):
-        r = _as_u64(r_mz)
+    def lincheck_dev(self, d_fz, d_mz, r_mz, d_p1, d_p2, n, d_out, prime_field=False, words=3):
+        r = _as_u64(r_mz, words)
         if r.shape[0] != len(d_mz):
             raise ValueError("Not enough random linear combination coefficients were provided")
         ptrs = (_vp * len(d_mz))(*d_mz)
-        fn = self.c.iopx_lincheck_fp3_dev if prime_field else self.c.iopx_lincheck_gf192_dev
+        fn = self.c.iopx_lincheck_gf64_dev if words == 1 else self.c.iopx_lincheck_fp3_dev if prime_field else self.c.iopx_lincheck_gf192_dev
         self._check(fn(_vp(d_fz), ptrs, len(d_mz), r.ctypes.data_as(_u64p), _vp(d_p1), _vp(d_p2), int(n), _vp(d_out)))
 
     def lincheck(self, fz, mz, r_mz, p1, p2, prime_field=False):
@@ -884,8 +898,9 @@ class Library:
     def aurora_instance(self, field_code, matrices, num_variables, num_inputs, assignment):
         """iopx_aurora_instance_create: an instance from the caller's own constraint system and variable assignment.  matrices = three
         (row_ptr, col, coeff) triples in CSR form (A, B, C; coeff: (entries, 3) uint64 words; column 0 is the constant 1), assignment =
-        (num_variables, 3) words, primary inputs first; four words per element over FIELD_ALT_BN128_FR (2).  Release with aurora_instance_free."""
-        words = 4 if int(field_code) == 2 else 3
+        (num_variables, 3) words, primary inputs first; four words per element over FIELD_ALT_BN128_FR (2), one over FIELD_GF64 (4).  Release with
+        aurora_instance_free."""
+        words = {FIELD_ALT_BN128_FR: 4, FIELD_GF64: 1}.get(int(field_code), 3)
         class _R1CS(ctypes.Structure):
             _fields_ = [("num_constraints", _sz), ("num_variables", _sz), ("num_inputs", _sz), ("row_ptr", _u64p * 3),
                         ("col", ctypes.POINTER(ctypes.c_uint32) * 3), ("coeff", _u64p * 3)]
@@ -1246,9 +1261,10 @@ class Library:
         self._check(self.c.iopx_add_combine_inv_gf192_dev(_vp(d_lo), _vp(d_up), _vp(d_out), count, index_base, basis.ctypes.data_as(_u64p),
                                                           basis.shape[0], shift_term.ctypes.data_as(_u64p), int(upper)))
 
-    def pow_table_dev(self, d_out, count, base, init):
-        base, init = _as_u64(base), _as_u64(init)
-        self._check(self.c.iopx_gf192_pow_table_dev(_vp(d_out), count, base.ctypes.data_as(_u64p), init.ctypes.data_as(_u64p)))
+    def pow_table_dev(self, d_out, count, base, init, words=3):
+        base, init = _as_u64(base, words), _as_u64(init, words)
+        fn = self.c.iopx_gf64_pow_table_dev if words == 1 else self.c.iopx_gf192_pow_table_dev
+        self._check(fn(_vp(d_out), count, base.ctypes.data_as(_u64p), init.ctypes.data_as(_u64p)))
 
     def combine_dev(self, d_a, d_b, d_out, count, index_base, basis, shift_term, upper):
         basis, shift_term = _as_u64(basis), _as_u64(shift_term)
@@ -1281,39 +1297,40 @@ class Library:
         self._check(self.c.iopx_merkle_inner_blake2b_dev(_vp(d_nodes), int(num_leaves)))
 
     # ---- encoded Aurora prover: vector-sized steps between the transforms (include/libiop_amd.h) ----
-    def spmv_dev(self, d_row_ptr, d_col, d_coeff, rows, d_vec, d_out, scale=None, accumulate=False, prime_field=False):
+    def spmv_dev(self, d_row_ptr, d_col, d_coeff, rows, d_vec, d_out, scale=None, accumulate=False, prime_field=False, words=3):
         """out[r] (+)= scale * sum_t coeff[t] * vec[col[t]] over CSR rows (r1cs.tcc:236-268; basic_lincheck_aux.tcc:64-88)."""
-        sc = _as_u64(scale).ctypes.data_as(_u64p) if scale is not None else None
-        fn = self.c.iopx_spmv_fp3_dev if prime_field else self.c.iopx_spmv_gf192_dev
+        sc = _as_u64(scale, words).ctypes.data_as(_u64p) if scale is not None else None
+        fn = self.c.iopx_spmv_gf64_dev if words == 1 else self.c.iopx_spmv_fp3_dev if prime_field else self.c.iopx_spmv_gf192_dev
         self._check(fn(_vp(d_row_ptr), _vp(d_col), _vp(d_coeff), int(rows), _vp(d_vec), sc, int(bool(accumulate)), _vp(d_out)))
 
-    def poly_div_vanishing_dev(self, d_poly, n_coeffs, basis, shift, d_quotient):
+    def poly_div_vanishing_dev(self, d_poly, n_coeffs, basis, shift, d_quotient, words=3):
         """Quotient by the vanishing polynomial of the affine subspace (basis, shift): n_coeffs - 2^dim coefficients."""
-        shift = _as_u64(shift)
-        b = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, 3)
-        self._check(self.c.iopx_poly_div_vanishing_gf192_dev(_vp(d_poly), int(n_coeffs), b.ctypes.data_as(_u64p), b.shape[0],
+        shift = _as_u64(shift, words)
+        b = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, words)
+        fn = self.c.iopx_poly_div_vanishing_gf64_dev if words == 1 else self.c.iopx_poly_div_vanishing_gf192_dev
+        self._check(fn(_vp(d_poly), int(n_coeffs), b.ctypes.data_as(_u64p), b.shape[0],
                                                              shift.ctypes.data_as(_u64p), _vp(d_quotient)))
 
     def poly_div_vanishing_multiplicative_dev(self, d_poly, n_coeffs, log_order, shift, d_quotient):
         shift = _as_u64(shift)
         self._check(self.c.iopx_poly_div_vanishing_fp3_dev(_vp(d_poly), int(n_coeffs), int(log_order), shift.ctypes.data_as(_u64p), _vp(d_quotient)))
 
-    def lincomb_dev(self, d_oracles, coefficients, n, d_out, prime_field=False):
+    def lincomb_dev(self, d_oracles, coefficients, n, d_out, prime_field=False, words=3):
         """random_linear_combination_oracle::evaluated_contents: out = sum_i coefficients[i] * oracle_i."""
-        co = _as_u64(coefficients)
+        co = _as_u64(coefficients, words)
         if co.shape[0] != len(d_oracles):
             raise ValueError("Random Linear Combination Oracle: Expected same number of random coefficients as oracles.")
         ptrs = (_vp * len(d_oracles))(*d_oracles)
-        fn = self.c.iopx_lincomb_fp3_dev if prime_field else self.c.iopx_lincomb_gf192_dev
+        fn = self.c.iopx_lincomb_gf64_dev if words == 1 else self.c.iopx_lincomb_fp3_dev if prime_field else self.c.iopx_lincomb_gf192_dev
         self._check(fn(ptrs, len(d_oracles), co.ctypes.data_as(_u64p), int(n), _vp(d_out)))
 
-    def lincomb_affine_dev(self, d_oracles, coefficients, constant, n, d_out, prime_field=False):
+    def lincomb_affine_dev(self, d_oracles, coefficients, constant, n, d_out, prime_field=False, words=3):
         """sum_i coefficients[i] * oracle_i + constant (single_matrix_denominator::evaluated_contents)."""
-        co, c0 = _as_u64(coefficients), _as_u64(constant)
+        co, c0 = _as_u64(coefficients, words), _as_u64(constant, words)
         if co.shape[0] != len(d_oracles):
             raise ValueError("Expected same number of coefficients as oracles.")
         ptrs = (_vp * len(d_oracles))(*d_oracles)
-        fn = self.c.iopx_lincomb_affine_fp3_dev if prime_field else self.c.iopx_lincomb_affine_gf192_dev
+        fn = self.c.iopx_lincomb_affine_gf64_dev if words == 1 else self.c.iopx_lincomb_affine_fp3_dev if prime_field else self.c.iopx_lincomb_affine_gf192_dev
         self._check(fn(ptrs, len(d_oracles), co.ctypes.data_as(_u64p), c0.ctypes.data_as(_u64p), int(n), _vp(d_out)))
 
     def field_div_dev(self, d_num, d_den, d_out, count, prime_field=False):
@@ -1378,8 +1395,9 @@ class Library:
         self._check(self.c.iopx_gf192_inverse_host(x.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
         return out
 
-    def field_add_dev(self, d_a, d_b, d_out, count):
-        self._check(self.c.iopx_gf192_add_dev(_vp(d_a), _vp(d_b), _vp(d_out), int(count)))
+    def field_add_dev(self, d_a, d_b, d_out, count, words=3):
+        fn = self.c.iopx_gf64_add_dev if words == 1 else self.c.iopx_gf192_add_dev
+        self._check(fn(_vp(d_a), _vp(d_b), _vp(d_out), int(count)))
 
     def field_inv_dev(self, d_a, d_out, count, prime_field=False):
         fn = self.c.iopx_fp3_inv_dev if prime_field else self.c.iopx_gf192_inv_dev

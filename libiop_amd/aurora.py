@@ -30,6 +30,11 @@ def _is_pow2(n):
     return n > 0 and (n & (n - 1)) == 0
 
 
+def _words(field):
+    """uint64 words per element: three, or one over GF(2^64)"""
+    return getattr(field, "words", 3)
+
+
 class AuroraParameters:
     """aurora_snark_parameters + aurora_iop_parameters (non-zk, heuristic FRI soundness, optimistic-heuristic LDT-reducer
     soundness: the settings of profiling/instrument_aurora_snark.cpp:209-217 / boost_profile.cpp:11-21)."""
@@ -85,10 +90,11 @@ class FzVirtualOracle(VirtualOracle):
         self.d_f1v_coefficients = None
 
     def set_primary_input(self, primary_input):
-        primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, 3)
+        w = _words(self.ops.field)
+        primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, w)
         if primary_input.shape[0] != self.k:
             raise ValueError("Primary input size does not match the previously declared size.")
-        one = np.array([[1, 0, 0]], dtype=np.uint64) if self.ops.field.additive else self.ops.field.from_int(1).reshape(1, 3)
+        one = self.ops.field.one().reshape(1, w)
         f1v_evals = self.ops.upload(np.concatenate([one, primary_input]))                      # :199-206
         self.d_f1v_coefficients = self.ops.IFFT(f1v_evals, self.I)                             # :207-210
 
@@ -128,13 +134,13 @@ class MultiLincheckVirtualOracle(VirtualOracle):
             raise ValueError("Not enough random linear combination coefficients were provided")
         ops, f = self.ops, self.ops.field
         self.r_Mz = r_Mz
-        one = np.array([1, 0, 0], dtype=np.uint64) if f.additive else f.from_int(1)
+        one = f.one()
         alpha_powers = ops.pow_table(self.C.size, alpha, one)                                   # :37-45
         if self.C.size == self.S.size:                                                         # reindex_by_subset is the identity
             prime_evals = alpha_powers
         else:
             idx = ops.upload_raw(self.S.reindex_by_subset_array(self.C.dim, self.C.size), ops.torch.int64)
-            prime_evals = ops.torch.zeros((self.S.size, 3), dtype=ops.torch.int64, device=ops.device)
+            prime_evals = ops.torch.zeros((self.S.size, _words(f)), dtype=ops.torch.int64, device=ops.device)
             prime_evals[idx] = alpha_powers                                                    # :50-58
         # the two p_alpha evaluation vectors over the summation domain, back to back; the reference interpolates them here (:94-98)
         # and extends them in evaluated_contents (:112-118): both happen there, as one re-extension
@@ -335,11 +341,11 @@ class EncodedAuroraProtocol:
         equals z), is divided by Z_I and extended together with f_Az, f_Bz, f_Cz.  d_assignment: the variable assignment
         (1, primary, auxiliary) already resident on the device (then auxiliary_input may be None)."""
         ops = self.ops
-        primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, 3)
+        primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, _words(ops.field))
         self.fz_oracle.set_primary_input(primary_input)                                                  # :485, :508-516
         f1v_over_variable_domain = ops.FFT(self.fz_oracle.d_f1v_coefficients, self.I.size, self.V)       # :517-518
         if d_assignment is None:
-            auxiliary_input = np.ascontiguousarray(auxiliary_input, dtype=np.uint64).reshape(-1, 3)
+            auxiliary_input = np.ascontiguousarray(auxiliary_input, dtype=np.uint64).reshape(-1, _words(ops.field))
             d_z = ops.upload(assignment_vector(ops.field, primary_input, auxiliary_input))               # :581-585
         else:
             d_z = d_assignment
@@ -511,8 +517,9 @@ class AuroraIOP:
 
 def assignment_vector(field, primary_input, auxiliary_input):
     """The variable assignment z = (1, primary, auxiliary) (r1cs_rs_iop.tcc:581-585) as host words."""
-    one = np.array([[1, 0, 0]], dtype=np.uint64) if field.additive else field.from_int(1).reshape(1, 3)
-    return np.concatenate([one, np.asarray(primary_input, dtype=np.uint64).reshape(-1, 3), np.asarray(auxiliary_input, dtype=np.uint64).reshape(-1, 3)])
+    w = _words(field)
+    return np.concatenate([field.one().reshape(1, w), np.asarray(primary_input, dtype=np.uint64).reshape(-1, w),
+                           np.asarray(auxiliary_input, dtype=np.uint64).reshape(-1, w)])
 
 
 def aurora_snark_prover(ops, constraint_system, primary_input, auxiliary_input, parameters, round_hook=None, d_assignment=None):

@@ -64,7 +64,7 @@ device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coe
         device_vector<FieldT> out(dist::local_size(D));
         if (additive(D)) {                                                                   // its coset range of the transform; phase 1 on the coefficients is replicated
             const auto range = dist::coset_range(D, detail::log2_ceil(n_coeffs));
-            check(iopx_add_lde_gf192_dev(coeffs.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), range.first, range.second, out.words()));
+            check(ops::add_lde<field_of<FieldT>>(coeffs.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), range.first, range.second, out.words()));
         } else {                                                                             // one ordinary transform over the rank's sub-coset
             if (n_coeffs > out.size()) throw std::invalid_argument("more coefficients than a residue class holds");
             const field_subset<FieldT> loc = dist::local_domain(D);
@@ -73,7 +73,7 @@ device_vector<FieldT> FFT(const device_vector<FieldT> &coeffs, std::size_t n_coe
         return out;
     }
     device_vector<FieldT> out(D.num_elements());
-    if (additive(D)) { check(iopx_add_fft_gf192_dev(coeffs.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), out.words())); return out; }
+    if (additive(D)) { check(ops::add_fft<field_of<FieldT>>(coeffs.words(), n_coeffs, basis_words(D), D.dimension(), shift_words(D), out.words())); return out; }
     // the windows the prover will ask for (dist::window_collector) leave the transform's last pass together with the codeword
     // (a field without that entry takes the plain transform: the prover gathers them; so does alt_bn128 Fr under IOPX_BN128_FFT_WINDOWS=0)
     const P *prime = field_of<FieldT>::prime;
@@ -107,7 +107,7 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
     if (evals.size() != D.num_elements()) throw std::invalid_argument("IFFT: evaluation count != domain size");
     require_whole(D);
     device_vector<FieldT> out(D.num_elements());
-    if (additive(D)) check(iopx_add_ifft_gf192_dev(evals.words(), basis_words(D), D.dimension(), shift_words(D), out.words()));
+    if (additive(D)) check(ops::add_ifft<field_of<FieldT>>(evals.words(), basis_words(D), D.dimension(), shift_words(D), out.words()));
     else check(field_entry<FieldT>(&P::mul_ifft, "IFFT")(evals.words(), D.dimension(), gen_words(D), shift_words(D), out.words()));
     return out;
 }
@@ -115,13 +115,14 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
 // FFT_over_field_subset(IFFT_over_field_subset(v, H), L) for `batch` vectors stored back to back.  When H is spanned by the first basis
 // vectors of L the coefficient form is skipped (iopx_add_reextend_gf192_batch_dev); otherwise the two transforms run one after the other.
 // H_is_first_coset: H is the first coset of its span inside L (same shift), so the first |H| entries of each codeword are the input itself.
+// An 8-byte field (gf64) has no fused or batched re-extension: here and in the two forms below its transforms run one after the other.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &packed, std::size_t batch, const field_subset<FieldT> &H,
                                                    const field_subset<FieldT> &L, bool H_is_first_coset = false)
 {
     const std::size_t n = H.num_elements();
     std::vector<device_vector<FieldT>> outs;
-    bool prefix = additive(L) && H.dimension() <= L.dimension();
+    bool prefix = additive(L) && sizeof(FieldT) != 8 && H.dimension() <= L.dimension();
     if (prefix) for (std::size_t i = 0; i < H.dimension(); ++i) prefix = prefix && std::memcmp(&H.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     if (prefix) {
         std::vector<uint64_t *> ptrs;
@@ -148,7 +149,7 @@ std::vector<device_vector<FieldT>> reextend2_packed(const device_vector<FieldT> 
                                                     std::size_t batch_b, const field_subset<FieldT> &Hb, const field_subset<FieldT> &L)
 {
     std::vector<device_vector<FieldT>> outs;
-    bool together = additive(L) && additive(Ha) && additive(Hb) && Ha.dimension() == Hb.dimension() && Ha.dimension() > 0 && Ha.dimension() <= L.dimension();
+    bool together = sizeof(FieldT) != 8 && additive(L) && additive(Ha) && additive(Hb) && Ha.dimension() == Hb.dimension() && Ha.dimension() > 0 && Ha.dimension() <= L.dimension();
     for (std::size_t i = 0; together && i < Ha.dimension(); ++i)
         together = std::memcmp(&Ha.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0 && std::memcmp(&Hb.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     if (!together) {
@@ -171,7 +172,7 @@ template<typename FieldT>
 std::vector<device_vector<FieldT>> FFT_and_reextend_packed(const device_vector<FieldT> &poly, const device_vector<FieldT> &packed, std::size_t batch,
                                                            const field_subset<FieldT> &H, const field_subset<FieldT> &L)
 {
-    bool prefix = additive(L) && additive(H) && H.dimension() <= L.dimension() && poly.size() <= H.num_elements() && H.dimension() > 0;
+    bool prefix = sizeof(FieldT) != 8 && additive(L) && additive(H) && H.dimension() <= L.dimension() && poly.size() <= H.num_elements() && H.dimension() > 0;
     if (prefix) for (std::size_t i = 0; i < H.dimension(); ++i) prefix = prefix && std::memcmp(&H.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     std::vector<device_vector<FieldT>> outs;
     if (!prefix) {
@@ -259,7 +260,7 @@ device_vector<FieldT> fold(const device_vector<FieldT> &f, const field_subset<Fi
     const field_subset<FieldT> &D = D_in;
     require_whole(D);
     device_vector<FieldT> out(D.num_elements() / coset_size);
-    if (additive(D)) check(iopx_fri_fold_add_gf192_dev(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    if (additive(D)) check(ops::fri_fold_add<field_of<FieldT>>(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
     else check(field_entry<FieldT>(&P::fri_fold_mul, "fold")(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
     return out;
 }
@@ -323,10 +324,17 @@ inline bool head_evaluation_enabled()
 {
     return iopx_get_option("IOPX_HEAD_EVAL", 1) != 0;   // looked up per proof (iopx_set_option): tests and bench.py prove the same instance both ways
 }
+// ... for FieldT: an 8-byte field (gf64) always runs the reference's schedule, whatever the option says — its re-extensions have no fused form and its
+// pointwise division by Z_I no entry, so nothing of the head route is built over it
+template<typename FieldT>
+bool head_evaluation()
+{
+    return sizeof(FieldT) != 8 && head_evaluation_enabled();
+}
 template<typename FieldT>
 bool use_head(const field_subset<FieldT> &D, std::size_t count)
 {
-    return head_evaluation_enabled() && count * 4 <= D.num_elements() && D.num_elements() % count == 0 && dist::head_on_rank0(D, count);
+    return head_evaluation<FieldT>() && count * 4 <= D.num_elements() && D.num_elements() % count == 0 && dist::head_on_rank0(D, count);
 }
 
 template<typename FieldT>
@@ -821,7 +829,7 @@ public:
         const sparse_matrix<FieldT> *M[3] = { &cs_.A, &cs_.B, &cs_.C };
         for (int q = 0; q < 3; ++q) M[q]->times_vector(d_z, Mz.slice(q * nC, cs_.num_constraints()));                                       // :586-592, r1cs.tcc:236-268
         std::vector<device_vector<FieldT>> codewords;
-        if (dev::head_evaluation_enabled() && dev::spanned_by_prefix(V_, L_) && dev::spanned_by_prefix(I_, V_) && V_.dimension() < L_.dimension() && I_.num_elements() < V_.num_elements()) {
+        if (dev::head_evaluation<FieldT>() && dev::spanned_by_prefix(V_, L_) && dev::spanned_by_prefix(I_, V_) && V_.dimension() < L_.dimension() && I_.num_elements() < V_.num_elements()) {
             // f_w = f_w' / Z_I exactly (f_w' vanishes on the input positions by construction), deg f_w < |V|: so f_w over the first coset V0 of V inside L
             // is f_w' there (one re-extension from V) divided by Z_I pointwise (V0 does not meet I), and its codeword is the re-extension of THAT —
             // the coefficient form (:551-555), the division passes (:563-565) and both basis conversions drop out.  Same field elements.
@@ -879,7 +887,7 @@ class FRI_protocol {                                                            
             std::vector<std::size_t> dims;
             for (std::size_t eta : localization_) { d -= eta; dims.push_back(d); total += d; }
             std::vector<FieldT> bases(total ? total : 1), shifts(localization_.size());
-            check(iopx_fri_domains_gf192(dev::basis_words(L), L.dimension(), dev::shift_words(L), localization_.data(), localization_.size(),
+            check(ops::fri_domains<field_of<FieldT>>(dev::basis_words(L), L.dimension(), dev::shift_words(L), localization_.data(), localization_.size(),
                                          detail::words(bases.data()), detail::words(shifts.data())));
             std::size_t off = 0;
             for (std::size_t i = 0; i < dims.size(); ++i) {
@@ -908,7 +916,7 @@ class FRI_protocol {                                                            
     // so a whole window of agreement does not happen by accident.
     bool first_round_from_head(std::vector<std::vector<device_vector<FieldT>>> &by_interaction)
     {
-        if (num_reductions_ < 2 || !dev::head_evaluation_enabled()) return false;
+        if (num_reductions_ < 2 || !dev::head_evaluation<FieldT>()) return false;
         const field_subset<FieldT> &L0 = domains_[0], &L1 = domains_[1];
         const std::size_t head = (std::size_t)1 << detail::log2_ceil(poly_degree_bound_), cs0 = (std::size_t)1 << localization_[0];
         if (!dev::use_head(L0, head) || head / cs0 < 2) return false;
@@ -980,7 +988,7 @@ public:
         {
             dist::window h0, c0;
             std::size_t confirm;
-            if (dev::head_evaluation_enabled() && head_windows(h0, c0, confirm)) { IOP_.want_window(codeword_domain_handle_, h0); IOP_.want_window(codeword_domain_handle_, c0); }
+            if (dev::head_evaluation<FieldT>() && head_windows(h0, c0, confirm)) { IOP_.want_window(codeword_domain_handle_, h0); IOP_.want_window(codeword_domain_handle_, c0); }
         }
         std::size_t total = localization_[0];
         domain_handles_.assign(num_reductions_, codeword_domain_handle_);

@@ -12,7 +12,7 @@
 namespace libiop_amd {
 
 // ---- host scalars of FieldT (per-proof constants only) --------------------------------------------------------------------------
-// One body for all three fields, written against the table of field_ops.hpp: gf192 keeps its branches (xor, the subspace forms of Z_S),
+// One body for every field, written against the table of field_ops.hpp: gf192 keeps its branches (xor, the subspace forms of Z_S),
 // everything else is the field's entry.  A size / kind the table does not have fails to compile.
 template<typename FieldT>
 struct field_host {
@@ -56,6 +56,7 @@ struct field_host {
     static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
+            if (WORDS == 1) ops::missing("vanishing_eval", table::vec->name);               // gf64: no host form of Z_S (only the head route and Fractal ask)
             uint64_t w[WORDS];
             const FieldT shift = S.shift();
             check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), w, nullptr));
@@ -67,6 +68,7 @@ struct field_host {
     static FieldT vanishing_derivative(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
+            if (WORDS == 1) ops::missing("vanishing_derivative", table::vec->name);
             uint64_t w[WORDS];
             const FieldT shift = S.shift();
             check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), nullptr, w));
@@ -81,7 +83,8 @@ struct field_host {
             if (!S.subspace().is_standard_basis()) throw std::logic_error("membership test for a non-standard basis");
             const FieldT v = add(x, S.shift());
             const uint64_t *w = detail::words(&v);
-            return w[1] == 0 && w[2] == 0 && (S.dimension() >= 64 || w[0] < ((uint64_t)1 << S.dimension()));
+            for (std::size_t i = 1; i < WORDS; ++i) if (w[i]) return false;
+            return S.dimension() >= 64 || w[0] < ((uint64_t)1 << S.dimension());
         }
         const FieldT r = pow(mul(x, inverse(S.shift())), S.num_elements());
         const FieldT o = one();

@@ -12,7 +12,7 @@
 namespace libiop_amd {
 namespace ops {
 
-// the entries with one signature in all three fields
+// the entries with one signature in every field
 struct vector_ops {
     const char *name;
     std::size_t soundness_bits;                  // libff::soundness_log_of_field_size_helper: the extension degree / floor(log2 p)
@@ -41,6 +41,13 @@ inline constexpr vector_ops gf192 = {
     iopx_gf192_host_mul, iopx_gf192_inverse_host,
     iopx_gf192_add_dev, iopx_gf192_mul_dev, iopx_gf192_inv_dev, iopx_gf192_div_dev, iopx_gf192_pow_table_dev,
     iopx_lincomb_gf192_dev, iopx_lincomb_affine_gf192_dev, iopx_lincheck_gf192_dev, iopx_spmv_gf192_dev, iopx_rational_combine_gf192_dev,
+};
+// libff::gf64: the Aurora prover's entries (csrc/gf64_ops.hip); no batch division and no rational combination (Fractal is not built over it)
+inline constexpr vector_ops gf64 = {
+    "gf64", 64, false,
+    iopx_gf64_host_mul, iopx_gf64_inverse_host,
+    iopx_gf64_add_dev, iopx_gf64_mul_dev, iopx_gf64_inv_dev, nullptr, iopx_gf64_pow_table_dev,
+    iopx_lincomb_gf64_dev, iopx_lincomb_affine_gf64_dev, iopx_lincheck_gf64_dev, iopx_spmv_gf64_dev, nullptr,
 };
 inline constexpr prime_field_ops edwards_Fr = {
     { "edwards Fr", 180, true,
@@ -74,6 +81,7 @@ inline constexpr prime_field_ops alt_bn128_Fr = {
 // ---- selection ---------------------------------------------------------------------------------------------------------------------
 template<std::size_t Bytes, bool Additive> struct field;                   // by field_kind<FieldT> and sizeof(FieldT)
 template<> struct field<24, true> { static constexpr const vector_ops *vec = &gf192; static constexpr const prime_field_ops *prime = nullptr; static constexpr bool additive = true; };
+template<> struct field<8, true> { static constexpr const vector_ops *vec = &gf64; static constexpr const prime_field_ops *prime = nullptr; static constexpr bool additive = true; };
 template<> struct field<24, false> { static constexpr const prime_field_ops *vec = &edwards_Fr, *prime = &edwards_Fr; static constexpr bool additive = false; };
 template<> struct field<32, false> { static constexpr const prime_field_ops *vec = &alt_bn128_Fr, *prime = &alt_bn128_Fr; static constexpr bool additive = false; };
 // by size alone, for reference_binding.hpp (it does not see field_kind): the prime field of that size; the domain's kind tells gf192 from edwards Fr
@@ -106,38 +114,67 @@ template<class F> inline bool subspace(const domain &D, const char *op)
     return D.additive;
 }
 
+// the binary field of the selection: one-word elements take the gf64 entry of a subspace operation, three-word ones the gf192 entry
+template<class F> inline bool one_word() { return static_cast<const vector_ops *>(F::vec) == &gf64; }
+
+// the transforms over affine subspaces, the FRI fold and the FRI domain chain (the arguments of the C entries)
+template<class F> inline int add_fft(const uint64_t *d_coeffs, std::size_t n_coeffs, const uint64_t *basis, std::size_t m, const uint64_t *shift, uint64_t *d_out)
+{
+    return (one_word<F>() ? iopx_add_fft_gf64_dev : iopx_add_fft_gf192_dev)(d_coeffs, n_coeffs, basis, m, shift, d_out);
+}
+template<class F> inline int add_lde(const uint64_t *d_coeffs, std::size_t n_coeffs, const uint64_t *basis, std::size_t m, const uint64_t *shift, std::size_t coset_begin,
+                                     std::size_t coset_count, uint64_t *d_out)
+{
+    return (one_word<F>() ? iopx_add_lde_gf64_dev : iopx_add_lde_gf192_dev)(d_coeffs, n_coeffs, basis, m, shift, coset_begin, coset_count, d_out);
+}
+template<class F> inline int add_ifft(const uint64_t *d_evals, const uint64_t *basis, std::size_t m, const uint64_t *shift, uint64_t *d_out)
+{
+    return (one_word<F>() ? iopx_add_ifft_gf64_dev : iopx_add_ifft_gf192_dev)(d_evals, basis, m, shift, d_out);
+}
+template<class F> inline int fri_fold_add(const uint64_t *d_f, const uint64_t *basis, std::size_t m, const uint64_t *shift, std::size_t coset_size, const uint64_t *x_i, uint64_t *d_next)
+{
+    return (one_word<F>() ? iopx_fri_fold_add_gf64_dev : iopx_fri_fold_add_gf192_dev)(d_f, basis, m, shift, coset_size, x_i, d_next);
+}
+template<class F> inline int fri_domains(const uint64_t *basis, std::size_t m, const uint64_t *shift, const std::size_t *localization, std::size_t num_reductions, uint64_t *out_bases,
+                                         uint64_t *out_shifts)
+{
+    return (one_word<F>() ? iopx_fri_domains_gf64 : iopx_fri_domains_gf192)(basis, m, shift, localization, num_reductions, out_bases, out_shifts);
+}
+
 template<class F> inline int ldt_combine(const domain &L, const void *const *d_oracles, std::size_t num_oracles, const std::size_t *degrees, const uint64_t *coefficients, uint64_t *d_out)
 {
-    if (subspace<F>(L, "ldt_combine")) return iopx_ldt_combine_gf192_dev(d_oracles, num_oracles, degrees, coefficients, L.basis, L.dim, L.shift, d_out);
+    if (subspace<F>(L, "ldt_combine")) return (one_word<F>() ? iopx_ldt_combine_gf64_dev : iopx_ldt_combine_gf192_dev)(d_oracles, num_oracles, degrees, coefficients, L.basis, L.dim, L.shift, d_out);
     return entry<F>(&prime_field_ops::ldt_combine, "ldt_combine")(d_oracles, num_oracles, degrees, coefficients, L.dim, L.gen, L.shift, d_out);
 }
 template<class F> inline int rowcheck(const domain &L, const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, std::size_t h_dim, const uint64_t *h_shift, uint64_t *d_out)
 {
-    if (subspace<F>(L, "rowcheck")) return iopx_rowcheck_gf192_dev(d_Az, d_Bz, d_Cz, L.basis, L.dim, L.shift, h_dim, h_shift, d_out);
+    if (subspace<F>(L, "rowcheck")) return (one_word<F>() ? iopx_rowcheck_gf64_dev : iopx_rowcheck_gf192_dev)(d_Az, d_Bz, d_Cz, L.basis, L.dim, L.shift, h_dim, h_shift, d_out);
     return entry<F>(&prime_field_ops::rowcheck, "rowcheck")(d_Az, d_Bz, d_Cz, L.dim, L.gen, L.shift, h_dim, h_shift, d_out);
 }
 template<class F> inline int fz(const domain &L, const domain &I, const uint64_t *d_fw, const uint64_t *d_f1v, uint64_t *d_out)
 {
-    if (subspace<F>(L, "fz")) return iopx_fz_gf192_dev(d_fw, d_f1v, L.basis, L.dim, L.shift, I.basis, I.dim, I.shift, d_out);
+    if (subspace<F>(L, "fz")) return (one_word<F>() ? iopx_fz_gf64_dev : iopx_fz_gf192_dev)(d_fw, d_f1v, L.basis, L.dim, L.shift, I.basis, I.dim, I.shift, d_out);
     return entry<F>(&prime_field_ops::fz, "fz")(d_fw, d_f1v, L.dim, L.gen, L.shift, I.dim, I.shift, d_out);
 }
 template<class F> inline int sumcheck_g(const domain &L, const domain &H, const uint64_t *d_f, const uint64_t *d_h, const uint64_t *claimed_sum, uint64_t *d_out)
 {
-    if (subspace<F>(L, "sumcheck_g")) return iopx_sumcheck_g_gf192_dev(d_f, d_h, L.basis, L.dim, L.shift, H.basis, H.dim, H.shift, claimed_sum, d_out);
+    if (subspace<F>(L, "sumcheck_g")) return (one_word<F>() ? iopx_sumcheck_g_gf64_dev : iopx_sumcheck_g_gf192_dev)(d_f, d_h, L.basis, L.dim, L.shift, H.basis, H.dim, H.shift, claimed_sum, d_out);
     return entry<F>(&prime_field_ops::sumcheck_g, "sumcheck_g")(d_f, d_h, L.dim, L.gen, L.shift, H.dim, H.shift, claimed_sum, d_out);
 }
 template<class F> inline int poly_div_vanishing(const domain &D, const uint64_t *d_poly, std::size_t n_coeffs, uint64_t *d_quotient)
 {
-    if (subspace<F>(D, "poly_div_vanishing")) return iopx_poly_div_vanishing_gf192_dev(d_poly, n_coeffs, D.basis, D.dim, D.shift, d_quotient);
+    if (subspace<F>(D, "poly_div_vanishing")) return (one_word<F>() ? iopx_poly_div_vanishing_gf64_dev : iopx_poly_div_vanishing_gf192_dev)(d_poly, n_coeffs, D.basis, D.dim, D.shift, d_quotient);
     return entry<F>(&prime_field_ops::poly_div_vanishing, "poly_div_vanishing")(d_poly, n_coeffs, D.dim, D.shift, d_quotient);
 }
 template<class F> inline int domain_offsets(const domain &D, const uint64_t *point, uint64_t *d_out)
 {
+    if (one_word<F>()) missing("domain_offsets", F::vec->name);
     if (subspace<F>(D, "domain_offsets")) return iopx_domain_offsets_gf192_dev(D.basis, D.dim, D.shift, point, d_out);
     return entry<F>(&prime_field_ops::domain_offsets, "domain_offsets")(D.dim, D.gen, D.shift, point, d_out);
 }
 template<class F> inline int vanishing_evals(const domain &D, const domain &S, const uint64_t *constant, uint64_t *d_out)
 {
+    if (one_word<F>()) missing("vanishing_evals", F::vec->name);
     if (subspace<F>(D, "vanishing_evals")) return iopx_vanishing_evals_gf192_dev(D.basis, D.dim, D.shift, S.basis, S.dim, S.shift, constant, d_out);
     return entry<F>(&prime_field_ops::vanishing_evals, "vanishing_evals")(D.dim, D.gen, D.shift, S.dim, S.shift, constant, d_out);
 }
@@ -145,6 +182,7 @@ template<class F> inline int vanishing_evals(const domain &D, const domain &S, c
 template<class F> inline int rational_sumcheck_constraint(const domain &L, const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, const uint64_t *d_xinv, std::size_t k_dim,
                                                           const uint64_t *k_shift, const uint64_t *claimed_sum, uint64_t *d_out)
 {
+    if (one_word<F>()) missing("rational_sumcheck_constraint", F::vec->name);
     if (subspace<F>(L, "rational_sumcheck_constraint"))
         return iopx_rational_sumcheck_constraint_gf192_dev(d_p, d_N, d_D, d_xinv, L.basis, L.dim, L.shift, k_dim, k_shift, claimed_sum, d_out);
     return entry<F>(&prime_field_ops::rational_sumcheck_constraint, "rational_sumcheck_constraint")(d_p, d_N, d_D, L.dim, L.gen, L.shift, k_dim, k_shift, claimed_sum, d_out);

@@ -107,8 +107,9 @@ inline uint64_t splitmix64_at(uint64_t seed, uint64_t index)
     return z ^ (z >> 31);
 }
 
-// element i takes stream outputs 3 i .. 3 i + 2 as its low words, in every field: GF(2^192) the raw words; a prime field the 192-bit draw
-// reduced mod p (over alt_bn128 Fr it is below p already), in Montgomery form (one Montgomery product with R^2 does both)
+// element i takes stream outputs 3 i .. 3 i + 2 as its low words, in every field of three or four words: GF(2^192) the raw words; a prime field the
+// 192-bit draw reduced mod p (over alt_bn128 Fr it is below p already), in Montgomery form (one Montgomery product with R^2 does both).  Over the
+// one-word GF(2^64) element i is stream output i, as libiop_amd/r1cs.py draws it.
 template<typename FieldT>
 std::vector<FieldT> seeded_elements(uint64_t seed, std::size_t count)
 {
@@ -117,7 +118,8 @@ std::vector<FieldT> seeded_elements(uint64_t seed, std::size_t count)
     const FieldT R2 = H::additive() ? H::one() : H::pow(H::from_uint(2), 64 * H::WORDS);      // the element R = 2^192 / 2^256: its stored words are R^2 mod p
     for (std::size_t i = 0; i < count; ++i) {
         uint64_t w[H::WORDS] = {};
-        for (int k = 0; k < 3; ++k) w[k] = splitmix64_at(seed, 3 * i + k);
+        if (H::WORDS == 1) w[0] = splitmix64_at(seed, i);
+        else for (std::size_t k = 0; k < 3 && k < H::WORDS; ++k) w[k] = splitmix64_at(seed, 3 * i + k);
         out[i] = H::from_words(w);
         if (!H::additive()) out[i] = H::mul(out[i], R2);
     }

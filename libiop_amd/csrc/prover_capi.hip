@@ -1,7 +1,7 @@
 // The Aurora, Fractal and FRI-only provers behind the C ABI: iopx_aurora_* / iopx_fractal_* / iopx_fri_snark_* (include/libiop_amd.h).
 //
 // The orchestration is the C++ surface of libiop_amd/cpp/aurora.hpp — aurora_snark_prover<FieldT>(cs, primary, auxiliary, params),
-// the signature of libiop/snark/aurora_snark.tcc:120-146 — instantiated for the three accelerated fields and wrapped in plain C types, so
+// the signature of libiop/snark/aurora_snark.tcc:120-146 — instantiated for the four accelerated fields and wrapped in plain C types, so
 // that a caller without a C++ toolchain (the ctypes binding, bench.py) reaches the native prover too.  Host-only code: no kernels here.
 #include <cstring>
 #include <memory>
@@ -58,14 +58,17 @@ struct Instance : InstanceBase {
 
     size_t num_constraints() const override { return cs.num_constraints(); }
     static constexpr bool bn128 = sizeof(F) == 32;                // alt_bn128 Fr: Aurora only, on one GPU
+    static constexpr bool gf64 = sizeof(F) == 8;                  // gf64: Aurora only, on one GPU, BLAKE2b
     std::vector<std::string> fractal_index(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
         if constexpr (bn128) throw std::invalid_argument("iopx_fractal_index: there is no Fractal prover over alt_bn128 Fr");
+        else if constexpr (gf64) throw std::invalid_argument("iopx_fractal_index: there is no Fractal prover over gf64");
         else return fractal_index_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
     }
     std::string fractal_prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
         if constexpr (bn128) throw std::invalid_argument("iopx_fractal_prove: there is no Fractal prover over alt_bn128 Fr");
+        else if constexpr (gf64) throw std::invalid_argument("iopx_fractal_prove: there is no Fractal prover over gf64");
         else return fractal_prove_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
     }
     std::vector<std::string> fractal_index_(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter)
@@ -95,14 +98,19 @@ struct Instance : InstanceBase {
     {
         if (bcs_hash_type != IOPX_HASH_BLAKE2B && bcs_hash_type != IOPX_HASH_POSEIDON_STARKWARE && bcs_hash_type != IOPX_HASH_POSEIDON_HIGH_ALPHA)
             throw std::invalid_argument("bcs_hash_type unknown");
+        if (bcs_hash_type != IOPX_HASH_BLAKE2B && gf64) throw std::invalid_argument("gf64 proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
         if (bcs_hash_type != IOPX_HASH_BLAKE2B && !bn128) throw std::invalid_argument("Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
         if (bn128 && comm) throw std::invalid_argument("alt_bn128 Fr has no distributed prover: pass no communicator");
+        if (gf64 && comm) throw std::invalid_argument("gf64 has no distributed prover: pass no communicator");
         require_supported_security(security_parameter);
         const dist::scope bound(comm);
         const aurora_snark_parameters<F> params(cs.num_constraints(), cs.num_variables(), cs.num_inputs(), security_parameter, RS_extra_dimensions,
                                                 FRI_localization_parameter);
         if (bn128 && params.codeword_domain_dim_ > 28)
             throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": alt_bn128 Fr has subgroups of order up to 2^28");
+        if (gf64 && params.codeword_domain_dim_ > IOPX_GF64_MAX_DOMAIN_DIM)            // before any device work
+            throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": the gf64 transforms take domains of dimension up to " +
+                                        std::to_string(IOPX_GF64_MAX_DOMAIN_DIM));
         if constexpr (bn128) {
             if (bcs_hash_type != IOPX_HASH_BLAKE2B) return aurora_snark_prover_serialized<F, poseidon>(cs, primary, auxiliary, params, &d_assignment, poseidon(bcs_hash_type));
         }
@@ -188,7 +196,12 @@ int fri_entry(int field, int bcs_hash_type, iopx_comm *comm, const uint64_t *d_p
     int rc = iopx::ensure_device();
     if (rc != IOPX_OK) return rc;
     if (!transcript || !transcript_bytes || (n_coeffs && !d_poly_coeffs)) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (field == IOPX_FIELD_GF64 && codeword_domain_dim > IOPX_GF64_MAX_DOMAIN_DIM)
+        return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "codeword domain dimension %zu: the gf64 transforms take domains of dimension up to %d", codeword_domain_dim, IOPX_GF64_MAX_DOMAIN_DIM);
     if (codeword_domain_dim > 40) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "codeword domain dimension %zu too large", codeword_domain_dim);
+    if (field == IOPX_FIELD_GF64 && comm) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf64 has no distributed prover: pass no communicator");
+    if (field == IOPX_FIELD_GF64 && bcs_hash_type != IOPX_HASH_BLAKE2B && (bcs_hash_type == IOPX_HASH_POSEIDON_STARKWARE || bcs_hash_type == IOPX_HASH_POSEIDON_HIGH_ALPHA))
+        return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf64 proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
     if (field == IOPX_FIELD_ALT_BN128_FR && codeword_domain_dim > 28)
         return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "codeword domain dimension %zu: alt_bn128 Fr has subgroups of order up to 2^28", codeword_domain_dim);
     if (field == IOPX_FIELD_ALT_BN128_FR && comm) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "alt_bn128 Fr has no distributed prover: pass no communicator");
@@ -201,6 +214,7 @@ int fri_entry(int field, int bcs_hash_type, iopx_comm *comm, const uint64_t *d_p
         std::string t;
         if (field == IOPX_FIELD_GF192) t = fri_prove<gf192_element>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_EDWARDS_FR) t = fri_prove<edwards_Fr_element>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
+        else if (field == IOPX_FIELD_GF64) t = fri_prove<libiop_amd::gf64>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_ALT_BN128_FR && bcs_hash_type == IOPX_HASH_BLAKE2B) t = fri_prove<alt_bn128_Fr_element>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_ALT_BN128_FR) t = fri_prove<alt_bn128_Fr_element>(comm, d_poly_coeffs, n_coeffs, params, poseidon(bcs_hash_type));
         else throw std::invalid_argument("unknown field");
@@ -228,6 +242,7 @@ int iopx_aurora_instance_create(const iopx_r1cs *r1cs, const uint64_t *assignmen
         if (field == IOPX_FIELD_GF192) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<gf192_element>(r1cs, assignment));
         else if (field == IOPX_FIELD_EDWARDS_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<edwards_Fr_element>(r1cs, assignment));
         else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<alt_bn128_Fr_element>(r1cs, assignment));
+        else if (field == IOPX_FIELD_GF64) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<libiop_amd::gf64>(r1cs, assignment));
         else throw std::invalid_argument("unknown field");
     });
 }
@@ -241,6 +256,7 @@ int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_
         if (field == IOPX_FIELD_GF192) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<gf192_element>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_EDWARDS_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<edwards_Fr_element>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<alt_bn128_Fr_element>(num_constraints, num_inputs, num_variables, seed));
+        else if (field == IOPX_FIELD_GF64) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<libiop_amd::gf64>(num_constraints, num_inputs, num_variables, seed));
         else throw std::invalid_argument("unknown field");
     });
 }

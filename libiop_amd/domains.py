@@ -961,5 +961,108 @@ for _name in ("FFT_batch", "IFFT_batch", "IFFT_batch_packed", "reextend_packed",
     setattr(GF64DeviceOps, _name, _gf64_not_implemented(_name))
 
 
+class GF64AuroraOps(GF64DeviceOps):
+    """GF64DeviceOps plus what the Aurora prover (libiop_amd/aurora.py, libiop_amd/bcs.py) calls: the iopx_*_gf64_dev entries of
+    libiop_amd/csrc/gf64_ops.hip.  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  Batches and the
+    re-extension are one single-vector transform per vector (no fused or batched gf64 form); the operators only Fractal calls
+    (div, domain_offsets, domain_elements, vanishing_evals, lagrange_evals, rational_*) keep raising; lincomb_affine is there because its
+    entry shares the kernel of lincomb."""
+
+    upload_raw = DeviceOps.upload_raw
+
+    # ---- transforms ----
+    def FFT_batch(self, d_coeffs_list, n_coeffs, domain):
+        return [self.FFT(t, n_coeffs, domain) for t in d_coeffs_list]
+
+    def IFFT_batch(self, d_evals_list, domain):
+        return [self.IFFT(t, domain) for t in d_evals_list]
+
+    def IFFT_batch_packed(self, packed, batch, domain):
+        n = domain.size
+        return [self.IFFT(packed[k * n:(k + 1) * n], domain) for k in range(batch)]
+
+    def _coset_range(self, codeword_domain, d):
+        return 0, 1 << (codeword_domain.dim - d)
+
+    def reextend_packed(self, packed, batch, eval_domain, codeword_domain):
+        """FFT(IFFT(v, eval_domain), codeword_domain) per vector: the inverse transform, then the extension onto this process's cosets."""
+        n = eval_domain.size
+        d = max(n - 1, 0).bit_length()
+        lo, cnt = self._coset_range(codeword_domain, d)
+        outs = []
+        for coeffs in self.IFFT_batch_packed(packed, batch, eval_domain):
+            out = self.empty(cnt << d)
+            self.lib.additive_LDE_gf64_dev(coeffs.data_ptr(), n, codeword_domain.basis, codeword_domain.shift, lo, cnt, out.data_ptr())
+            outs.append(out)
+        return outs
+
+    # ---- virtual oracles ----
+    def rowcheck(self, d_az, d_bz, d_cz, codeword_domain, constraint_domain):
+        out = self.empty(codeword_domain.size)
+        self.lib.rowcheck_dev(d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), codeword_domain.basis, codeword_domain.shift,
+                                   constraint_domain.dim, constraint_domain.shift, out.data_ptr(), words=1)
+        return out
+
+    def fz(self, d_fw, d_f1v, codeword_domain, input_domain):
+        out = self.empty(codeword_domain.size)
+        self.lib.fz_dev(d_fw.data_ptr(), d_f1v.data_ptr(), codeword_domain.basis, codeword_domain.shift, input_domain.basis, input_domain.shift,
+                             out.data_ptr(), words=1)
+        return out
+
+    def sumcheck_g(self, d_f, d_h, codeword_domain, summation_domain, claimed_sum):
+        out = self.empty(codeword_domain.size)
+        self.lib.sumcheck_g_dev(d_f.data_ptr(), d_h.data_ptr(), codeword_domain.basis, codeword_domain.shift, summation_domain.basis,
+                                     summation_domain.shift, claimed_sum, out.data_ptr(), words=1)
+        return out
+
+    def lincheck(self, d_fz, d_mz, r_mz, d_p1, d_p2, n):
+        out = self.empty(n)
+        self.lib.lincheck_dev(d_fz.data_ptr(), [t.data_ptr() for t in d_mz], r_mz, d_p1.data_ptr(), d_p2.data_ptr(), n, out.data_ptr(), words=1)
+        return out
+
+    def lincomb(self, d_oracles, coefficients, n):
+        out = self.empty(n)
+        self.lib.lincomb_dev([t.data_ptr() for t in d_oracles], coefficients, n, out.data_ptr(), words=1)
+        return out
+
+    def lincomb_affine(self, d_oracles, coefficients, constant, n):
+        out = self.empty(n)
+        self.lib.lincomb_affine_dev([t.data_ptr() for t in d_oracles], coefficients, constant, n, out.data_ptr(), words=1)
+        return out
+
+    # ---- vector-sized steps ----
+    def sub(self, d_a, d_b):
+        out = self.empty(d_a.shape[0])
+        self.lib.field_add_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0], words=1)
+        return out
+
+    def mul(self, d_a, d_b):
+        out = self.empty(d_a.shape[0])
+        self.lib.gf64_mul_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
+        return out
+
+    def inv(self, d_a):
+        out = self.empty(d_a.shape[0])
+        self.lib.gf64_inv_dev(d_a.data_ptr(), out.data_ptr(), d_a.shape[0])
+        return out
+
+    def pow_table(self, count, base, init):
+        out = self.empty(count)
+        self.lib.pow_table_dev(out.data_ptr(), count, base, init, words=1)
+        return out
+
+    def spmv(self, csr, d_vec, d_out=None, scale=None, accumulate=False):
+        out = self.empty(csr.rows) if d_out is None else d_out
+        self.lib.spmv_dev(csr.d_row_ptr.data_ptr(), csr.d_col.data_ptr(), csr.d_coeff.data_ptr(), csr.rows, d_vec.data_ptr(), out.data_ptr(),
+                               scale=scale, accumulate=accumulate, words=1)
+        return out
+
+    def poly_div_vanishing(self, d_poly, n_coeffs, domain, out=None):
+        out = self.empty(max(n_coeffs - domain.size, 0)) if out is None else out
+        if n_coeffs > domain.size:
+            self.lib.poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.basis, domain.shift, out.data_ptr(), words=1)
+        return out
+
+
 def _p(words):
     return np.ascontiguousarray(words, dtype=np.uint64).ctypes.data_as(la._u64p)

@@ -103,8 +103,7 @@ def generate_r1cs_example(ops, num_constraints, num_inputs, num_variables, seed)
         coef_h, ab_h = ops.download(coef), ops.download(ab)
         coef_h[c_zero] = ab_h[c_zero]
         coef = ops.upload(coef_h)
-    one = field.from_int(1) if not field.additive else np.array([1, 0, 0], dtype=np.uint64)
-    ones = np.broadcast_to(one, (num_constraints, 3))
+    ones = np.broadcast_to(field.one(), (num_constraints, getattr(field, "words", 3)))
     row_ptr = np.arange(num_constraints + 1, dtype=np.int64)
     A = CSRMatrix(ops, row_ptr, a_idx + 1, ones, num_constraints)
     B = CSRMatrix(ops, row_ptr, b_idx + 1, ones, num_constraints)

@@ -4,7 +4,10 @@ and verifier.  Shared by
 tests/test_gf64_aurora_emu.py (CPU emulation) and tests/test_gpu_gf64_aurora.py (MI355X): every function takes the Library under test.
 
 Every comparison is byte equality.  Elements are (n, 1) uint64 arrays.  Each kernel case runs with its vectors at a 16-byte boundary and 8
-bytes past one: the entries take two elements per lane in the first placement and one in the second."""
+bytes past one: the entries take two elements per lane in the first placement and one in the second.  The edge cases (check_small_domains,
+check_short_vectors, check_mixed_placements, check_aliased_outputs, check_domain_table_turnover) add the smallest domains and vectors, one
+argument alone off the boundary, outputs over inputs and the turnover of the library's domain tables; tests/gf64_large_cases.py has the
+same entries past their launch caps."""
 import ctypes
 import hashlib
 import json
@@ -283,6 +286,161 @@ def check_add(lib):
     for n in (1, 4097):
         a, b = G.seeded("add a %d" % n, n), G.seeded("add b %d" % n, n)
         assert np.array_equal(on_device(lib, [a, b], n, lambda p, o: lib.field_add_dev(p[0], p[1], o, n, words=1)), a ^ b)
+
+
+# ---- edges of the same entries: the smallest domains, short and odd vectors, one argument off the 16-byte boundary, outputs over inputs ----
+def check_small_domains(lib):
+    """m = 0 and m = 1 (at n = 1 the pair form's second element is absent), h = 0 and h = m, input_dim = m, summation_dim = 0"""
+    mu = G.elem(int(G.seeded("sumcheck mu", 1)[0, 0]) | BIT63)
+    for m, h in ((0, 0), (1, 0), (1, 1), (9, 0), (9, 9)):
+        basis, shift = codeword_domain(m)
+        n = 1 << m
+        cshift = G.elem(BIT63 >> 1)
+        az, bz, cz = (G.seeded("small rowcheck %s %d" % (t, m), n) for t in "abc")
+        got = on_device(lib, [az, bz, cz], n, lambda p, o: lib.rowcheck_dev(p[0], p[1], p[2], basis, shift, h, cshift, o, words=1))
+        assert np.array_equal(got, oracle.rowcheck_additive(az, bz, cz, basis, shift, h, cshift)), (m, h)
+    for m, input_dim in ((0, 0), (1, 0), (1, 1), (10, 10)):
+        basis, shift = codeword_domain(m)
+        n = 1 << m
+        ib, ishift = basis[:input_dim], G.elem(BIT63 | 9)
+        fw, f1v = G.seeded("small fz w %d" % m, n), G.seeded("small fz 1v %d" % m, n)
+        got = on_device(lib, [fw, f1v], n, lambda p, o: lib.fz_dev(p[0], p[1], basis, shift, ib, ishift, o, words=1))
+        assert np.array_equal(got, oracle.fz_additive(fw, f1v, basis, shift, ib, ishift)), (m, input_dim)
+    for m, sdim in ((0, 0), (1, 0), (1, 1), (9, 0)):
+        for shifted in (True, False):                                  # unshifted: position 0 is the zero element
+            for claimed in (G.elem(0), mu):
+                basis, shift = codeword_domain(m, shifted)
+                n = 1 << m
+                sb, sshift = basis[:sdim], G.elem(BIT63 | 0x40)
+                f, h = G.seeded("small sumcheck f %d" % m, n), G.seeded("small sumcheck h %d" % m, n)
+                got = on_device(lib, [f, h], n, lambda p, o: lib.sumcheck_g_dev(p[0], p[1], basis, shift, sb, sshift, claimed, o, words=1))
+                assert np.array_equal(got, oracle.sumcheck_g_additive(f, h, basis, shift, sb, sshift, claimed)), (m, sdim, shifted, int(claimed[0]))
+
+
+def check_short_vectors(lib):
+    """n in {1, 2, 3, 511, 513} for the vector entries, two and three powers, division by X + s and by one coefficient more than |H|"""
+    for n in (1, 2, 3, 511, 513):
+        a, b = G.seeded("short add a %d" % n, n), G.seeded("short add b %d" % n, n)
+        assert np.array_equal(on_device(lib, [a, b], n, lambda p, o: lib.field_add_dev(p[0], p[1], o, n, words=1)), a ^ b), n
+        vecs = [G.seeded("short lincomb %d %d" % (n, k), n) for k in range(3)]
+        coef, constant = G.seeded("short lincomb coef", 3), G.elem(int(G.seeded("lincomb constant", 1)[0, 0]))
+        want = xor_all([scaled(v, c) for v, c in zip(vecs, coef)])
+        assert np.array_equal(on_device(lib, vecs, n, lambda p, o: lib.lincomb_dev(p, coef, n, o, words=1)), want), n
+        assert np.array_equal(on_device(lib, vecs, n, lambda p, o: lib.lincomb_affine_dev(p, coef, constant, n, o, words=1)), want ^ constant.reshape(1, 1)), n
+        fz, p1, p2 = (G.seeded("short lincheck %s %d" % (t, n), n) for t in ("fz", "p1", "p2"))
+        mz, r = [G.seeded("short lincheck mz %d %d" % (n, k), n) for k in range(2)], G.seeded("short lincheck r", 2)
+        got = on_device(lib, [fz, p1, p2] + mz, n, lambda p, o: lib.lincheck_dev(p[0], p[3:], r, p[1], p[2], n, o, words=1))
+        assert np.array_equal(got, oracle.lincheck_combine(fz, mz, r, p1, p2)), n
+    base, init = G.elem(int(G.seeded("pow base", 1)[0, 0]) | BIT63), G.elem(int(G.seeded("pow init", 1)[0, 0]))
+    for count in (2, 3):
+        got = on_device(lib, [], count, lambda p, o: lib.pow_table_dev(o, count, base, init, words=1))
+        want = [init.reshape(1, 1)]
+        while len(want) < count:
+            want.append(oracle.gf_mul(want[-1], base.reshape(1, 1)))
+        assert np.array_equal(got, np.concatenate(want)), count
+    big_basis, big_shift = codeword_domain(9)
+    ev = lambda c: oracle.additive_fft(c, big_basis, big_shift)
+    for basis, shift, counts in ((G.std_basis(0), G.elem(BIT63 | 0x80), (1, 2, 3, 300)), (G.std_basis(0), G.elem(0), (2, 257)), (G.std_basis(6), G.elem(BIT63 | 0x80), (65,))):
+        N = 1 << basis.shape[0]
+        Z = _vanishing_coefficients(basis, shift)
+        assert Z.shape[0] == N + 1 and int(Z[N, 0]) == 1
+        for n_coeffs in counts:
+            poly = G.seeded("short polydiv %d %d" % (N, n_coeffs), n_coeffs)
+            M = n_coeffs - N
+            got = on_device(lib, [poly], M, lambda p, o: lib.poly_div_vanishing_dev(p[0], n_coeffs, basis, shift, o, words=1))
+            assert got.shape[0] == M
+            if M == 0:
+                continue
+            remainder = poly ^ _poly_mul(got, Z)
+            assert not remainder[N:].any(), (N, n_coeffs, "the remainder has degree >= |H|")
+            assert np.array_equal(oracle.gf_mul(ev(got), ev(Z)) ^ ev(remainder[:N]), ev(poly)), (N, n_coeffs)
+
+
+def run_placed(lib, inputs, out_count, call, offsets, alias=None):
+    """call(pointers of the inputs, pointer of the output) with input i placed offsets[i] bytes past a 16-byte boundary and the output offsets[-1]
+    past one, or over input `alias`; (the output, the library's profile of the call)"""
+    with Device(lib) as dev:
+        ptrs = []
+        for a, off in zip(inputs, offsets):
+            dev.off = off
+            ptrs.append(dev.put(a))
+        dev.off = offsets[-1]
+        out = ptrs[alias] if alias is not None else dev.empty(8 * max(out_count, 1))
+        lib.profile_begin()
+        call(ptrs, out)
+        prof = lib.profile_report()
+        return dev.get(out, out_count), prof
+
+
+def pair_form_entries(lib):
+    """(profile label, inputs, output length, call) of every entry that has a two-elements-per-lane form, at a length that ends in half a pair
+    (513) or on a domain of 2^9"""
+    n, m = 513, 9
+    basis, shift = codeword_domain(m)
+    mu = G.elem(int(G.seeded("sumcheck mu", 1)[0, 0]) | BIT63)
+    coef, constant, r = G.seeded("placed lincomb coef", 3), G.elem(int(G.seeded("lincomb constant", 1)[0, 0])), G.seeded("placed lincheck r", 2)
+    vec = lambda tag, count: [G.seeded("placed %s %d" % (tag, k), count) for k in range(5)]
+    sb, sshift = basis[:6], G.elem(0)
+    return [
+        ("k64_add", vec("add", n)[:2], n, lambda p, o: lib.field_add_dev(p[0], p[1], o, n, words=1)),
+        ("k64_lincomb", vec("lincomb", n)[:3], n, lambda p, o: lib.lincomb_dev(p, coef, n, o, words=1)),
+        ("k64_lincomb", vec("affine", n)[:3], n, lambda p, o: lib.lincomb_affine_dev(p, coef, constant, n, o, words=1)),
+        ("k64_lincheck", vec("lincheck", n), n, lambda p, o: lib.lincheck_dev(p[0], p[3:], r, p[1], p[2], n, o, words=1)),
+        ("k64_rowcheck", vec("rowcheck", 1 << m)[:3], 1 << m, lambda p, o: lib.rowcheck_dev(p[0], p[1], p[2], basis, shift, 4, G.elem(0x55), o, words=1)),
+        ("k64_fz", vec("fz", 1 << m)[:2], 1 << m, lambda p, o: lib.fz_dev(p[0], p[1], basis, shift, basis[:4], G.elem(BIT63 | 9), o, words=1)),
+        ("k64_sumcheck_g_zero_sum", vec("sumcheck 0", 1 << m)[:2], 1 << m,
+         lambda p, o: lib.sumcheck_g_dev(p[0], p[1], basis, shift, sb, sshift, G.elem(0), o, words=1)),
+        ("k64_sumcheck_g", vec("sumcheck mu", 1 << m)[:2], 1 << m, lambda p, o: lib.sumcheck_g_dev(p[0], p[1], basis, shift, sb, sshift, mu, o, words=1)),
+    ]
+
+
+def _for_each_entry(lib, body):
+    for label, inputs, out_count, call in pair_form_entries(lib):
+        aligned, prof = run_placed(lib, inputs, out_count, call, [0] * (len(inputs) + 1))
+        assert prof.get(label, (0,))[0] == 1, label
+        body(label, inputs, out_count, call, aligned)
+
+
+def check_mixed_placements(lib):
+    """exactly one vector, each argument in turn and the output last, 8 bytes past a 16-byte boundary: the entry takes one element per lane
+    (the same profile label), launches once and returns the all-aligned result"""
+    def body(label, inputs, out_count, call, aligned):
+        for which in range(len(inputs) + 1):
+            offsets = [8 if i == which else 0 for i in range(len(inputs) + 1)]
+            got, prof = run_placed(lib, inputs, out_count, call, offsets)
+            assert prof.get(label, (0,))[0] == 1, (label, which)
+            assert np.array_equal(got, aligned), (label, which)
+    _for_each_entry(lib, body)
+
+
+def check_aliased_outputs(lib):
+    """the output over each input in turn, at both placements: every entry here is elementwise (position j of the output depends on position j
+    of the inputs), and the provers call them that way"""
+    def body(label, inputs, out_count, call, aligned):
+        for off in OFFSETS:
+            for which in range(len(inputs)):
+                got, prof = run_placed(lib, inputs, out_count, call, [off] * (len(inputs) + 1), alias=which)
+                assert prof.get(label, (0,))[0] == 1, (label, off, which)
+                assert np.array_equal(got, aligned), (label, off, which)
+    _for_each_entry(lib, body)
+
+
+def check_domain_table_turnover(lib):
+    """70 distinct codeword domains in a row through fz_dev (the library keeps the tables of 64 pairs of domains), then the first again"""
+    m = 6
+    basis, n = G.std_basis(m), 1 << m
+    ib, ishift = basis[:2], G.elem(BIT63 | 9)
+    fw, f1v = G.seeded("turnover w", n), G.seeded("turnover 1v", n)
+    shifts = [G.elem(BIT63 | ((t + 1) << 8)) for t in range(70)]
+    with Device(lib) as dev:
+        pw, pf, out = dev.put(fw), dev.put(f1v), dev.empty(8 * n)
+        first = None
+        for shift in shifts + shifts[:1]:
+            lib.fz_dev(pw, pf, basis, shift, ib, ishift, out, words=1)
+            got = dev.get(out, n)
+            assert np.array_equal(got, oracle.fz_additive(fw, f1v, basis, shift, ib, ishift)), int(shift[0])
+            first = got if first is None else first
+        assert np.array_equal(got, first)
 
 
 def check_null_pointers(lib):

@@ -220,6 +220,28 @@ def check_lde_ranges(lib):
         lib.free(do)
 
 
+def check_lde_upper_pass_whole(lib):
+    """2^13 coefficients, the smallest count whose plan has a k64_bfly_upper pass with the default tile, onto m = 15: every coset range of the four
+    against the oracle's transform, whole; the ranges of more than one coset go through the block-order staging (one group)"""
+    m, d = 15, 13
+    basis, shift = std_basis(m), elem((1 << 63) | 0x55)
+    coeffs = seeded("lde upper", 1 << d)
+    full = oracle.additive_fft(coeffs, basis, shift)
+    dc, do = lib.malloc(8 << d), lib.malloc(8 << m)
+    try:
+        lib.h2d(dc, coeffs)
+        for begin, count in ((0, 4), (1, 3), (3, 1)):
+            lib.profile_begin()
+            lib.additive_LDE_gf64_dev(dc, coeffs.shape[0], basis, shift, begin, count, do)
+            assert lib.profile_report().get("k64_bfly_upper", (0,))[0] >= 1, "the plan has no upper pass"
+            out = np.empty((count << d, 1), dtype=np.uint64)
+            lib.d2h(out, do)
+            assert np.array_equal(out, full[begin << d:(begin + count) << d]), (begin, count)
+    finally:
+        lib.free(dc)
+        lib.free(do)
+
+
 # ---- 5. fold ----
 def fold_domains():
     return [("std", std_basis(10), elem((1 << 63) | 0x77))] + [("derived %d" % i, b, s) for i, (b, s) in enumerate(derived_domains(0x1234))]

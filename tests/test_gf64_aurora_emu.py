@@ -47,6 +47,26 @@ def test_add():
     C.check_add(emu())
 
 
+def test_small_domains():
+    C.check_small_domains(emu())
+
+
+def test_short_vectors():
+    C.check_short_vectors(emu())
+
+
+def test_one_argument_off_the_boundary():
+    C.check_mixed_placements(emu())
+
+
+def test_output_over_an_input():
+    C.check_aliased_outputs(emu())
+
+
+def test_domain_table_turnover():
+    C.check_domain_table_turnover(emu())
+
+
 def test_null_pointers_are_refused():
     C.check_null_pointers(emu())
 

@@ -24,6 +24,10 @@ def test_lde_coset_ranges():
     C.check_lde_ranges(emu())
 
 
+def test_lde_upper_pass_whole():
+    C.check_lde_upper_pass_whole(emu())
+
+
 def test_ifft():
     C.check_ifft(emu())
 

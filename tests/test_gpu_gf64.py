@@ -39,6 +39,10 @@ def test_lde_coset_ranges(lib):
     C.check_lde_ranges(lib)
 
 
+def test_lde_upper_pass_whole(lib):
+    C.check_lde_upper_pass_whole(lib)
+
+
 def test_ifft(lib):
     C.check_ifft(lib)
 

@@ -30,11 +30,6 @@ def _is_pow2(n):
     return n > 0 and (n & (n - 1)) == 0
 
 
-def _words(field):
-    """uint64 words per element: three, or one over GF(2^64)"""
-    return getattr(field, "words", 3)
-
-
 class AuroraParameters:
     """aurora_snark_parameters + aurora_iop_parameters (non-zk, heuristic FRI soundness, optimistic-heuristic LDT-reducer
     soundness: the settings of profiling/instrument_aurora_snark.cpp:209-217 / boost_profile.cpp:11-21)."""
@@ -90,7 +85,7 @@ class FzVirtualOracle(VirtualOracle):
         self.d_f1v_coefficients = None
 
     def set_primary_input(self, primary_input):
-        w = _words(self.ops.field)
+        w = self.ops.field.words
         primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, w)
         if primary_input.shape[0] != self.k:
             raise ValueError("Primary input size does not match the previously declared size.")
@@ -140,7 +135,7 @@ class MultiLincheckVirtualOracle(VirtualOracle):
             prime_evals = alpha_powers
         else:
             idx = ops.upload_raw(self.S.reindex_by_subset_array(self.C.dim, self.C.size), ops.torch.int64)
-            prime_evals = ops.torch.zeros((self.S.size, _words(f)), dtype=ops.torch.int64, device=ops.device)
+            prime_evals = ops.torch.zeros((self.S.size, f.words), dtype=ops.torch.int64, device=ops.device)
             prime_evals[idx] = alpha_powers                                                    # :50-58
         # the two p_alpha evaluation vectors over the summation domain, back to back; the reference interpolates them here (:94-98)
         # and extends them in evaluated_contents (:112-118): both happen there, as one re-extension
@@ -341,11 +336,11 @@ class EncodedAuroraProtocol:
         equals z), is divided by Z_I and extended together with f_Az, f_Bz, f_Cz.  d_assignment: the variable assignment
         (1, primary, auxiliary) already resident on the device (then auxiliary_input may be None)."""
         ops = self.ops
-        primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, _words(ops.field))
+        primary_input = np.ascontiguousarray(primary_input, dtype=np.uint64).reshape(-1, ops.field.words)
         self.fz_oracle.set_primary_input(primary_input)                                                  # :485, :508-516
         f1v_over_variable_domain = ops.FFT(self.fz_oracle.d_f1v_coefficients, self.I.size, self.V)       # :517-518
         if d_assignment is None:
-            auxiliary_input = np.ascontiguousarray(auxiliary_input, dtype=np.uint64).reshape(-1, _words(ops.field))
+            auxiliary_input = np.ascontiguousarray(auxiliary_input, dtype=np.uint64).reshape(-1, ops.field.words)
             d_z = ops.upload(assignment_vector(ops.field, primary_input, auxiliary_input))               # :581-585
         else:
             d_z = d_assignment
@@ -517,7 +512,7 @@ class AuroraIOP:
 
 def assignment_vector(field, primary_input, auxiliary_input):
     """The variable assignment z = (1, primary, auxiliary) (r1cs_rs_iop.tcc:581-585) as host words."""
-    w = _words(field)
+    w = field.words
     return np.concatenate([field.one().reshape(1, w), np.asarray(primary_input, dtype=np.uint64).reshape(-1, w),
                            np.asarray(auxiliary_input, dtype=np.uint64).reshape(-1, w)])
 

@@ -256,7 +256,7 @@ class BCSProver:
         self.oracles[oid] = d_contents
 
     def submit_prover_message(self, handle, contents):
-        contents = np.ascontiguousarray(contents, dtype=np.uint64).reshape(-1, getattr(self.field, "words", 3))
+        contents = np.ascontiguousarray(contents, dtype=np.uint64).reshape(-1, self.field.words)
         if self.prover_messages[handle] is not None:
             raise ValueError("attempted to submit already submitted prover message")
         if self.prover_message_sizes[handle] != contents.shape[0]:

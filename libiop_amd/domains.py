@@ -3,8 +3,8 @@
 `Domain` mirrors the reference's tagged union field_subset<FieldT> (libiop/algebra/field_subset/field_subset.tcc:3-62,
 130-237): an affine subspace of GF(2^192) (subspace.tcc) or a multiplicative coset of the 181-bit prime field
 (subgroup.tcc).  `GF192` / `EdwardsFr` carry what differs between the arms — scalar arithmetic on Python ints for the
-handful of host-side constants, the hashchain extractor (blake2b.tcc:162-257), and the dispatch of every device operator
-to the matching C-ABI entry point (FFT_over_field_subset and friends dispatch on the domain type the same way,
+handful of host-side constants, the hashchain extractor (blake2b.tcc:162-257), and `entries`, the table that takes every device
+operator of `DeviceOps` to the matching C-ABI entry point (FFT_over_field_subset and friends dispatch on the domain type the same way,
 fft.tcc:407-475, fri_aux.tcc:5-34).  Citations are relative to the reference tree."""
 import hashlib
 
@@ -26,25 +26,26 @@ class Domain:
     def __init__(self, field, kind, basis=None, shift=None, log_n=None):
         self.field, self.kind = field, kind
         if kind == ADDITIVE:
-            w = getattr(field, "words", 3)                               # GF(2^192): three words; GF(2^64): one
-            self.basis = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, w)
-            self.shift = np.ascontiguousarray(shift, dtype=np.uint64).reshape(w)
+            self.basis = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, field.words)
+            self.shift = np.ascontiguousarray(shift, dtype=np.uint64).reshape(field.words)
             self.dim = self.basis.shape[0]
-        elif getattr(field, "words", 3) == 4:                            # alt_bn128 Fr: the same coset, four-word elements
+        else:
             self.dim = int(log_n)
-            self.shift_int = int(shift) % field.P
+            self.shift_int = int(shift) % field.P                        # canonical integer
             if self.shift_int == 0:
                 raise ValueError("coset_shift was supplied as 0, it was likely intended to be 1")
             self.shift = field.from_int(self.shift_int)
-            self.gen = field.subgroup_generator(self.dim)
-        else:
-            self.dim = int(log_n)
-            self.shift_int = int(shift) % la.EDWARDS_FR_MODULUS          # canonical integer
-            if self.shift_int == 0:
-                raise ValueError("coset_shift was supplied as 0, it was likely intended to be 1")
-            self.shift = la.edwards_to_montgomery([self.shift_int])[0]
-            self.gen = la.edwards_subgroup_generator(self.dim)          # subgroup.tcc:55-59
+            self.gen = field.subgroup_generator(self.dim)                # subgroup.tcc:55-59
         self.size = 1 << self.dim
+
+    # ---- what the device entries take (DeviceOps passes these on as they are) ----
+    def args(self):
+        """This domain as the domain an entry runs over: (basis, shift) of a subspace, (dim, gen, shift) of a coset."""
+        return (self.basis, self.shift) if self.additive else (self.dim, self.gen, self.shift)
+
+    def sub_args(self):
+        """This domain as an entry's second domain (input, summation, vanishing): (basis, shift) / (dim, shift)."""
+        return (self.basis, self.shift) if self.additive else (self.dim, self.shift)
 
     # ---- field_subset.tcc ----
     @property
@@ -70,17 +71,13 @@ class Domain:
 
     def element_outside_of_subset(self):
         """subspace.tcc:219-227 (standard basis): shift + FieldT(1 << dim); subgroup.tcc:311-315: shift * multiplicative_generator."""
-        if self.additive and getattr(self.field, "words", 3) == 1:
+        if self.additive:
             if not np.array_equal(self.basis, self.field.standard_basis(self.dim)):
                 raise ValueError("subspace.element_outside_of_subset() is only supported for standard basis")
-            return np.array([int(self.shift[0]) ^ (1 << self.dim)], dtype=np.uint64)
-        if self.additive:
-            if not np.array_equal(self.basis, la.standard_basis(self.dim)):
-                raise ValueError("subspace.element_outside_of_subset() is only supported for standard basis")
-            return host.gf_to_words(host.gf_from_words(self.shift) ^ (1 << self.dim))
-        if getattr(self.field, "words", 3) == 4:
-            return (self.shift_int * self.field.GENERATOR) % self.field.P
-        return (self.shift_int * la.EDWARDS_FR_GENERATOR) % la.EDWARDS_FR_MODULUS
+            out = self.shift.copy()
+            out[self.dim // 64] ^= np.uint64(1) << np.uint64(self.dim % 64)
+            return out
+        return (self.shift_int * self.field.GENERATOR) % self.field.P
 
     def reindex_by_subset(self, reindex_subset_dim, index):
         """:130-142; subgroup.tcc:149-173."""
@@ -116,12 +113,40 @@ class Domain:
 
 class GF192:
     """libff::gf192, additive arm."""
-    name, additive, elem_bytes, soundness_bits = "gf192", True, 24, 192
+    name, additive, elem_bytes, words, soundness_bits = "gf192", True, 24, 3, 192
+    standard_basis = staticmethod(la.standard_basis)
+    # DeviceOps operator (or optional slot) -> (Library method, its fixed keyword arguments)
+    entries = {
+        "FFT": ("additive_FFT_dev", {}),
+        "IFFT": ("additive_IFFT_dev", {}),
+        "LDE_batch": ("additive_LDE_batch_dev", {}),                    # optional: FFT_batch
+        "IFFT_batch": ("additive_IFFT_batch_dev", {}),                  # optional: IFFT_batch, IFFT_batch_packed
+        "reextend_batch": ("additive_reextend_batch_dev", {}),          # optional: reextend_packed, fused
+        "fold": ("fri_fold_dev", {}),
+        "ldt_combine": ("ldt_combine_dev", {}),
+        "rowcheck": ("rowcheck_dev", {}),
+        "fz": ("fz_dev", {}),
+        "sumcheck_g": ("sumcheck_g_dev", {}),
+        "lincheck": ("lincheck_dev", {}),
+        "lincomb": ("lincomb_dev", {}),
+        "lincomb_affine": ("lincomb_affine_dev", {}),
+        "sub": ("field_add_dev", {}),
+        "mul": ("gf192_mul_dev", {}),
+        "inv": ("field_inv_dev", {}),
+        "pow_table": ("pow_table_dev", {}),
+        "spmv": ("spmv_dev", {}),
+        "div": ("field_div_dev", {}),
+        "domain_offsets": ("domain_offsets_dev", {}),
+        "vanishing_evals": ("vanishing_evals_dev", {}),
+        "rational_combine": ("rational_combine_dev", {}),
+        "rational_sumcheck_constraint": ("rational_sumcheck_constraint_dev", {}),
+        "poly_div_vanishing": ("poly_div_vanishing_dev", {}),
+    }
 
     def domain(self, num_elements, shift=None):
         """field_subset(num_elements[, shift]) — field_subset.tcc:3-18,45-62."""
         d = _log2(num_elements)
-        return Domain(self, ADDITIVE, basis=la.standard_basis(d), shift=np.zeros(3, dtype=np.uint64) if shift is None else shift)
+        return Domain(self, ADDITIVE, basis=self.standard_basis(d), shift=np.zeros(3, dtype=np.uint64) if shift is None else shift)
 
     # host scalars: (3,) uint64 words
     def zero(self):
@@ -155,7 +180,7 @@ class GF192:
 
     def element_in_domain(self, domain, x):
         v = host.gf_from_words(self.add(x, domain.shift))
-        if not np.array_equal(domain.basis, la.standard_basis(domain.dim)):
+        if not np.array_equal(domain.basis, self.standard_basis(domain.dim)):
             raise NotImplementedError("membership test for a non-standard basis")
         return v < (1 << domain.dim)
 
@@ -172,6 +197,26 @@ class GF64:
     """libff::gf64 (x^64 + x^4 + x^3 + x + 1, one word), additive arm.  Host scalars are (1,) uint64 arrays; the handful of host-side
     products run on Python integers."""
     name, additive, elem_bytes, words, soundness_bits = "gf64", True, 8, 1, 64
+    # no batched or fused transform, nothing that only Fractal calls; lincomb_affine is there because its entry shares the kernel of lincomb
+    entries = {
+        "FFT": ("additive_FFT_gf64_dev", {}),
+        "IFFT": ("additive_IFFT_gf64_dev", {}),
+        "LDE": ("additive_LDE_gf64_dev", {}),                           # optional: reextend_packed, one vector at a time
+        "fold": ("evaluate_next_f_i_over_entire_domain_gf64_dev", {}),
+        "ldt_combine": ("ldt_combine_gf64_dev", {}),
+        "rowcheck": ("rowcheck_dev", {"words": 1}),
+        "fz": ("fz_dev", {"words": 1}),
+        "sumcheck_g": ("sumcheck_g_dev", {"words": 1}),
+        "lincheck": ("lincheck_dev", {"words": 1}),
+        "lincomb": ("lincomb_dev", {"words": 1}),
+        "lincomb_affine": ("lincomb_affine_dev", {"words": 1}),
+        "sub": ("field_add_dev", {"words": 1}),
+        "mul": ("gf64_mul_dev", {}),
+        "inv": ("gf64_inv_dev", {}),
+        "pow_table": ("pow_table_dev", {"words": 1}),
+        "spmv": ("spmv_dev", {"words": 1}),
+        "poly_div_vanishing": ("poly_div_vanishing_dev", {"words": 1}),
+    }
 
     @staticmethod
     def standard_basis(m):
@@ -273,8 +318,33 @@ class GF64:
 
 class EdwardsFr:
     """libff::edwards_Fr (181 bits, 3 Montgomery limbs), multiplicative arm."""
-    name, additive, elem_bytes, soundness_bits = "edwards_Fr", False, 24, 180
-    P = la.EDWARDS_FR_MODULUS
+    name, additive, elem_bytes, words, soundness_bits = "edwards_Fr", False, 24, 3, 180
+    P, GENERATOR = la.EDWARDS_FR_MODULUS, la.EDWARDS_FR_GENERATOR
+    # the transforms and the fold call the C entry itself (iopx_*): DeviceOps passes the words as pointers
+    entries = {
+        "FFT": ("iopx_mul_fft_fp3_dev", {}),
+        "IFFT": ("iopx_mul_ifft_fp3_dev", {}),
+        "IFFT_of_known_degree": ("iopx_mul_ifft_known_degree_fp3_dev", {}),
+        "fold": ("iopx_fri_fold_mul_fp3_dev", {}),
+        "ldt_combine": ("ldt_combine_multiplicative_dev", {}),
+        "rowcheck": ("rowcheck_multiplicative_dev", {}),
+        "fz": ("fz_multiplicative_dev", {}),
+        "sumcheck_g": ("sumcheck_g_multiplicative_dev", {}),
+        "lincheck": ("lincheck_dev", {"prime_field": True}),
+        "lincomb": ("lincomb_dev", {"prime_field": True}),
+        "lincomb_affine": ("lincomb_affine_dev", {"prime_field": True}),
+        "sub": ("fp3_sub_dev", {}),
+        "mul": ("fp3_mul_dev", {}),
+        "inv": ("field_inv_dev", {"prime_field": True}),
+        "pow_table": ("fp3_pow_table_dev", {}),
+        "spmv": ("spmv_dev", {"prime_field": True}),
+        "div": ("field_div_dev", {"prime_field": True}),
+        "domain_offsets": ("domain_offsets_multiplicative_dev", {}),
+        "vanishing_evals": ("vanishing_evals_multiplicative_dev", {}),
+        "rational_combine": ("rational_combine_dev", {"prime_field": True}),
+        "rational_sumcheck_constraint": ("rational_sumcheck_constraint_multiplicative_dev", {}),
+        "poly_div_vanishing": ("poly_div_vanishing_multiplicative_dev", {}),
+    }
 
     def domain(self, num_elements, shift=None):
         return Domain(self, MULTIPLICATIVE, shift=1 if shift is None else shift, log_n=_log2(num_elements))
@@ -285,6 +355,10 @@ class EdwardsFr:
 
     def from_int(self, v):
         return la.edwards_to_montgomery([int(v) % self.P])[0]
+
+    def subgroup_generator(self, log_order):
+        """multiplicative_generator^((p - 1) / 2^log_order) (subgroup.tcc:55-59)"""
+        return la.edwards_subgroup_generator(log_order)
 
     def zero(self):
         return np.zeros(3, dtype=np.uint64)
@@ -344,12 +418,42 @@ class EdwardsFr:
         return out
 
 
+def _ldt_combine_bn128(lib, d_oracles, degrees, random_coefficients, log_n, gen, shift, d_out):
+    """Library.ldt_combine_bn128_dev takes the generator last, unlike ldt_combine_multiplicative_dev: the one entry whose order is adapted."""
+    lib.ldt_combine_bn128_dev(d_oracles, degrees, random_coefficients, log_n, shift, d_out, gen=gen)
+
+
 class AltBn128Fr(EdwardsFr):
     """libff::alt_bn128_Fr (254 bits, 4 Montgomery limbs, x * 2^256 mod r), multiplicative arm: the device operators of the
     protocol layer.  No prover runs over it yet: challenge sampling (the hashchain extractor into this field) is not here."""
     name, additive, elem_bytes, soundness_bits, words = "alt_bn128_Fr", False, 32, 253, 4
     P = 21888242871839275222246405745257275088548364400416034343698204186575808495617
     GENERATOR, TWO_ADICITY = 5, 28
+    # the transforms and the fold call the C entry itself, as over edwards_Fr
+    entries = {
+        "FFT": ("iopx_mul_fft_bn128_dev", {}),
+        "IFFT": ("iopx_mul_ifft_bn128_dev", {}),
+        "IFFT_of_known_degree": ("iopx_mul_ifft_known_degree_bn128_dev", {}),
+        "fold": ("iopx_fri_fold_mul_bn128_dev", {}),
+        "ldt_combine": (_ldt_combine_bn128, {}),
+        "rowcheck": ("bn128_rowcheck_dev", {}),
+        "fz": ("bn128_fz_dev", {}),
+        "sumcheck_g": ("bn128_sumcheck_g_dev", {}),
+        "lincheck": ("bn128_lincheck_dev", {}),
+        "lincomb": ("bn128_lincomb_dev", {}),
+        "lincomb_affine": ("bn128_lincomb_affine_dev", {}),
+        "sub": ("bn128_sub_dev", {}),
+        "mul": ("bn128_mul_dev", {}),
+        "inv": ("bn128_inv_dev", {}),
+        "pow_table": ("bn128_pow_table_dev", {}),
+        "spmv": ("bn128_spmv_dev", {}),
+        "div": ("bn128_div_dev", {}),
+        "domain_offsets": ("bn128_domain_offsets_dev", {}),
+        "vanishing_evals": ("bn128_vanishing_evals_dev", {}),
+        "rational_combine": ("bn128_rational_combine_dev", {}),
+        "rational_sumcheck_constraint": ("bn128_rational_sumcheck_constraint_dev", {}),
+        "poly_div_vanishing": ("bn128_poly_div_vanishing_dev", {}),
+    }
 
     def to_int(self, words):
         v = sum(int(w) << (64 * k) for k, w in enumerate(np.asarray(words, dtype=np.uint64).reshape(4)))
@@ -388,23 +492,25 @@ class MerkleTree:
 
 
 class DeviceOps:
-    """The device operators of the path, dispatched on the domain type.  Vectors are (count, 3) int64 torch tensors on the
-    device the library is bound to; every call enqueues on the library's stream and returns without synchronising."""
+    """The device operators of the path: one body each, for every field.  What differs between the fields is data: `field.words` and
+    `field.elem_bytes` size the vectors, `field.entries` names the entry of each operator, and a Domain hands over its own arguments
+    (`Domain.args`, `Domain.sub_args`).  Vectors are (count, field.words) int64 torch tensors on the device the library is bound to; every
+    call enqueues on the library's stream and returns without synchronising."""
 
     def __new__(cls, lib, torch, device, field, *args, **kwargs):
-        # alt_bn128 Fr has its own entries and four-word vectors; GF(2^192) and edwards_Fr run this class as it is.  Only DeviceOps itself is
+        # alt_bn128 Fr and GF(2^64) have a class of their own (below); GF(2^192) and edwards_Fr run this class as it is.  Only DeviceOps itself is
         # redirected: a subclass (the sharded operators of libiop_amd/dist.py) is built as asked, and __init__ refuses the field there
-        if cls is DeviceOps and getattr(field, "words", 3) == 4:
+        if cls is DeviceOps and field.words == 4:
             cls = AltBn128DeviceOps
-        if cls is DeviceOps and getattr(field, "words", 3) == 1:        # GF(2^64): one-word vectors, the iopx_*_gf64 entries
+        if cls is DeviceOps and field.words == 1:
             cls = GF64DeviceOps
         return object.__new__(cls)
 
     def __init__(self, lib, torch, device, field):
         self.lib, self.torch, self.device, self.field = lib, torch, device, field
-        if getattr(field, "words", 3) == 4 and not isinstance(self, AltBn128DeviceOps):
+        if field.words == 4 and not isinstance(self, AltBn128DeviceOps):
             raise NotImplementedError("%s: no operators over a four-word field (alt_bn128 Fr runs on one GPU, through DeviceOps)" % type(self).__name__)
-        if getattr(field, "words", 3) == 1 and not isinstance(self, GF64DeviceOps):
+        if field.words == 1 and not isinstance(self, GF64DeviceOps):
             raise NotImplementedError("%s: no operators over a one-word field (gf64 runs on one GPU, through DeviceOps)" % type(self).__name__)
         # The provers interleave torch ops (copies, index assignments, torch.cat, buffers recycled by the caching allocator) with
         # library kernels WITHOUT host synchronisation: that is only ordered when both enqueue on the same stream.  Refuse the
@@ -413,6 +519,20 @@ class DeviceOps:
         if dev.type == "cuda" and not lib.shares_stream_with(torch, dev):
             raise RuntimeError("DeviceOps: the library must enqueue on torch's current stream — call "
                                "lib.set_stream(torch.cuda.current_stream().cuda_stream) before constructing the operators")
+
+    def _call(self, op, *args, **kwargs):
+        """The field's entry for `op` on `args`: a Library method by name, a C entry by name (iopx_*) or, for the one method whose argument
+        order differs from its twins', the function that adapts it.  A name the field's table lacks raises: nothing falls through to another
+        field's entry (libiop_amd/cpp/field_ops.hpp does the same)."""
+        if op not in self.field.entries:
+            raise NotImplementedError("%s: DeviceOps.%s has no entry over this field" % (self.field.name, op))
+        target, fixed = self.field.entries[op]
+        if callable(target):
+            target(self.lib, *args, **fixed, **kwargs)
+        elif target.startswith("iopx_"):                                 # the C entry itself: integers and addresses as they are, words as pointers
+            self.lib._check(getattr(self.lib.c, target)(*[a if isinstance(a, int) else _p(a) for a in args]))
+        else:
+            getattr(self.lib, target)(*args, **fixed, **kwargs)
 
     # ---- layout: one GPU holds every vector whole (libiop_amd/dist.py overrides these for contiguous-coset sharding) ----
     def local_size(self, domain):
@@ -425,14 +545,14 @@ class DeviceOps:
         return domains
 
     def query_responses(self, d_oracles, domain, positions):
-        """values[p][k] = oracle_k[positions[p]] (bcs_prover.tcc:187-197) as a (positions, oracles, 3) uint64 array."""
-        return self.lib.query_responses_dev([t.data_ptr() for t in d_oracles], 24, domain.size, positions)
+        """values[p][k] = oracle_k[positions[p]] (bcs_prover.tcc:187-197) as a (positions, oracles, field.words) uint64 array."""
+        return self.lib.query_responses_dev([t.data_ptr() for t in d_oracles], self.field.elem_bytes, domain.size, positions)
 
     def empty(self, n):
-        return self.torch.empty((max(int(n), 1), 3), dtype=self.torch.int64, device=self.device)[: int(n)]
+        return self.torch.empty((max(int(n), 1), self.field.words), dtype=self.torch.int64, device=self.device)[: int(n)]
 
     def upload(self, host_words):
-        a = np.ascontiguousarray(host_words, dtype=np.uint64).reshape(-1, 3)
+        a = np.ascontiguousarray(host_words, dtype=np.uint64).reshape(-1, self.field.words)
         t = self.empty(a.shape[0])
         if a.shape[0]:
             self.lib.h2d(t.data_ptr(), a)
@@ -447,7 +567,7 @@ class DeviceOps:
 
     def download(self, t, count=None):
         n = t.shape[0] if count is None else count
-        out = np.empty((n, 3), dtype=np.uint64)
+        out = np.empty((n, self.field.words), dtype=np.uint64)
         if n:
             self.lib.d2h(out, t.data_ptr())
         return out
@@ -456,60 +576,61 @@ class DeviceOps:
     def FFT(self, d_coeffs, n_coeffs, domain):
         """FFT_over_field_subset (fft.tcc:407-419)."""
         out = self.empty(domain.size)
-        if domain.additive:
-            self.lib.additive_FFT_dev(d_coeffs.data_ptr(), int(n_coeffs), domain.basis, domain.shift, out.data_ptr())
-        else:
-            self.lib._check(self.lib.c.iopx_mul_fft_fp3_dev(d_coeffs.data_ptr(), int(n_coeffs), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
+        self._call("FFT", d_coeffs.data_ptr(), int(n_coeffs), *domain.args(), out.data_ptr())
         return out
 
     def FFT_batch(self, d_coeffs_list, n_coeffs, domain):
-        """Several polynomials with the same coefficient count onto one domain."""
-        if domain.additive and len(d_coeffs_list) > 1:
+        """Several polynomials with the same coefficient count onto one domain: one batched extension where the field has it."""
+        if "LDE_batch" in self.field.entries and len(d_coeffs_list) > 1:
             outs = [self.empty(domain.size) for _ in d_coeffs_list]
             d = max(int(n_coeffs) - 1, 0).bit_length()
-            self.lib.additive_LDE_batch_dev([t.data_ptr() for t in d_coeffs_list], int(n_coeffs), domain.basis, domain.shift, 0,
-                                            1 << (domain.dim - d), [o.data_ptr() for o in outs])
+            self._call("LDE_batch", [t.data_ptr() for t in d_coeffs_list], int(n_coeffs), *domain.args(), 0, 1 << (domain.dim - d),
+                       [o.data_ptr() for o in outs])
             return outs
         return [self.FFT(t, n_coeffs, domain) for t in d_coeffs_list]
 
     def IFFT(self, d_evals, domain):
         """IFFT_over_field_subset (fft.tcc:421-433)."""
         out = self.empty(domain.size)
-        if domain.additive:
-            self.lib.additive_IFFT_dev(d_evals.data_ptr(), domain.basis, domain.shift, out.data_ptr())
-        else:
-            self.lib._check(self.lib.c.iopx_mul_ifft_fp3_dev(d_evals.data_ptr(), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
+        self._call("IFFT", d_evals.data_ptr(), *domain.args(), out.data_ptr())
         return out
 
     def IFFT_batch(self, d_evals_list, domain):
-        if domain.additive and len(d_evals_list) > 1:
+        if "IFFT_batch" in self.field.entries and len(d_evals_list) > 1:
             packed = self.empty(domain.size * len(d_evals_list))
             for k, t in enumerate(d_evals_list):
                 packed[k * domain.size:(k + 1) * domain.size].copy_(t)
-            out = self.empty(domain.size * len(d_evals_list))
-            self.lib.additive_IFFT_batch_dev(packed.data_ptr(), len(d_evals_list), domain.basis, domain.shift, out.data_ptr())
-            return [out[k * domain.size:(k + 1) * domain.size] for k in range(len(d_evals_list))]
+            return self.IFFT_batch_packed(packed, len(d_evals_list), domain)
         return [self.IFFT(t, domain) for t in d_evals_list]
 
     def IFFT_batch_packed(self, packed, batch, domain):
-        """`batch` vectors stored back to back in one tensor: one batched inverse transform (phase-1 passes shared)."""
+        """`batch` vectors stored back to back in one tensor: one batched inverse transform (phase-1 passes shared) where the field has it."""
         n = domain.size
-        if domain.additive and batch > 1:
+        if "IFFT_batch" in self.field.entries and batch > 1:
             out = self.empty(n * batch)
-            self.lib.additive_IFFT_batch_dev(packed.data_ptr(), batch, domain.basis, domain.shift, out.data_ptr())
+            self._call("IFFT_batch", packed.data_ptr(), batch, *domain.args(), out.data_ptr())
             return [out[k * n:(k + 1) * n] for k in range(batch)]
         return [self.IFFT(packed[k * n:(k + 1) * n], domain) for k in range(batch)]
 
     def reextend_packed(self, packed, batch, eval_domain, codeword_domain):
         """FFT_over_field_subset(IFFT_over_field_subset(v, eval_domain), codeword_domain) for `batch` vectors stored back to back.
-        When the evaluation domain is spanned by the first basis vectors of the codeword domain the coefficient form is skipped
-        (iopx_add_reextend_gf192_batch_dev); otherwise the two transforms run one after the other."""
-        n = eval_domain.size
-        if codeword_domain.additive and np.array_equal(eval_domain.basis, codeword_domain.basis[: eval_domain.dim]):
-            lo, cnt = self._coset_range(codeword_domain, eval_domain.dim)
-            outs = [self.empty(cnt << eval_domain.dim) for _ in range(batch)]
-            self.lib.additive_reextend_batch_dev(packed.data_ptr(), batch, codeword_domain.basis, eval_domain.dim, eval_domain.shift,
-                                                 codeword_domain.shift, lo, cnt, [o.data_ptr() for o in outs])
+        With a fused entry, and the evaluation domain spanned by the first basis vectors of the codeword domain, the coefficient form is
+        skipped (iopx_add_reextend_gf192_batch_dev).  With a coset-range extension alone, the inverse transforms are followed by one
+        extension per vector onto this process's cosets.  Otherwise the two transforms run one after the other."""
+        n, d = eval_domain.size, eval_domain.dim
+        if "reextend_batch" in self.field.entries and np.array_equal(eval_domain.basis, codeword_domain.basis[:d]):
+            lo, cnt = self._coset_range(codeword_domain, d)
+            outs = [self.empty(cnt << d) for _ in range(batch)]
+            self._call("reextend_batch", packed.data_ptr(), batch, codeword_domain.basis, d, eval_domain.shift, codeword_domain.shift, lo, cnt,
+                       [o.data_ptr() for o in outs])
+            return outs
+        if "LDE" in self.field.entries:
+            lo, cnt = self._coset_range(codeword_domain, d)
+            outs = []
+            for coeffs in self.IFFT_batch_packed(packed, batch, eval_domain):
+                out = self.empty(cnt << d)
+                self._call("LDE", coeffs.data_ptr(), n, *codeword_domain.args(), lo, cnt, out.data_ptr())
+                outs.append(out)
             return outs
         return self.FFT_batch(self.IFFT_batch_packed(packed, batch, eval_domain), n, codeword_domain)
 
@@ -523,19 +644,14 @@ class DeviceOps:
         if domain.additive:
             return self.IFFT(d_evals[: 1 << k], domain.get_subset_of_order(1 << k))
         out = self.empty(1 << k)
-        self.lib._check(self.lib.c.iopx_mul_ifft_known_degree_fp3_dev(d_evals.data_ptr(), int(degree), domain.dim, _p(domain.gen), _p(domain.shift),
-                                                                      out.data_ptr()))
+        self._call("IFFT_of_known_degree", d_evals.data_ptr(), int(degree), *domain.args(), out.data_ptr())
         return out
 
     # ---- FRI / Merkle ----
     def fold(self, d_f, domain, coset_size, x_i, next_domain=None):
         """evaluate_next_f_i_over_entire_domain (fri_aux.tcc:5-34)."""
         out = self.empty(domain.size // coset_size)
-        if domain.additive:
-            self.lib.fri_fold_dev(d_f.data_ptr(), domain.basis, domain.shift, coset_size, x_i, out.data_ptr())
-        else:
-            self.lib._check(self.lib.c.iopx_fri_fold_mul_fp3_dev(d_f.data_ptr(), domain.dim, _p(domain.gen), _p(domain.shift), int(coset_size),
-                                                                 _p(x_i), out.data_ptr()))
+        self._call("fold", d_f.data_ptr(), *domain.args(), int(coset_size), x_i, out.data_ptr())
         return out
 
     def solve_pow(self, challenge, pow_bitlen):
@@ -546,111 +662,80 @@ class DeviceOps:
         """construct_with_leaves_serialized_by_cosets + compute_inner_nodes over device-resident oracles."""
         leaves = domain.size // coset_size
         nodes = self.torch.empty((2 * leaves - 1, 32), dtype=self.torch.uint8, device=self.device)
-        self.lib.merkle_tree_dev([t.data_ptr() for t in d_oracles], 24, domain.size, coset_size, nodes.data_ptr(), domain_type=domain.domain_type)
+        self.lib.merkle_tree_dev([t.data_ptr() for t in d_oracles], self.field.elem_bytes, domain.size, coset_size, nodes.data_ptr(),
+                                 domain_type=domain.domain_type)
         return MerkleTree(self.lib, nodes, leaves)
 
     # ---- virtual oracles ----
     def rowcheck(self, d_az, d_bz, d_cz, codeword_domain, constraint_domain):
         out = self.empty(codeword_domain.size)
-        if codeword_domain.additive:
-            self.lib.rowcheck_dev(d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), codeword_domain.basis, codeword_domain.shift,
-                                  constraint_domain.dim, constraint_domain.shift, out.data_ptr())
-        else:
-            self.lib.rowcheck_multiplicative_dev(d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), codeword_domain.dim, codeword_domain.gen,
-                                                 codeword_domain.shift, constraint_domain.dim, constraint_domain.shift, out.data_ptr())
+        self._call("rowcheck", d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), *codeword_domain.args(), constraint_domain.dim,
+                   constraint_domain.shift, out.data_ptr())
         return out
 
     def fz(self, d_fw, d_f1v, codeword_domain, input_domain):
         out = self.empty(codeword_domain.size)
-        if codeword_domain.additive:
-            self.lib.fz_dev(d_fw.data_ptr(), d_f1v.data_ptr(), codeword_domain.basis, codeword_domain.shift, input_domain.basis, input_domain.shift,
-                            out.data_ptr())
-        else:
-            self.lib.fz_multiplicative_dev(d_fw.data_ptr(), d_f1v.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift,
-                                           input_domain.dim, input_domain.shift, out.data_ptr())
+        self._call("fz", d_fw.data_ptr(), d_f1v.data_ptr(), *codeword_domain.args(), *input_domain.sub_args(), out.data_ptr())
         return out
 
     def sumcheck_g(self, d_f, d_h, codeword_domain, summation_domain, claimed_sum):
         out = self.empty(codeword_domain.size)
-        if codeword_domain.additive:
-            self.lib.sumcheck_g_dev(d_f.data_ptr(), d_h.data_ptr(), codeword_domain.basis, codeword_domain.shift, summation_domain.basis,
-                                    summation_domain.shift, claimed_sum, out.data_ptr())
-        else:
-            self.lib.sumcheck_g_multiplicative_dev(d_f.data_ptr(), d_h.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift,
-                                                   summation_domain.dim, summation_domain.shift, claimed_sum, out.data_ptr())
+        self._call("sumcheck_g", d_f.data_ptr(), d_h.data_ptr(), *codeword_domain.args(), *summation_domain.sub_args(), claimed_sum, out.data_ptr())
         return out
 
     def lincheck(self, d_fz, d_mz, r_mz, d_p1, d_p2, n):
         out = self.empty(n)
-        self.lib.lincheck_dev(d_fz.data_ptr(), [t.data_ptr() for t in d_mz], r_mz, d_p1.data_ptr(), d_p2.data_ptr(), n, out.data_ptr(),
-                              prime_field=not self.field.additive)
+        self._call("lincheck", d_fz.data_ptr(), [t.data_ptr() for t in d_mz], r_mz, d_p1.data_ptr(), d_p2.data_ptr(), n, out.data_ptr())
         return out
 
     def ldt_combine(self, d_oracles, degrees, random_coefficients, domain):
         out = self.empty(domain.size)
-        ptrs = [t.data_ptr() for t in d_oracles]
-        if domain.additive:
-            self.lib.ldt_combine_dev(ptrs, degrees, random_coefficients, domain.basis, domain.shift, out.data_ptr())
-        else:
-            self.lib.ldt_combine_multiplicative_dev(ptrs, degrees, random_coefficients, domain.dim, domain.gen, domain.shift, out.data_ptr())
+        self._call("ldt_combine", [t.data_ptr() for t in d_oracles], degrees, random_coefficients, *domain.args(), out.data_ptr())
         return out
 
     def lincomb(self, d_oracles, coefficients, n):
         out = self.empty(n)
-        self.lib.lincomb_dev([t.data_ptr() for t in d_oracles], coefficients, n, out.data_ptr(), prime_field=not self.field.additive)
+        self._call("lincomb", [t.data_ptr() for t in d_oracles], coefficients, n, out.data_ptr())
         return out
 
     # ---- vector-sized steps of the encoded prover ----
     def sub(self, d_a, d_b):
         out = self.empty(d_a.shape[0])
-        if self.field.additive:
-            self.lib.field_add_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
-        else:
-            self.lib.fp3_sub_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
+        self._call("sub", d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
         return out
 
     def mul(self, d_a, d_b):
         out = self.empty(d_a.shape[0])
-        if self.field.additive:
-            self.lib.gf192_mul_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
-        else:
-            self.lib.fp3_mul_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
+        self._call("mul", d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
         return out
 
     def inv(self, d_a):
         out = self.empty(d_a.shape[0])
-        self.lib.field_inv_dev(d_a.data_ptr(), out.data_ptr(), d_a.shape[0], prime_field=not self.field.additive)
+        self._call("inv", d_a.data_ptr(), out.data_ptr(), d_a.shape[0])
         return out
 
     def pow_table(self, count, base, init):
         out = self.empty(count)
-        if self.field.additive:
-            self.lib.pow_table_dev(out.data_ptr(), count, base, init)
-        else:
-            self.lib.fp3_pow_table_dev(out.data_ptr(), count, base, init)
+        self._call("pow_table", out.data_ptr(), count, base, init)
         return out
 
     def spmv(self, csr, d_vec, d_out=None, scale=None, accumulate=False):
         out = self.empty(csr.rows) if d_out is None else d_out
-        self.lib.spmv_dev(csr.d_row_ptr.data_ptr(), csr.d_col.data_ptr(), csr.d_coeff.data_ptr(), csr.rows, d_vec.data_ptr(), out.data_ptr(),
-                          scale=scale, accumulate=accumulate, prime_field=not self.field.additive)
+        self._call("spmv", csr.d_row_ptr.data_ptr(), csr.d_col.data_ptr(), csr.d_coeff.data_ptr(), csr.rows, d_vec.data_ptr(), out.data_ptr(),
+                   scale=scale, accumulate=accumulate)
         return out
 
     # ---- vector-sized steps of the holographic prover ----
     def div(self, d_num, d_den):
         """d_num / d_den elementwise by batch inversion (d_num None: the inverses)."""
         out = self.empty(d_den.shape[0])
-        self.lib.field_div_dev(d_num.data_ptr() if d_num is not None else None, d_den.data_ptr(), out.data_ptr(), d_den.shape[0],
-                               prime_field=not self.field.additive)
+        self._call("div", d_num.data_ptr() if d_num is not None else None, d_den.data_ptr(), out.data_ptr(), d_den.shape[0])
         return out
 
     def domain_offsets(self, domain, point):
         """point - x over the whole domain."""
         out = self.empty(domain.size)
-        if domain.additive:
-            self.lib.domain_offsets_dev(domain.basis, domain.shift, point, out.data_ptr())
-        else:
-            self.lib.domain_offsets_multiplicative_dev(domain.dim, domain.gen, domain.shift, point, out.data_ptr())
+        self._call("domain_offsets", *domain.args(), point, out.data_ptr())
         return out
 
     def domain_elements(self, domain):
@@ -662,11 +747,7 @@ class DeviceOps:
     def vanishing_evals(self, vanishing_domain, domain, constant):
         """constant - Z_S(x) over the whole domain (S = vanishing_domain)."""
         out = self.empty(domain.size)
-        S = vanishing_domain
-        if domain.additive:
-            self.lib.vanishing_evals_dev(domain.basis, domain.shift, S.basis, S.shift, constant, out.data_ptr())
-        else:
-            self.lib.vanishing_evals_multiplicative_dev(domain.dim, domain.gen, domain.shift, S.dim, S.shift, constant, out.data_ptr())
+        self._call("vanishing_evals", *domain.args(), *vanishing_domain.sub_args(), constant, out.data_ptr())
         return out
 
     def lagrange_evals(self, x, S, evaldomain):
@@ -680,388 +761,77 @@ class DeviceOps:
 
     def lincomb_affine(self, d_oracles, coefficients, constant, n):
         out = self.empty(n)
-        self.lib.lincomb_affine_dev([t.data_ptr() for t in d_oracles], coefficients, constant, n, out.data_ptr(), prime_field=not self.field.additive)
+        self._call("lincomb_affine", [t.data_ptr() for t in d_oracles], coefficients, constant, n, out.data_ptr())
         return out
 
     def rational_combine(self, d_numerators, d_denominators, coefficients, n):
         """(combined numerator, combined denominator) of sum_i c_i N_i / D_i."""
         N, D = self.empty(n), self.empty(n)
-        self.lib.rational_combine_dev([t.data_ptr() for t in d_numerators], [t.data_ptr() for t in d_denominators], coefficients, n,
-                                      N.data_ptr(), D.data_ptr(), prime_field=not self.field.additive)
+        self._call("rational_combine", [t.data_ptr() for t in d_numerators], [t.data_ptr() for t in d_denominators], coefficients, n,
+                   N.data_ptr(), D.data_ptr())
         return N, D
 
     def rational_sumcheck_constraint(self, d_p, d_N, d_D, codeword_domain, summation_domain, claimed_sum):
         out = self.empty(codeword_domain.size)
         L, K = codeword_domain, summation_domain
-        if L.additive:
+        xinv = []
+        if L.additive:                                                   # the subspace entry also takes 1 / x over the codeword domain
             if not np.array_equal(K.basis, L.basis[: K.dim]):
                 raise ValueError("the summation domain must be spanned by a prefix of the codeword domain's basis")
-            xinv = self.div(None, self.domain_offsets(L, self.field.zero()))
-            self.lib.rational_sumcheck_constraint_dev(d_p.data_ptr(), d_N.data_ptr(), d_D.data_ptr(), xinv.data_ptr(), L.basis, L.shift, K.dim, K.shift,
-                                                      claimed_sum, out.data_ptr())
-        else:
-            self.lib.rational_sumcheck_constraint_multiplicative_dev(d_p.data_ptr(), d_N.data_ptr(), d_D.data_ptr(), L.dim, L.gen, L.shift, K.dim, K.shift,
-                                                                     claimed_sum, out.data_ptr())
+            xinv = [self.div(None, self.domain_offsets(L, self.field.zero()))]
+        self._call("rational_sumcheck_constraint", d_p.data_ptr(), d_N.data_ptr(), d_D.data_ptr(), *[t.data_ptr() for t in xinv], *L.args(), K.dim,
+                   K.shift, claimed_sum, out.data_ptr())
         return out
 
     def poly_div_vanishing(self, d_poly, n_coeffs, domain, out=None):
         """polynomial_over_vanishing_polynomial(P, Z_domain).first (written to the head of `out` when given)."""
         out = self.empty(max(n_coeffs - domain.size, 0)) if out is None else out
         if n_coeffs > domain.size:
-            if domain.additive:
-                self.lib.poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.basis, domain.shift, out.data_ptr())
-            else:
-                self.lib.poly_div_vanishing_multiplicative_dev(d_poly.data_ptr(), n_coeffs, domain.dim, domain.shift, out.data_ptr())
+            self._call("poly_div_vanishing", d_poly.data_ptr(), n_coeffs, *domain.sub_args(), out.data_ptr())
         return out
 
 
 class AltBn128DeviceOps(DeviceOps):
-    """DeviceOps over AltBn128Fr: (count, 4) int64 vectors, the iopx_*_bn128_dev entries.  Operators without a single-field
-    entry of their own (batches, re-extension) loop over the single-vector ones."""
-    W = 4
-
-    def query_responses(self, d_oracles, domain, positions):
-        return self.lib.query_responses_dev([t.data_ptr() for t in d_oracles], 32, domain.size, positions)
-
-    def empty(self, n):
-        return self.torch.empty((max(int(n), 1), 4), dtype=self.torch.int64, device=self.device)[: int(n)]
-
-    def upload(self, host_words):
-        a = np.ascontiguousarray(host_words, dtype=np.uint64).reshape(-1, 4)
-        t = self.empty(a.shape[0])
-        if a.shape[0]:
-            self.lib.h2d(t.data_ptr(), a)
-        return t
-
-    def download(self, t, count=None):
-        n = t.shape[0] if count is None else count
-        out = np.empty((n, 4), dtype=np.uint64)
-        if n:
-            self.lib.d2h(out, t.data_ptr())
-        return out
-
-    # ---- transforms ----
-    def FFT(self, d_coeffs, n_coeffs, domain):
-        out = self.empty(domain.size)
-        self.lib._check(self.lib.c.iopx_mul_fft_bn128_dev(d_coeffs.data_ptr(), int(n_coeffs), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
-        return out
-
-    def FFT_batch(self, d_coeffs_list, n_coeffs, domain):
-        return [self.FFT(t, n_coeffs, domain) for t in d_coeffs_list]
-
-    def IFFT(self, d_evals, domain):
-        out = self.empty(domain.size)
-        self.lib._check(self.lib.c.iopx_mul_ifft_bn128_dev(d_evals.data_ptr(), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
-        return out
-
-    def IFFT_batch(self, d_evals_list, domain):
-        return [self.IFFT(t, domain) for t in d_evals_list]
-
-    def IFFT_batch_packed(self, packed, batch, domain):
-        n = domain.size
-        return [self.IFFT(packed[k * n:(k + 1) * n], domain) for k in range(batch)]
-
-    def reextend_packed(self, packed, batch, eval_domain, codeword_domain):
-        return self.FFT_batch(self.IFFT_batch_packed(packed, batch, eval_domain), eval_domain.size, codeword_domain)
-
-    def _coset_range(self, codeword_domain, d):
-        raise NotImplementedError("coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
-
-    def IFFT_of_known_degree(self, d_evals, degree, domain):
-        out = self.empty(1 << _log2(degree))
-        self.lib._check(self.lib.c.iopx_mul_ifft_known_degree_bn128_dev(d_evals.data_ptr(), int(degree), domain.dim, _p(domain.gen), _p(domain.shift),
-                                                                        out.data_ptr()))
-        return out
-
-    # ---- FRI / Merkle ----
-    def fold(self, d_f, domain, coset_size, x_i, next_domain=None):
-        out = self.empty(domain.size // coset_size)
-        self.lib._check(self.lib.c.iopx_fri_fold_mul_bn128_dev(d_f.data_ptr(), domain.dim, _p(domain.gen), _p(domain.shift), int(coset_size),
-                                                               _p(x_i), out.data_ptr()))
-        return out
-
-    def merkle_tree(self, d_oracles, domain, coset_size):
-        leaves = domain.size // coset_size
-        nodes = self.torch.empty((2 * leaves - 1, 32), dtype=self.torch.uint8, device=self.device)
-        self.lib.merkle_tree_dev([t.data_ptr() for t in d_oracles], 32, domain.size, coset_size, nodes.data_ptr(), domain_type=domain.domain_type)
-        return MerkleTree(self.lib, nodes, leaves)
-
-    def ldt_combine(self, d_oracles, degrees, random_coefficients, domain):
-        out = self.empty(domain.size)
-        rc = np.ascontiguousarray(random_coefficients, dtype=np.uint64).reshape(-1, 4)
-        if rc.shape[0] != 2 * len(d_oracles):
-            raise ValueError("Expected the nunmber of random coefficients to be twice the number of oracles.")
-        ptrs = (la._vp * len(d_oracles))(*[t.data_ptr() for t in d_oracles])
-        deg = (la._sz * len(degrees))(*[int(d) for d in degrees])
-        self.lib._check(self.lib.c.iopx_ldt_combine_bn128_dev(ptrs, len(d_oracles), deg, _p(rc), domain.dim, _p(domain.gen), _p(domain.shift), out.data_ptr()))
-        return out
-
-    # ---- virtual oracles ----
-    def rowcheck(self, d_az, d_bz, d_cz, codeword_domain, constraint_domain):
-        out = self.empty(codeword_domain.size)
-        self.lib.bn128_rowcheck_dev(d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift,
-                                    constraint_domain.dim, constraint_domain.shift, out.data_ptr())
-        return out
-
-    def fz(self, d_fw, d_f1v, codeword_domain, input_domain):
-        out = self.empty(codeword_domain.size)
-        self.lib.bn128_fz_dev(d_fw.data_ptr(), d_f1v.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift, input_domain.dim,
-                              input_domain.shift, out.data_ptr())
-        return out
-
-    def sumcheck_g(self, d_f, d_h, codeword_domain, summation_domain, claimed_sum):
-        out = self.empty(codeword_domain.size)
-        self.lib.bn128_sumcheck_g_dev(d_f.data_ptr(), d_h.data_ptr(), codeword_domain.dim, codeword_domain.gen, codeword_domain.shift,
-                                      summation_domain.dim, summation_domain.shift, claimed_sum, out.data_ptr())
-        return out
-
-    def lincheck(self, d_fz, d_mz, r_mz, d_p1, d_p2, n):
-        out = self.empty(n)
-        self.lib.bn128_lincheck_dev(d_fz.data_ptr(), [t.data_ptr() for t in d_mz], r_mz, d_p1.data_ptr(), d_p2.data_ptr(), n, out.data_ptr())
-        return out
-
-    def lincomb(self, d_oracles, coefficients, n):
-        out = self.empty(n)
-        self.lib.bn128_lincomb_dev([t.data_ptr() for t in d_oracles], coefficients, n, out.data_ptr())
-        return out
-
-    # ---- vector-sized steps ----
-    def sub(self, d_a, d_b):
-        out = self.empty(d_a.shape[0])
-        self.lib.bn128_sub_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
-        return out
-
-    def mul(self, d_a, d_b):
-        out = self.empty(d_a.shape[0])
-        self.lib.bn128_mul_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
-        return out
-
-    def inv(self, d_a):
-        out = self.empty(d_a.shape[0])
-        self.lib.bn128_inv_dev(d_a.data_ptr(), out.data_ptr(), d_a.shape[0])
-        return out
-
-    def pow_table(self, count, base, init):
-        out = self.empty(count)
-        self.lib.bn128_pow_table_dev(out.data_ptr(), count, base, init)
-        return out
-
-    def spmv(self, csr, d_vec, d_out=None, scale=None, accumulate=False):
-        out = self.empty(csr.rows) if d_out is None else d_out
-        self.lib.bn128_spmv_dev(csr.d_row_ptr.data_ptr(), csr.d_col.data_ptr(), csr.d_coeff.data_ptr(), csr.rows, d_vec.data_ptr(), out.data_ptr(),
-                                scale=scale, accumulate=accumulate)
-        return out
-
-    def div(self, d_num, d_den):
-        out = self.empty(d_den.shape[0])
-        self.lib.bn128_div_dev(d_num.data_ptr() if d_num is not None else None, d_den.data_ptr(), out.data_ptr(), d_den.shape[0])
-        return out
-
-    def domain_offsets(self, domain, point):
-        out = self.empty(domain.size)
-        self.lib.bn128_domain_offsets_dev(domain.dim, domain.gen, domain.shift, point, out.data_ptr())
-        return out
-
-    def vanishing_evals(self, vanishing_domain, domain, constant):
-        out = self.empty(domain.size)
-        self.lib.bn128_vanishing_evals_dev(domain.dim, domain.gen, domain.shift, vanishing_domain.dim, vanishing_domain.shift, constant, out.data_ptr())
-        return out
-
-    def lincomb_affine(self, d_oracles, coefficients, constant, n):
-        out = self.empty(n)
-        self.lib.bn128_lincomb_affine_dev([t.data_ptr() for t in d_oracles], coefficients, constant, n, out.data_ptr())
-        return out
-
-    def rational_combine(self, d_numerators, d_denominators, coefficients, n):
-        N, D = self.empty(n), self.empty(n)
-        self.lib.bn128_rational_combine_dev([t.data_ptr() for t in d_numerators], [t.data_ptr() for t in d_denominators], coefficients, n,
-                                            N.data_ptr(), D.data_ptr())
-        return N, D
-
-    def rational_sumcheck_constraint(self, d_p, d_N, d_D, codeword_domain, summation_domain, claimed_sum):
-        out = self.empty(codeword_domain.size)
-        L, K = codeword_domain, summation_domain
-        self.lib.bn128_rational_sumcheck_constraint_dev(d_p.data_ptr(), d_N.data_ptr(), d_D.data_ptr(), L.dim, L.gen, L.shift, K.dim, K.shift,
-                                                        claimed_sum, out.data_ptr())
-        return out
-
-    def poly_div_vanishing(self, d_poly, n_coeffs, domain, out=None):
-        out = self.empty(max(n_coeffs - domain.size, 0)) if out is None else out
-        if n_coeffs > domain.size:
-            self.lib.bn128_poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.dim, domain.shift, out.data_ptr())
-        return out
+    """DeviceOps over AltBn128Fr: (count, 4) int64 vectors, the iopx_*_bn128_dev entries of AltBn128Fr.entries.  The field has no batched or
+    fused transform, so batches and the re-extension loop over the single-vector ones; a coset range has no alt_bn128 Fr form."""
 
 
 class GF64DeviceOps(DeviceOps):
-    """DeviceOps over GF64: (count, 1) int64 vectors, the iopx_*_gf64 entries.  It has what the FRI-only SNARK (libiop_amd/fri.py) calls;
-    every other operator of DeviceOps raises NotImplementedError — nothing falls through to a gf192 entry."""
-    W = 1
-
-    def query_responses(self, d_oracles, domain, positions):
-        return self.lib.query_responses_dev([t.data_ptr() for t in d_oracles], 8, domain.size, positions)
-
-    def empty(self, n):
-        return self.torch.empty((max(int(n), 1), 1), dtype=self.torch.int64, device=self.device)[: int(n)]
-
-    def upload(self, host_words):
-        a = np.ascontiguousarray(host_words, dtype=np.uint64).reshape(-1, 1)
-        t = self.empty(a.shape[0])
-        if a.shape[0]:
-            self.lib.h2d(t.data_ptr(), a)
-        return t
-
-    def download(self, t, count=None):
-        n = t.shape[0] if count is None else count
-        out = np.empty((n, 1), dtype=np.uint64)
-        if n:
-            self.lib.d2h(out, t.data_ptr())
-        return out
-
-    def FFT(self, d_coeffs, n_coeffs, domain):
-        out = self.empty(domain.size)
-        self.lib.additive_FFT_gf64_dev(d_coeffs.data_ptr(), int(n_coeffs), domain.basis, domain.shift, out.data_ptr())
-        return out
-
-    def IFFT(self, d_evals, domain):
-        out = self.empty(domain.size)
-        self.lib.additive_IFFT_gf64_dev(d_evals.data_ptr(), domain.basis, domain.shift, out.data_ptr())
-        return out
-
-    def IFFT_of_known_degree(self, d_evals, degree, domain):
-        k = _log2(degree)
-        return self.IFFT(d_evals[: 1 << k], domain.get_subset_of_order(1 << k))
-
-    def fold(self, d_f, domain, coset_size, x_i, next_domain=None):
-        out = self.empty(domain.size // coset_size)
-        self.lib.evaluate_next_f_i_over_entire_domain_gf64_dev(d_f.data_ptr(), domain.basis, domain.shift, coset_size, x_i, out.data_ptr())
-        return out
-
-    def merkle_tree(self, d_oracles, domain, coset_size):
-        leaves = domain.size // coset_size
-        nodes = self.torch.empty((2 * leaves - 1, 32), dtype=self.torch.uint8, device=self.device)
-        self.lib.merkle_tree_dev([t.data_ptr() for t in d_oracles], 8, domain.size, coset_size, nodes.data_ptr(), domain_type=domain.domain_type)
-        return MerkleTree(self.lib, nodes, leaves)
-
-    def ldt_combine(self, d_oracles, degrees, random_coefficients, domain):
-        out = self.empty(domain.size)
-        self.lib.ldt_combine_gf64_dev([t.data_ptr() for t in d_oracles], degrees, random_coefficients, domain.basis, domain.shift, out.data_ptr())
-        return out
-
-
-def _gf64_not_implemented(name):
-    def op(self, *args, **kwargs):
-        raise NotImplementedError("gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK is the only prover over this field)" % name)
-    op.__name__ = name
-    return op
-
-
-for _name in ("FFT_batch", "IFFT_batch", "IFFT_batch_packed", "reextend_packed", "_coset_range", "rowcheck", "fz", "sumcheck_g", "lincheck", "lincomb",
-              "sub", "mul", "inv", "pow_table", "spmv", "div", "domain_offsets", "domain_elements", "vanishing_evals", "lagrange_evals",
-              "lincomb_affine", "rational_combine", "rational_sumcheck_constraint", "poly_div_vanishing", "upload_raw"):
-    setattr(GF64DeviceOps, _name, _gf64_not_implemented(_name))
+    """DeviceOps over GF64: (count, 1) int64 vectors, the iopx_*_gf64 entries of GF64.entries.  It allows what the FRI-only SNARK
+    (libiop_amd/fri.py) calls; every other operator of DeviceOps raises NotImplementedError."""
 
 
 class GF64AuroraOps(GF64DeviceOps):
     """GF64DeviceOps plus what the Aurora prover (libiop_amd/aurora.py, libiop_amd/bcs.py) calls: the iopx_*_gf64_dev entries of
-    libiop_amd/csrc/gf64_ops.hip.  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  Batches and the
-    re-extension are one single-vector transform per vector (no fused or batched gf64 form); the operators only Fractal calls
-    (div, domain_offsets, domain_elements, vanishing_evals, lagrange_evals, rational_*) keep raising; lincomb_affine is there because its
-    entry shares the kernel of lincomb."""
+    libiop_amd/csrc/gf64_ops.hip.  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  The operators only Fractal
+    calls (div, domain_offsets, domain_elements, vanishing_evals, lagrange_evals, rational_*) keep raising."""
 
-    upload_raw = DeviceOps.upload_raw
 
-    # ---- transforms ----
-    def FFT_batch(self, d_coeffs_list, n_coeffs, domain):
-        return [self.FFT(t, n_coeffs, domain) for t in d_coeffs_list]
+_OPERATORS = frozenset(name for name, f in vars(DeviceOps).items() if callable(f) and not name.startswith("__") and name != "_call")
+_GF64_FRI = frozenset({"local_size", "mark_codeword_domain", "mark_fri_domains", "query_responses", "empty", "upload", "download", "FFT", "IFFT",
+                       "IFFT_of_known_degree", "fold", "solve_pow", "merkle_tree", "ldt_combine"})
+_GF64_AURORA = _GF64_FRI | {"upload_raw", "FFT_batch", "IFFT_batch", "IFFT_batch_packed", "reextend_packed", "_coset_range", "rowcheck", "fz",
+                            "sumcheck_g", "lincheck", "lincomb", "lincomb_affine", "sub", "mul", "inv", "pow_table", "spmv", "poly_div_vanishing"}
 
-    def IFFT_batch(self, d_evals_list, domain):
-        return [self.IFFT(t, domain) for t in d_evals_list]
 
-    def IFFT_batch_packed(self, packed, batch, domain):
-        n = domain.size
-        return [self.IFFT(packed[k * n:(k + 1) * n], domain) for k in range(batch)]
+def _allow_only(cls, allowed, why):
+    """Every operator of DeviceOps, set on `cls`: the base function where `allowed` names it, otherwise a stub that raises before it looks at
+    its arguments, whatever their number.  An operator added to DeviceOps later is refused until a set names it."""
+    def refusing(name):
+        def op(self, *args, **kwargs):
+            raise NotImplementedError(why % name)
+        op.__name__ = name
+        return op
+    if not allowed <= _OPERATORS:
+        raise TypeError("not operators of DeviceOps: %s" % sorted(allowed - _OPERATORS))
+    for name in _OPERATORS:
+        setattr(cls, name, getattr(DeviceOps, name) if name in allowed else refusing(name))
 
-    def _coset_range(self, codeword_domain, d):
-        return 0, 1 << (codeword_domain.dim - d)
 
-    def reextend_packed(self, packed, batch, eval_domain, codeword_domain):
-        """FFT(IFFT(v, eval_domain), codeword_domain) per vector: the inverse transform, then the extension onto this process's cosets."""
-        n = eval_domain.size
-        d = max(n - 1, 0).bit_length()
-        lo, cnt = self._coset_range(codeword_domain, d)
-        outs = []
-        for coeffs in self.IFFT_batch_packed(packed, batch, eval_domain):
-            out = self.empty(cnt << d)
-            self.lib.additive_LDE_gf64_dev(coeffs.data_ptr(), n, codeword_domain.basis, codeword_domain.shift, lo, cnt, out.data_ptr())
-            outs.append(out)
-        return outs
-
-    # ---- virtual oracles ----
-    def rowcheck(self, d_az, d_bz, d_cz, codeword_domain, constraint_domain):
-        out = self.empty(codeword_domain.size)
-        self.lib.rowcheck_dev(d_az.data_ptr(), d_bz.data_ptr(), d_cz.data_ptr(), codeword_domain.basis, codeword_domain.shift,
-                                   constraint_domain.dim, constraint_domain.shift, out.data_ptr(), words=1)
-        return out
-
-    def fz(self, d_fw, d_f1v, codeword_domain, input_domain):
-        out = self.empty(codeword_domain.size)
-        self.lib.fz_dev(d_fw.data_ptr(), d_f1v.data_ptr(), codeword_domain.basis, codeword_domain.shift, input_domain.basis, input_domain.shift,
-                             out.data_ptr(), words=1)
-        return out
-
-    def sumcheck_g(self, d_f, d_h, codeword_domain, summation_domain, claimed_sum):
-        out = self.empty(codeword_domain.size)
-        self.lib.sumcheck_g_dev(d_f.data_ptr(), d_h.data_ptr(), codeword_domain.basis, codeword_domain.shift, summation_domain.basis,
-                                     summation_domain.shift, claimed_sum, out.data_ptr(), words=1)
-        return out
-
-    def lincheck(self, d_fz, d_mz, r_mz, d_p1, d_p2, n):
-        out = self.empty(n)
-        self.lib.lincheck_dev(d_fz.data_ptr(), [t.data_ptr() for t in d_mz], r_mz, d_p1.data_ptr(), d_p2.data_ptr(), n, out.data_ptr(), words=1)
-        return out
-
-    def lincomb(self, d_oracles, coefficients, n):
-        out = self.empty(n)
-        self.lib.lincomb_dev([t.data_ptr() for t in d_oracles], coefficients, n, out.data_ptr(), words=1)
-        return out
-
-    def lincomb_affine(self, d_oracles, coefficients, constant, n):
-        out = self.empty(n)
-        self.lib.lincomb_affine_dev([t.data_ptr() for t in d_oracles], coefficients, constant, n, out.data_ptr(), words=1)
-        return out
-
-    # ---- vector-sized steps ----
-    def sub(self, d_a, d_b):
-        out = self.empty(d_a.shape[0])
-        self.lib.field_add_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0], words=1)
-        return out
-
-    def mul(self, d_a, d_b):
-        out = self.empty(d_a.shape[0])
-        self.lib.gf64_mul_dev(d_a.data_ptr(), d_b.data_ptr(), out.data_ptr(), d_a.shape[0])
-        return out
-
-    def inv(self, d_a):
-        out = self.empty(d_a.shape[0])
-        self.lib.gf64_inv_dev(d_a.data_ptr(), out.data_ptr(), d_a.shape[0])
-        return out
-
-    def pow_table(self, count, base, init):
-        out = self.empty(count)
-        self.lib.pow_table_dev(out.data_ptr(), count, base, init, words=1)
-        return out
-
-    def spmv(self, csr, d_vec, d_out=None, scale=None, accumulate=False):
-        out = self.empty(csr.rows) if d_out is None else d_out
-        self.lib.spmv_dev(csr.d_row_ptr.data_ptr(), csr.d_col.data_ptr(), csr.d_coeff.data_ptr(), csr.rows, d_vec.data_ptr(), out.data_ptr(),
-                               scale=scale, accumulate=accumulate, words=1)
-        return out
-
-    def poly_div_vanishing(self, d_poly, n_coeffs, domain, out=None):
-        out = self.empty(max(n_coeffs - domain.size, 0)) if out is None else out
-        if n_coeffs > domain.size:
-            self.lib.poly_div_vanishing_dev(d_poly.data_ptr(), n_coeffs, domain.basis, domain.shift, out.data_ptr(), words=1)
-        return out
+_GF64_WHY = "gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK and, through GF64AuroraOps, Aurora are the provers over this field)"
+_allow_only(GF64DeviceOps, _GF64_FRI, _GF64_WHY)
+_allow_only(GF64AuroraOps, _GF64_AURORA, _GF64_WHY)
+_allow_only(AltBn128DeviceOps, _OPERATORS - {"_coset_range"}, "DeviceOps.%s: coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
 
 
 def _p(words):

@@ -74,7 +74,7 @@ def _splitmix64(seed, index):
 def seeded_elements(field, seed, count):
     """count field elements from the seed: element i takes stream outputs 3 i .. 3 i + 2 as its words (GF(2^192): the raw
     words; the prime field: the 192-bit draw reduced mod p, then Montgomery form)."""
-    if field.additive and getattr(field, "words", 3) == 1:               # GF(2^64): element i is stream output i
+    if field.words == 1:               # GF(2^64): element i is stream output i
         return _splitmix64(seed, np.arange(count, dtype=np.uint64)).reshape(count, 1)
     w = _splitmix64(seed, np.arange(3 * count, dtype=np.uint64)).reshape(count, 3)
     if field.additive:
@@ -103,7 +103,7 @@ def generate_r1cs_example(ops, num_constraints, num_inputs, num_variables, seed)
         coef_h, ab_h = ops.download(coef), ops.download(ab)
         coef_h[c_zero] = ab_h[c_zero]
         coef = ops.upload(coef_h)
-    ones = np.broadcast_to(field.one(), (num_constraints, getattr(field, "words", 3)))
+    ones = np.broadcast_to(field.one(), (num_constraints, field.words))
     row_ptr = np.arange(num_constraints + 1, dtype=np.int64)
     A = CSRMatrix(ops, row_ptr, a_idx + 1, ones, num_constraints)
     B = CSRMatrix(ops, row_ptr, b_idx + 1, ones, num_constraints)

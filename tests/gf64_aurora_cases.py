@@ -568,6 +568,10 @@ def check_fractal_operators_refused(lib, torch, device):
     for name in ("div", "domain_offsets", "domain_elements", "vanishing_evals", "lagrange_evals", "rational_combine", "rational_sumcheck_constraint"):
         with pytest.raises(NotImplementedError, match="gf64"):
             getattr(ops, name)(None, None, None, None, None, None)
+    # lincomb_affine is the one operator of Fractal's that the class allows (its entry shares the kernel of lincomb) and the prover never calls
+    vecs, coef, constant = [G.seeded("ops affine %d" % k, 100) for k in range(3)], G.seeded("ops affine coef", 3), G.seeded("ops affine constant", 1)
+    got = ops.download(ops.lincomb_affine([ops.upload(v) for v in vecs], coef, constant[0], 100))
+    assert np.array_equal(got, xor_all([scaled(v, c) for v, c in zip(vecs, coef)]) ^ constant)
 
 
 def check_other_fields_unchanged(lib, torch, device):

@@ -115,14 +115,14 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
 // FFT_over_field_subset(IFFT_over_field_subset(v, H), L) for `batch` vectors stored back to back.  When H is spanned by the first basis
 // vectors of L the coefficient form is skipped (iopx_add_reextend_gf192_batch_dev); otherwise the two transforms run one after the other.
 // H_is_first_coset: H is the first coset of its span inside L (same shift), so the first |H| entries of each codeword are the input itself.
-// An 8-byte field (gf64) has no fused or batched re-extension: here and in the two forms below its transforms run one after the other.
+// An 8- or 16-byte field (gf64, gf128) has no fused or batched re-extension: here and in the two forms below its transforms run one after the other.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &packed, std::size_t batch, const field_subset<FieldT> &H,
                                                    const field_subset<FieldT> &L, bool H_is_first_coset = false)
 {
     const std::size_t n = H.num_elements();
     std::vector<device_vector<FieldT>> outs;
-    bool prefix = additive(L) && sizeof(FieldT) != 8 && H.dimension() <= L.dimension();
+    bool prefix = additive(L) && !detail::binary_only<FieldT>() && H.dimension() <= L.dimension();
     if (prefix) for (std::size_t i = 0; i < H.dimension(); ++i) prefix = prefix && std::memcmp(&H.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     if (prefix) {
         std::vector<uint64_t *> ptrs;
@@ -149,7 +149,7 @@ std::vector<device_vector<FieldT>> reextend2_packed(const device_vector<FieldT> 
                                                     std::size_t batch_b, const field_subset<FieldT> &Hb, const field_subset<FieldT> &L)
 {
     std::vector<device_vector<FieldT>> outs;
-    bool together = sizeof(FieldT) != 8 && additive(L) && additive(Ha) && additive(Hb) && Ha.dimension() == Hb.dimension() && Ha.dimension() > 0 && Ha.dimension() <= L.dimension();
+    bool together = !detail::binary_only<FieldT>() && additive(L) && additive(Ha) && additive(Hb) && Ha.dimension() == Hb.dimension() && Ha.dimension() > 0 && Ha.dimension() <= L.dimension();
     for (std::size_t i = 0; together && i < Ha.dimension(); ++i)
         together = std::memcmp(&Ha.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0 && std::memcmp(&Hb.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     if (!together) {
@@ -172,7 +172,7 @@ template<typename FieldT>
 std::vector<device_vector<FieldT>> FFT_and_reextend_packed(const device_vector<FieldT> &poly, const device_vector<FieldT> &packed, std::size_t batch,
                                                            const field_subset<FieldT> &H, const field_subset<FieldT> &L)
 {
-    bool prefix = sizeof(FieldT) != 8 && additive(L) && additive(H) && H.dimension() <= L.dimension() && poly.size() <= H.num_elements() && H.dimension() > 0;
+    bool prefix = !detail::binary_only<FieldT>() && additive(L) && additive(H) && H.dimension() <= L.dimension() && poly.size() <= H.num_elements() && H.dimension() > 0;
     if (prefix) for (std::size_t i = 0; i < H.dimension(); ++i) prefix = prefix && std::memcmp(&H.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     std::vector<device_vector<FieldT>> outs;
     if (!prefix) {
@@ -324,12 +324,12 @@ inline bool head_evaluation_enabled()
 {
     return iopx_get_option("IOPX_HEAD_EVAL", 1) != 0;   // looked up per proof (iopx_set_option): tests and bench.py prove the same instance both ways
 }
-// ... for FieldT: an 8-byte field (gf64) always runs the reference's schedule, whatever the option says — its re-extensions have no fused form and its
+// ... for FieldT: an 8- or 16-byte field (gf64, gf128) always runs the reference's schedule, whatever the option says — its re-extensions have no fused form and its
 // pointwise division by Z_I no entry, so nothing of the head route is built over it
 template<typename FieldT>
 bool head_evaluation()
 {
-    return sizeof(FieldT) != 8 && head_evaluation_enabled();
+    return !detail::binary_only<FieldT>() && head_evaluation_enabled();
 }
 template<typename FieldT>
 bool use_head(const field_subset<FieldT> &D, std::size_t count)

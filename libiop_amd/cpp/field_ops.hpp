@@ -35,6 +35,15 @@ struct prime_field_ops : vector_ops {
     decltype(&iopx_rational_sumcheck_constraint_fp3_dev) rational_sumcheck_constraint;
 };
 
+// ... and those a binary field has over its affine subspaces: the transforms, the FRI fold and domain chain, the subspace-shaped operators
+struct subspace_ops {
+    decltype(&iopx_add_fft_gf192_dev) add_fft; decltype(&iopx_add_lde_gf192_dev) add_lde; decltype(&iopx_add_ifft_gf192_dev) add_ifft;
+    decltype(&iopx_fri_fold_add_gf192_dev) fri_fold_add; decltype(&iopx_fri_domains_gf192) fri_domains; decltype(&iopx_ldt_combine_gf192_dev) ldt_combine;
+    decltype(&iopx_rowcheck_gf192_dev) rowcheck; decltype(&iopx_fz_gf192_dev) fz; decltype(&iopx_sumcheck_g_gf192_dev) sumcheck_g;
+    decltype(&iopx_poly_div_vanishing_gf192_dev) poly_div_vanishing; decltype(&iopx_domain_offsets_gf192_dev) domain_offsets;
+    decltype(&iopx_vanishing_evals_gf192_dev) vanishing_evals; decltype(&iopx_rational_sumcheck_constraint_gf192_dev) rational_sumcheck_constraint;
+};
+
 // the slots in the order of the declarations above, line for line
 inline constexpr vector_ops gf192 = {
     "gf192", 192, true,
@@ -48,6 +57,34 @@ inline constexpr vector_ops gf64 = {
     iopx_gf64_host_mul, iopx_gf64_inverse_host,
     iopx_gf64_add_dev, iopx_gf64_mul_dev, iopx_gf64_inv_dev, nullptr, iopx_gf64_pow_table_dev,
     iopx_lincomb_gf64_dev, iopx_lincomb_affine_gf64_dev, iopx_lincheck_gf64_dev, iopx_spmv_gf64_dev, nullptr,
+};
+// libff::gf128: the vector helpers of csrc/gf128.hip; the protocol-layer entries are not built over it (the FRI-only SNARK needs none)
+inline constexpr vector_ops gf128 = {
+    "gf128", 128, false,
+    iopx_gf128_host_mul, iopx_gf128_inverse_host,
+    iopx_gf128_add_dev, iopx_gf128_mul_dev, iopx_gf128_inv_dev, nullptr, nullptr,
+    nullptr, nullptr, nullptr, nullptr, nullptr,
+};
+inline constexpr subspace_ops gf192_subspace = {
+    iopx_add_fft_gf192_dev, iopx_add_lde_gf192_dev, iopx_add_ifft_gf192_dev,
+    iopx_fri_fold_add_gf192_dev, iopx_fri_domains_gf192, iopx_ldt_combine_gf192_dev,
+    iopx_rowcheck_gf192_dev, iopx_fz_gf192_dev, iopx_sumcheck_g_gf192_dev,
+    iopx_poly_div_vanishing_gf192_dev, iopx_domain_offsets_gf192_dev,
+    iopx_vanishing_evals_gf192_dev, iopx_rational_sumcheck_constraint_gf192_dev,
+};
+inline constexpr subspace_ops gf64_subspace = {
+    iopx_add_fft_gf64_dev, iopx_add_lde_gf64_dev, iopx_add_ifft_gf64_dev,
+    iopx_fri_fold_add_gf64_dev, iopx_fri_domains_gf64, iopx_ldt_combine_gf64_dev,
+    iopx_rowcheck_gf64_dev, iopx_fz_gf64_dev, iopx_sumcheck_g_gf64_dev,
+    iopx_poly_div_vanishing_gf64_dev, nullptr,
+    nullptr, nullptr,
+};
+inline constexpr subspace_ops gf128_subspace = {
+    iopx_add_fft_gf128_dev, iopx_add_lde_gf128_dev, iopx_add_ifft_gf128_dev,
+    iopx_fri_fold_add_gf128_dev, iopx_fri_domains_gf128, iopx_ldt_combine_gf128_dev,
+    nullptr, nullptr, nullptr,
+    nullptr, nullptr,
+    nullptr, nullptr,
 };
 inline constexpr prime_field_ops edwards_Fr = {
     { "edwards Fr", 180, true,
@@ -80,13 +117,17 @@ inline constexpr prime_field_ops alt_bn128_Fr = {
 
 // ---- selection ---------------------------------------------------------------------------------------------------------------------
 template<std::size_t Bytes, bool Additive> struct field;                   // by field_kind<FieldT> and sizeof(FieldT)
-template<> struct field<24, true> { static constexpr const vector_ops *vec = &gf192; static constexpr const prime_field_ops *prime = nullptr; static constexpr bool additive = true; };
-template<> struct field<8, true> { static constexpr const vector_ops *vec = &gf64; static constexpr const prime_field_ops *prime = nullptr; static constexpr bool additive = true; };
-template<> struct field<24, false> { static constexpr const prime_field_ops *vec = &edwards_Fr, *prime = &edwards_Fr; static constexpr bool additive = false; };
-template<> struct field<32, false> { static constexpr const prime_field_ops *vec = &alt_bn128_Fr, *prime = &alt_bn128_Fr; static constexpr bool additive = false; };
+template<const vector_ops *Vec, const subspace_ops *Sub> struct binary_field {
+    static constexpr const vector_ops *vec = Vec; static constexpr const subspace_ops *sub = Sub; static constexpr const prime_field_ops *prime = nullptr; static constexpr bool additive = true;
+};
+template<> struct field<24, true> : binary_field<&gf192, &gf192_subspace> {};
+template<> struct field<8, true> : binary_field<&gf64, &gf64_subspace> {};
+template<> struct field<16, true> : binary_field<&gf128, &gf128_subspace> {};
+template<> struct field<24, false> { static constexpr const prime_field_ops *vec = &edwards_Fr, *prime = &edwards_Fr; static constexpr const subspace_ops *sub = nullptr; static constexpr bool additive = false; };
+template<> struct field<32, false> { static constexpr const prime_field_ops *vec = &alt_bn128_Fr, *prime = &alt_bn128_Fr; static constexpr const subspace_ops *sub = nullptr; static constexpr bool additive = false; };
 // by size alone, for reference_binding.hpp (it does not see field_kind): the prime field of that size; the domain's kind tells gf192 from edwards Fr
 template<std::size_t Bytes> struct layout;
-template<> struct layout<24> : field<24, false> { static constexpr bool additive = true; };
+template<> struct layout<24> : field<24, false> { static constexpr const subspace_ops *sub = &gf192_subspace; static constexpr bool additive = true; };
 template<> struct layout<32> : field<32, false> {};
 
 [[noreturn]] inline void missing(const std::string &op, const char *field) { throw std::invalid_argument(op + ": " + field + " has no such entry"); }
@@ -103,6 +144,13 @@ template<class F, typename Fn> inline Fn entry(Fn prime_field_ops::*slot, const 
     if (!P || !(P->*slot)) missing(std::string(op) + " (multiplicative coset)", F::vec->name);
     return P->*slot;
 }
+template<class F, typename Fn> inline Fn entry(Fn subspace_ops::*slot, const char *op)
+{
+    const subspace_ops *S = F::sub;
+    if (!S) missing(std::string(op) + " (affine subspace)", F::vec->name);
+    if (!(S->*slot)) missing(op, F::vec->name);
+    return S->*slot;
+}
 
 // ---- domain-shaped operations --------------------------------------------------------------------------------------------------------
 // A domain as the C entries take it, all host pointers: basis[dim] + shift for a subspace (gen unused), shift * <gen> of order 2^dim for a coset (basis unused)
@@ -114,77 +162,71 @@ template<class F> inline bool subspace(const domain &D, const char *op)
     return D.additive;
 }
 
-// the binary field of the selection: one-word elements take the gf64 entry of a subspace operation, three-word ones the gf192 entry
-template<class F> inline bool one_word() { return static_cast<const vector_ops *>(F::vec) == &gf64; }
-
 // the transforms over affine subspaces, the FRI fold and the FRI domain chain (the arguments of the C entries)
 template<class F> inline int add_fft(const uint64_t *d_coeffs, std::size_t n_coeffs, const uint64_t *basis, std::size_t m, const uint64_t *shift, uint64_t *d_out)
 {
-    return (one_word<F>() ? iopx_add_fft_gf64_dev : iopx_add_fft_gf192_dev)(d_coeffs, n_coeffs, basis, m, shift, d_out);
+    return entry<F>(&subspace_ops::add_fft, "add_fft")(d_coeffs, n_coeffs, basis, m, shift, d_out);
 }
 template<class F> inline int add_lde(const uint64_t *d_coeffs, std::size_t n_coeffs, const uint64_t *basis, std::size_t m, const uint64_t *shift, std::size_t coset_begin,
                                      std::size_t coset_count, uint64_t *d_out)
 {
-    return (one_word<F>() ? iopx_add_lde_gf64_dev : iopx_add_lde_gf192_dev)(d_coeffs, n_coeffs, basis, m, shift, coset_begin, coset_count, d_out);
+    return entry<F>(&subspace_ops::add_lde, "add_lde")(d_coeffs, n_coeffs, basis, m, shift, coset_begin, coset_count, d_out);
 }
 template<class F> inline int add_ifft(const uint64_t *d_evals, const uint64_t *basis, std::size_t m, const uint64_t *shift, uint64_t *d_out)
 {
-    return (one_word<F>() ? iopx_add_ifft_gf64_dev : iopx_add_ifft_gf192_dev)(d_evals, basis, m, shift, d_out);
+    return entry<F>(&subspace_ops::add_ifft, "add_ifft")(d_evals, basis, m, shift, d_out);
 }
 template<class F> inline int fri_fold_add(const uint64_t *d_f, const uint64_t *basis, std::size_t m, const uint64_t *shift, std::size_t coset_size, const uint64_t *x_i, uint64_t *d_next)
 {
-    return (one_word<F>() ? iopx_fri_fold_add_gf64_dev : iopx_fri_fold_add_gf192_dev)(d_f, basis, m, shift, coset_size, x_i, d_next);
+    return entry<F>(&subspace_ops::fri_fold_add, "fri_fold_add")(d_f, basis, m, shift, coset_size, x_i, d_next);
 }
 template<class F> inline int fri_domains(const uint64_t *basis, std::size_t m, const uint64_t *shift, const std::size_t *localization, std::size_t num_reductions, uint64_t *out_bases,
                                          uint64_t *out_shifts)
 {
-    return (one_word<F>() ? iopx_fri_domains_gf64 : iopx_fri_domains_gf192)(basis, m, shift, localization, num_reductions, out_bases, out_shifts);
+    return entry<F>(&subspace_ops::fri_domains, "fri_domains")(basis, m, shift, localization, num_reductions, out_bases, out_shifts);
 }
 
 template<class F> inline int ldt_combine(const domain &L, const void *const *d_oracles, std::size_t num_oracles, const std::size_t *degrees, const uint64_t *coefficients, uint64_t *d_out)
 {
-    if (subspace<F>(L, "ldt_combine")) return (one_word<F>() ? iopx_ldt_combine_gf64_dev : iopx_ldt_combine_gf192_dev)(d_oracles, num_oracles, degrees, coefficients, L.basis, L.dim, L.shift, d_out);
+    if (subspace<F>(L, "ldt_combine")) return entry<F>(&subspace_ops::ldt_combine, "ldt_combine")(d_oracles, num_oracles, degrees, coefficients, L.basis, L.dim, L.shift, d_out);
     return entry<F>(&prime_field_ops::ldt_combine, "ldt_combine")(d_oracles, num_oracles, degrees, coefficients, L.dim, L.gen, L.shift, d_out);
 }
 template<class F> inline int rowcheck(const domain &L, const uint64_t *d_Az, const uint64_t *d_Bz, const uint64_t *d_Cz, std::size_t h_dim, const uint64_t *h_shift, uint64_t *d_out)
 {
-    if (subspace<F>(L, "rowcheck")) return (one_word<F>() ? iopx_rowcheck_gf64_dev : iopx_rowcheck_gf192_dev)(d_Az, d_Bz, d_Cz, L.basis, L.dim, L.shift, h_dim, h_shift, d_out);
+    if (subspace<F>(L, "rowcheck")) return entry<F>(&subspace_ops::rowcheck, "rowcheck")(d_Az, d_Bz, d_Cz, L.basis, L.dim, L.shift, h_dim, h_shift, d_out);
     return entry<F>(&prime_field_ops::rowcheck, "rowcheck")(d_Az, d_Bz, d_Cz, L.dim, L.gen, L.shift, h_dim, h_shift, d_out);
 }
 template<class F> inline int fz(const domain &L, const domain &I, const uint64_t *d_fw, const uint64_t *d_f1v, uint64_t *d_out)
 {
-    if (subspace<F>(L, "fz")) return (one_word<F>() ? iopx_fz_gf64_dev : iopx_fz_gf192_dev)(d_fw, d_f1v, L.basis, L.dim, L.shift, I.basis, I.dim, I.shift, d_out);
+    if (subspace<F>(L, "fz")) return entry<F>(&subspace_ops::fz, "fz")(d_fw, d_f1v, L.basis, L.dim, L.shift, I.basis, I.dim, I.shift, d_out);
     return entry<F>(&prime_field_ops::fz, "fz")(d_fw, d_f1v, L.dim, L.gen, L.shift, I.dim, I.shift, d_out);
 }
 template<class F> inline int sumcheck_g(const domain &L, const domain &H, const uint64_t *d_f, const uint64_t *d_h, const uint64_t *claimed_sum, uint64_t *d_out)
 {
-    if (subspace<F>(L, "sumcheck_g")) return (one_word<F>() ? iopx_sumcheck_g_gf64_dev : iopx_sumcheck_g_gf192_dev)(d_f, d_h, L.basis, L.dim, L.shift, H.basis, H.dim, H.shift, claimed_sum, d_out);
+    if (subspace<F>(L, "sumcheck_g")) return entry<F>(&subspace_ops::sumcheck_g, "sumcheck_g")(d_f, d_h, L.basis, L.dim, L.shift, H.basis, H.dim, H.shift, claimed_sum, d_out);
     return entry<F>(&prime_field_ops::sumcheck_g, "sumcheck_g")(d_f, d_h, L.dim, L.gen, L.shift, H.dim, H.shift, claimed_sum, d_out);
 }
 template<class F> inline int poly_div_vanishing(const domain &D, const uint64_t *d_poly, std::size_t n_coeffs, uint64_t *d_quotient)
 {
-    if (subspace<F>(D, "poly_div_vanishing")) return (one_word<F>() ? iopx_poly_div_vanishing_gf64_dev : iopx_poly_div_vanishing_gf192_dev)(d_poly, n_coeffs, D.basis, D.dim, D.shift, d_quotient);
+    if (subspace<F>(D, "poly_div_vanishing")) return entry<F>(&subspace_ops::poly_div_vanishing, "poly_div_vanishing")(d_poly, n_coeffs, D.basis, D.dim, D.shift, d_quotient);
     return entry<F>(&prime_field_ops::poly_div_vanishing, "poly_div_vanishing")(d_poly, n_coeffs, D.dim, D.shift, d_quotient);
 }
 template<class F> inline int domain_offsets(const domain &D, const uint64_t *point, uint64_t *d_out)
 {
-    if (one_word<F>()) missing("domain_offsets", F::vec->name);
-    if (subspace<F>(D, "domain_offsets")) return iopx_domain_offsets_gf192_dev(D.basis, D.dim, D.shift, point, d_out);
+    if (subspace<F>(D, "domain_offsets")) return entry<F>(&subspace_ops::domain_offsets, "domain_offsets")(D.basis, D.dim, D.shift, point, d_out);
     return entry<F>(&prime_field_ops::domain_offsets, "domain_offsets")(D.dim, D.gen, D.shift, point, d_out);
 }
 template<class F> inline int vanishing_evals(const domain &D, const domain &S, const uint64_t *constant, uint64_t *d_out)
 {
-    if (one_word<F>()) missing("vanishing_evals", F::vec->name);
-    if (subspace<F>(D, "vanishing_evals")) return iopx_vanishing_evals_gf192_dev(D.basis, D.dim, D.shift, S.basis, S.dim, S.shift, constant, d_out);
+    if (subspace<F>(D, "vanishing_evals")) return entry<F>(&subspace_ops::vanishing_evals, "vanishing_evals")(D.basis, D.dim, D.shift, S.basis, S.dim, S.shift, constant, d_out);
     return entry<F>(&prime_field_ops::vanishing_evals, "vanishing_evals")(D.dim, D.gen, D.shift, S.dim, S.shift, constant, d_out);
 }
 // d_xinv: 1 / x over L, read by the subspace arm only
 template<class F> inline int rational_sumcheck_constraint(const domain &L, const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, const uint64_t *d_xinv, std::size_t k_dim,
                                                           const uint64_t *k_shift, const uint64_t *claimed_sum, uint64_t *d_out)
 {
-    if (one_word<F>()) missing("rational_sumcheck_constraint", F::vec->name);
     if (subspace<F>(L, "rational_sumcheck_constraint"))
-        return iopx_rational_sumcheck_constraint_gf192_dev(d_p, d_N, d_D, d_xinv, L.basis, L.dim, L.shift, k_dim, k_shift, claimed_sum, d_out);
+        return entry<F>(&subspace_ops::rational_sumcheck_constraint, "rational_sumcheck_constraint")(d_p, d_N, d_D, d_xinv, L.basis, L.dim, L.shift, k_dim, k_shift, claimed_sum, d_out);
     return entry<F>(&prime_field_ops::rational_sumcheck_constraint, "rational_sumcheck_constraint")(d_p, d_N, d_D, L.dim, L.gen, L.shift, k_dim, k_shift, claimed_sum, d_out);
 }
 

@@ -1,4 +1,4 @@
-// Plain field-element types for C++ callers that do not link libff: 8 raw bytes with the layout of libff::gf64, 24 raw bytes with the layout of libff::gf192 (three
+// Plain field-element types for C++ callers that do not link libff: 8 raw bytes with the layout of libff::gf64, 16 with that of libff::gf128, 24 raw bytes with the layout of libff::gf192 (three
 // little-endian words, polynomial basis) / libff::edwards_Fr (three Montgomery limbs), 32 with that of libff::alt_bn128_Fr (four).
 // They provide what the mirror asks of a FieldT — construction from an integer, ==, + — through the library's host helpers; a libiop
 // integration uses libff's own types instead.
@@ -29,6 +29,18 @@ struct gf64 {
     gf64 &operator+=(const gf64 &o) { w[0] ^= o.w[0]; return *this; }
 };
 template<> struct field_kind<gf64> { static const field_subset_type type = affine_subspace_type; };
+
+// 16 raw bytes with the layout of libff::gf128 (two little-endian words, polynomial basis, x^128 + x^7 + x^2 + x + 1)
+struct gf128 {
+    uint64_t w[2];
+    gf128() : w{ 0, 0 } {}
+    explicit gf128(uint64_t v) : w{ v, 0 } {}
+    bool operator==(const gf128 &o) const { return w[0] == o.w[0] && w[1] == o.w[1]; }
+    bool operator!=(const gf128 &o) const { return !(*this == o); }
+    gf128 operator+(const gf128 &o) const { gf128 r; r.w[0] = w[0] ^ o.w[0]; r.w[1] = w[1] ^ o.w[1]; return r; }
+    gf128 &operator+=(const gf128 &o) { w[0] ^= o.w[0]; w[1] ^= o.w[1]; return *this; }
+};
+template<> struct field_kind<gf128> { static const field_subset_type type = affine_subspace_type; };
 
 struct edwards_Fr_element {
     uint64_t w[3];

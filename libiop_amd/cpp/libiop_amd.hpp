@@ -51,6 +51,8 @@ enum field_subset_type { affine_subspace_type = 1, multiplicative_coset_type = 2
 template<typename FieldT> struct field_kind;
 
 namespace detail {
+// a field with affine subspaces only, told by its size: libff::gf64 (8 bytes) and gf128 (16); 24 bytes is gf192 or edwards_Fr, 32 alt_bn128_Fr
+template<typename FieldT> constexpr bool binary_only() { return sizeof(FieldT) == 8 || sizeof(FieldT) == 16; }
 inline std::size_t log2_ceil(std::size_t n) { std::size_t d = 0; while (((std::size_t)1 << d) < n) ++d; return d; }
 } // namespace detail
 
@@ -106,11 +108,15 @@ template<typename FieldT>
 class multiplicative_coset {
     std::size_t order_;
     FieldT g_, shift_;
-    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32 || sizeof(FieldT) == 8, "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
-    // by size: the mirror asks nothing of FieldT beyond its bytes.  An 8-byte field (gf64) is binary: field_subset<FieldT> names this class, but no
-    // coset of it can be built (the constructors refuse), so F is never used for it
-    typedef ops::layout<sizeof(FieldT) == 8 ? 24 : sizeof(FieldT)> F;
-    static void refuse_binary() { if constexpr (sizeof(FieldT) == 8) throw std::invalid_argument("gf64: affine subspaces only"); }
+    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32 || detail::binary_only<FieldT>(), "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
+    // by size: the mirror asks nothing of FieldT beyond its bytes.  An 8- or 16-byte field (gf64, gf128) is binary: field_subset<FieldT> names this
+    // class, but no coset of it can be built (the constructors refuse), so F is never used for it
+    typedef ops::layout<detail::binary_only<FieldT>() ? 24 : sizeof(FieldT)> F;
+    static void refuse_binary()
+    {
+        if constexpr (sizeof(FieldT) == 8) throw std::invalid_argument("gf64: affine subspaces only");
+        if constexpr (sizeof(FieldT) == 16) throw std::invalid_argument("gf128: affine subspaces only");
+    }
     typedef ops::prime_field_ops P;
     static FieldT host_mul(const FieldT &a, const FieldT &b)
     {
@@ -285,7 +291,7 @@ template<typename FieldT>
 std::vector<FieldT> FFT_over_field_subset(const std::vector<FieldT> coeffs, field_subset<FieldT> domain)
 {
     if constexpr (sizeof(FieldT) == 32) return multiplicative_FFT<FieldT>(coeffs, domain.coset());     // alt_bn128_Fr: cosets only
-    else if constexpr (sizeof(FieldT) == 8) return additive_FFT<FieldT>(coeffs, domain.subspace());    // gf64: subspaces only
+    else if constexpr (detail::binary_only<FieldT>()) return additive_FFT<FieldT>(coeffs, domain.subspace());    // gf64, gf128: subspaces only
     else {
         if (domain.type() == multiplicative_coset_type) return multiplicative_FFT<FieldT>(coeffs, domain.coset());
         return additive_FFT<FieldT>(coeffs, domain.subspace());
@@ -296,7 +302,7 @@ template<typename FieldT>
 std::vector<FieldT> IFFT_over_field_subset(const std::vector<FieldT> evals, field_subset<FieldT> domain)
 {
     if constexpr (sizeof(FieldT) == 32) return multiplicative_IFFT<FieldT>(evals, domain.coset());
-    else if constexpr (sizeof(FieldT) == 8) return additive_IFFT<FieldT>(evals, domain.subspace());
+    else if constexpr (detail::binary_only<FieldT>()) return additive_IFFT<FieldT>(evals, domain.subspace());
     else {
         if (domain.type() == multiplicative_coset_type) return multiplicative_IFFT<FieldT>(evals, domain.coset());
         return additive_IFFT<FieldT>(evals, domain.subspace());
@@ -310,7 +316,7 @@ std::vector<FieldT> IFFT_of_known_degree_over_field_subset(const std::vector<Fie
 {
     const std::size_t pow2 = (std::size_t)1 << detail::log2_ceil(degree);
     const field_subset<FieldT> minimal = domain.get_subset_of_order(pow2);
-    if constexpr (sizeof(FieldT) == 8) {                                                    // gf64: subspaces only
+    if constexpr (detail::binary_only<FieldT>()) {                                          // gf64, gf128: subspaces only
         const std::vector<FieldT> head(evals.begin(), evals.begin() + pow2);
         return additive_IFFT<FieldT>(head, minimal.subspace());
     } else
@@ -353,7 +359,7 @@ std::shared_ptr<std::vector<FieldT>> evaluate_next_f_i_over_entire_domain(
     if constexpr (sizeof(FieldT) != 32) {
         if (f_i_domain.type() == affine_subspace_type) return additive_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
     }
-    if constexpr (sizeof(FieldT) != 8)
+    if constexpr (!detail::binary_only<FieldT>())
     if (f_i_domain.type() == multiplicative_coset_type) return multiplicative_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
     throw std::invalid_argument("f_i_domain is of unsupported domain type");               // fri_aux.tcc:33
 }

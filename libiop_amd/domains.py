@@ -316,6 +316,93 @@ class GF64:
         return [domain] + [Domain(self, ADDITIVE, basis=b, shift=s) for b, s in chain[1:]]
 
 
+class GF128(GF64):
+    """libff::gf128 (x^128 + x^7 + x^2 + x + 1, two little-endian words), additive arm: the FRI-only SNARK.  Host scalars are (2,) uint64
+    arrays; the host-side products run on Python integers, as GF64's do."""
+    name, additive, elem_bytes, words, soundness_bits = "gf128", True, 16, 2, 128
+    # the transforms, the fold, the LDT combination and the vector helpers: the gf192 methods with two words per element
+    entries = {
+        "FFT": ("additive_FFT_dev", {"words": 2}),
+        "IFFT": ("additive_IFFT_dev", {"words": 2}),
+        "LDE": ("additive_LDE_dev", {"words": 2}),
+        "fold": ("fri_fold_dev", {"words": 2}),
+        "ldt_combine": ("ldt_combine_dev", {"words": 2}),
+        "sub": ("field_add_dev", {"words": 2}),
+        "mul": ("gf192_mul_dev", {"words": 2}),
+        "inv": ("field_inv_dev", {"words": 2}),
+    }
+    _MASK = (1 << 64) - 1
+
+    @staticmethod
+    def standard_basis(m):
+        """subspace.tcc:93-108 — basis element i is FieldT(1 << i)."""
+        return np.array([[(1 << i) & GF128._MASK, (1 << i) >> 64] for i in range(m)], dtype=np.uint64).reshape(m, 2)
+
+    def domain(self, num_elements, shift=None):
+        d = _log2(num_elements)
+        return Domain(self, ADDITIVE, basis=self.standard_basis(d), shift=np.zeros(2, dtype=np.uint64) if shift is None else shift)
+
+    @staticmethod
+    def _int(a):
+        w = np.asarray(a, dtype=np.uint64).reshape(-1)
+        return int(w[0]) | (int(w[1]) << 64)
+
+    @staticmethod
+    def _elem(v):
+        return np.array([v & GF128._MASK, v >> 64], dtype=np.uint64)
+
+    @staticmethod
+    def _mul(a, b):
+        r = 0
+        while b:
+            if b & 1:
+                r ^= a
+            b >>= 1
+            a <<= 1
+            if a >> 128:
+                a ^= (1 << 128) | 0x87
+        return r
+
+    def zero(self):
+        return np.zeros(2, dtype=np.uint64)
+
+    def inv(self, a, lib):
+        return lib.gf128_inverse_host(a)
+
+    def _subspace_poly(self, domain):
+        """coefficients c_i of prod_{v in span(basis)} (X - v) = sum_i c_i X^(2^i) (vanishing_polynomial.tcc:373-395)"""
+        def ev(c, x):
+            r = 0
+            for ci in c:
+                r ^= self._mul(ci, x)
+                x = self._mul(x, x)
+            return r
+        c = [1]
+        for b in domain.basis:
+            zb = ev(c, self._int(b))
+            nxt = [0] * (len(c) + 1)
+            for i, ci in enumerate(c):
+                nxt[i + 1] ^= self._mul(ci, ci)
+                nxt[i] ^= self._mul(ci, zb)
+            c = nxt
+        return c, ev
+
+    def squeeze(self, hashchain, n):
+        """blake2b_FieldT_randomness_extractor for a binary field of 16 bytes (blake2b.tcc:162-185, 231-257): element i = keyed
+        BLAKE2b(state || index, key = i, 16 bytes), the two raw words."""
+        hashchain.squeeze_index += 1
+        msg = hashchain.state + hashchain.squeeze_index.to_bytes(8, "little")
+        out = np.zeros((n, 2), dtype=np.uint64)
+        for i in range(n):
+            out[i] = np.frombuffer(hashlib.blake2b(msg, digest_size=16, key=i.to_bytes(8, "little")).digest(), dtype="<u8")
+        return out
+
+    def fri_domains(self, domain, localization, lib):
+        """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338), by the library's host-side helper."""
+        chain = lib.fri_additive_domains_gf128(domain.basis, domain.shift, localization)
+        return [domain] + [Domain(self, ADDITIVE, basis=b, shift=s) for b, s in chain[1:]]
+
+
 class EdwardsFr:
     """libff::edwards_Fr (181 bits, 3 Montgomery limbs), multiplicative arm."""
     name, additive, elem_bytes, words, soundness_bits = "edwards_Fr", False, 24, 3, 180
@@ -498,12 +585,14 @@ class DeviceOps:
     call enqueues on the library's stream and returns without synchronising."""
 
     def __new__(cls, lib, torch, device, field, *args, **kwargs):
-        # alt_bn128 Fr and GF(2^64) have a class of their own (below); GF(2^192) and edwards_Fr run this class as it is.  Only DeviceOps itself is
+        # alt_bn128 Fr, GF(2^64) and GF(2^128) have a class of their own (below); GF(2^192) and edwards_Fr run this class as it is.  Only DeviceOps itself is
         # redirected: a subclass (the sharded operators of libiop_amd/dist.py) is built as asked, and __init__ refuses the field there
         if cls is DeviceOps and field.words == 4:
             cls = AltBn128DeviceOps
         if cls is DeviceOps and field.words == 1:
             cls = GF64DeviceOps
+        if cls is DeviceOps and field.words == 2:
+            cls = GF128DeviceOps
         return object.__new__(cls)
 
     def __init__(self, lib, torch, device, field):
@@ -512,6 +601,8 @@ class DeviceOps:
             raise NotImplementedError("%s: no operators over a four-word field (alt_bn128 Fr runs on one GPU, through DeviceOps)" % type(self).__name__)
         if field.words == 1 and not isinstance(self, GF64DeviceOps):
             raise NotImplementedError("%s: no operators over a one-word field (gf64 runs on one GPU, through DeviceOps)" % type(self).__name__)
+        if field.words == 2 and not isinstance(self, GF128DeviceOps):
+            raise NotImplementedError("%s: no operators over a two-word field (gf128 runs on one GPU, through DeviceOps)" % type(self).__name__)
         # The provers interleave torch ops (copies, index assignments, torch.cat, buffers recycled by the caching allocator) with
         # library kernels WITHOUT host synchronisation: that is only ordered when both enqueue on the same stream.  Refuse the
         # unshared configuration instead of racing (libiop_amd/dist.py's collectives have their own host-synchronised fallback).
@@ -801,6 +892,11 @@ class GF64DeviceOps(DeviceOps):
     (libiop_amd/fri.py) calls; every other operator of DeviceOps raises NotImplementedError."""
 
 
+class GF128DeviceOps(DeviceOps):
+    """DeviceOps over GF128: (count, 2) int64 vectors, the iopx_*_gf128 entries through GF128.entries.  It allows what the FRI-only SNARK
+    (libiop_amd/fri.py) calls; every other operator of DeviceOps raises NotImplementedError."""
+
+
 class GF64AuroraOps(GF64DeviceOps):
     """GF64DeviceOps plus what the Aurora prover (libiop_amd/aurora.py, libiop_amd/bcs.py) calls: the iopx_*_gf64_dev entries of
     libiop_amd/csrc/gf64_ops.hip.  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  The operators only Fractal
@@ -831,6 +927,7 @@ def _allow_only(cls, allowed, why):
 _GF64_WHY = "gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK and, through GF64AuroraOps, Aurora are the provers over this field)"
 _allow_only(GF64DeviceOps, _GF64_FRI, _GF64_WHY)
 _allow_only(GF64AuroraOps, _GF64_AURORA, _GF64_WHY)
+_allow_only(GF128DeviceOps, _GF64_FRI, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(AltBn128DeviceOps, _OPERATORS - {"_coset_range"}, "DeviceOps.%s: coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
 
 

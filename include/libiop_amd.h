@@ -348,6 +348,40 @@ int iopx_gf128_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out
 int iopx_gf128_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 int iopx_gf128_inverse_host(const uint64_t *x, uint64_t *out);
 
+/* ---- GF(2^256): additive FFT / IFFT, FRI fold, LDT combination ---------------------------------- */
+/* The same operators for FieldT = libff::gf256 (x^256 + x^10 + x^5 + x^2 + 1): a field element is FOUR little-endian uint64 words (32 bytes),
+ * libff::gf256's in-memory layout.  Every entry takes the arguments of its _gf128 twin above with four words per element, makes the same
+ * argument checks and cites the same reference lines.  Element arrays need only the 8-byte alignment of uint64_t: a launch whose
+ * pointers are all 16-byte aligned moves an element in two 128-bit accesses, any other launch in four 64-bit ones (the profile reports
+ * the latter under the kernel's name + "_w64").  Merkle trees, query responses, membership proofs and the proof of work take
+ * elem_bytes = 32.  The protocol-layer kernels (Aurora, Fractal) are not built over gf256: only the FRI-only SNARK runs over it. */
+int iopx_add_fft_gf256_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
+                           const uint64_t *shift, uint64_t *d_out);
+int iopx_add_fft_gf256(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
+                       const uint64_t *shift, uint64_t *out);
+int iopx_add_lde_gf256_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
+                           const uint64_t *shift, size_t coset_begin, size_t coset_count, uint64_t *d_out);
+/* In place allowed (d_evals == d_out). */
+int iopx_add_ifft_gf256_dev(const uint64_t *d_evals, const uint64_t *basis, size_t m, const uint64_t *shift,
+                            uint64_t *d_out);
+int iopx_add_ifft_gf256(const uint64_t *evals, const uint64_t *basis, size_t m, const uint64_t *shift,
+                        uint64_t *out);
+int iopx_fri_fold_add_gf256_dev(const uint64_t *d_f_i, const uint64_t *basis, size_t m, const uint64_t *shift,
+                                size_t coset_size, const uint64_t *x_i, uint64_t *d_next);
+int iopx_fri_fold_add_gf256(const uint64_t *f_i, const uint64_t *basis, size_t m, const uint64_t *shift,
+                            size_t coset_size, const uint64_t *x_i, uint64_t *next);
+int iopx_fri_domains_gf256(const uint64_t *basis, size_t m, const uint64_t *shift, const size_t *localization, size_t num_reductions,
+                           uint64_t *out_bases, uint64_t *out_shifts);
+int iopx_ldt_combine_gf256_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees,
+                               const uint64_t *random_coefficients, const uint64_t *basis, size_t m, const uint64_t *shift,
+                               uint64_t *d_out);
+/* d_out[i] = d_a[i] * d_b[i];  d_out[i] = d_a[i]^-1 (zero maps to zero);  d_out[i] = d_a[i] + d_b[i];  the host scalars (the inverse of zero is refused) */
+int iopx_gf256_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
+int iopx_gf256_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
+int iopx_gf256_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
+int iopx_gf256_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
+int iopx_gf256_inverse_host(const uint64_t *x, uint64_t *out);
+
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
  * libiop/bcs/merkle_tree.tcc:92-151, 200-229 with blake2b_leafhash / blake2b_two_to_one_hash
@@ -715,6 +749,8 @@ int iopx_fp3_modulus(uint64_t *out);
  * per element.  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, and an Aurora instance
  * (iopx_aurora_instance_create, iopx_aurora_example_instance_create): the protocol-layer kernels are not built over gf128. */
 #define IOPX_FIELD_GF128 5
+/* libff::gf256: as gf128, coefficients 4 words per element; the refusals name gf256. */
+#define IOPX_FIELD_GF256 6
 /* bcs_hash_type (libiop/bcs/hashing/hash_enum.hpp:21-26), as iopx_poseidon_shipped_params takes it */
 #define IOPX_HASH_BLAKE2B 1
 #define IOPX_HASH_POSEIDON_STARKWARE 2

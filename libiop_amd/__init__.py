@@ -79,6 +79,9 @@ EXPORTED_SYMBOLS = [
     "iopx_add_fft_gf128_dev", "iopx_add_fft_gf128", "iopx_add_lde_gf128_dev", "iopx_add_ifft_gf128_dev", "iopx_add_ifft_gf128",
     "iopx_fri_fold_add_gf128_dev", "iopx_fri_fold_add_gf128", "iopx_fri_domains_gf128", "iopx_ldt_combine_gf128_dev",
     "iopx_gf128_mul_dev", "iopx_gf128_inv_dev", "iopx_gf128_add_dev", "iopx_gf128_host_mul", "iopx_gf128_inverse_host",
+    "iopx_add_fft_gf256_dev", "iopx_add_fft_gf256", "iopx_add_lde_gf256_dev", "iopx_add_ifft_gf256_dev", "iopx_add_ifft_gf256",
+    "iopx_fri_fold_add_gf256_dev", "iopx_fri_fold_add_gf256", "iopx_fri_domains_gf256", "iopx_ldt_combine_gf256_dev",
+    "iopx_gf256_mul_dev", "iopx_gf256_inv_dev", "iopx_gf256_add_dev", "iopx_gf256_host_mul", "iopx_gf256_inverse_host",
     "iopx_mem_check_stats",
 ]
 
@@ -133,6 +136,7 @@ def _ints_to_words4(values):
 FIELD_GF192, FIELD_EDWARDS_FR, FIELD_ALT_BN128_FR = 0, 1, 2                 # IOPX_FIELD_*
 FIELD_GF64 = 4                                                              # libff::gf64 (3 stays unknown to the C ABI)
 FIELD_GF128 = 5                                                             # libff::gf128: the FRI-only SNARK
+FIELD_GF256 = 6                                                             # libff::gf256: the FRI-only SNARK
 HASH_BLAKE2B, HASH_POSEIDON_STARKWARE, HASH_POSEIDON_HIGH_ALPHA = 1, 2, 3   # IOPX_HASH_*: the reference's bcs_hash_type
 
 
@@ -304,10 +308,11 @@ class Library:
                            ("iopx_fz_gf64_dev", "iopx_fz_gf192_dev"), ("iopx_sumcheck_g_gf64_dev", "iopx_sumcheck_g_gf192_dev"),
                            ("iopx_poly_div_vanishing_gf64_dev", "iopx_poly_div_vanishing_gf192_dev")):
             getattr(c, name).argtypes = list(getattr(c, twin).argtypes)
-        # GF(2^128): the prototypes of the gf64 entries, two words per element
+        # GF(2^128), GF(2^256): the prototypes of the gf64 entries, two and four words per element
         for name in ("add_fft_%s_dev", "add_fft_%s", "add_lde_%s_dev", "add_ifft_%s_dev", "add_ifft_%s", "fri_fold_add_%s_dev", "fri_fold_add_%s",
                      "fri_domains_%s", "ldt_combine_%s_dev", "%s_mul_dev", "%s_inv_dev", "%s_add_dev", "%s_host_mul", "%s_inverse_host"):
             getattr(c, "iopx_" + name % "gf128").argtypes = list(getattr(c, "iopx_" + name % "gf64").argtypes)
+            getattr(c, "iopx_" + name % "gf256").argtypes = list(getattr(c, "iopx_" + name % "gf64").argtypes)
 
     # ---- error translation (the exception types the reference throws) ----
     def _check(self, rc):
@@ -808,13 +813,13 @@ class Library:
     # ---- LDT reducer (ldt_reducer_aux.tcc:39-131) ----
     def ldt_combine_dev(self, d_oracles, degrees, random_coefficients, basis, shift, d_out, words=3):
         """combined_LDT_virtual_oracle::evaluated_contents over the affine subspace (basis, shift); device pointers.  words: 3 over gf192,
-        2 over gf128 (iopx_ldt_combine_gf128_dev)."""
+        2 over gf128 (iopx_ldt_combine_gf128_dev), 4 over gf256 (iopx_ldt_combine_gf256_dev)."""
         basis, shift, rc = _as_u64(basis, words), _as_u64(shift, words), _as_u64(random_coefficients, words)
         if rc.shape[0] != 2 * len(d_oracles):
             raise ValueError("Expected the nunmber of random coefficients to be twice the number of oracles.")
         ptrs = (_vp * len(d_oracles))(*d_oracles)
         deg = (_sz * len(degrees))(*[int(d) for d in degrees])
-        fn = self.c.iopx_ldt_combine_gf128_dev if words == 2 else self.c.iopx_ldt_combine_gf192_dev
+        fn = self.c.iopx_ldt_combine_gf128_dev if words == 2 else self.c.iopx_ldt_combine_gf256_dev if words == 4 else self.c.iopx_ldt_combine_gf192_dev
         self._check(fn(ptrs, len(d_oracles), deg, rc.ctypes.data_as(_u64p), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), _vp(d_out)))
 
     def ldt_combine_multiplicative_dev(self, d_oracles, degrees, random_coefficients, log_n, gen, shift, d_out):
@@ -1205,15 +1210,15 @@ class Library:
 
     # ---- device-pointer operators (integers are raw device addresses, e.g. torch.Tensor.data_ptr()) ----
     def additive_FFT_dev(self, d_coeffs, n_coeffs, basis, shift, d_out, words=3):
-        """words: 3 over gf192, 2 over gf128 (the iopx_*_gf128_dev entries) — here and in the other transform, fold and vector methods that take it"""
+        """words: 3 over gf192, 2 over gf128 (the iopx_*_gf128_dev entries), 4 over gf256 (the iopx_*_gf256_dev entries) — here and in the other transform, fold and vector methods that take it"""
         basis, shift = _as_u64(basis, words), _as_u64(shift, words)
-        fn = self.c.iopx_add_fft_gf128_dev if words == 2 else self.c.iopx_add_fft_gf192_dev
+        fn = self.c.iopx_add_fft_gf128_dev if words == 2 else self.c.iopx_add_fft_gf256_dev if words == 4 else self.c.iopx_add_fft_gf192_dev
         self._check(fn(_vp(d_coeffs), n_coeffs, basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), _vp(d_out)))
 
     def additive_LDE_dev(self, d_coeffs, n_coeffs, basis, shift, coset_begin, coset_count, d_out, words=3):
         """Cosets [coset_begin, +coset_count) of the transform (one GPU's shard of a codeword)."""
         basis, shift = _as_u64(basis, words), _as_u64(shift, words)
-        fn = self.c.iopx_add_lde_gf128_dev if words == 2 else self.c.iopx_add_lde_gf192_dev
+        fn = self.c.iopx_add_lde_gf128_dev if words == 2 else self.c.iopx_add_lde_gf256_dev if words == 4 else self.c.iopx_add_lde_gf192_dev
         self._check(fn(_vp(d_coeffs), n_coeffs, basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), coset_begin, coset_count, _vp(d_out)))
 
     def additive_IFFT_batch_dev(self, d_evals, batch, basis, shift, d_out):
@@ -1283,12 +1288,12 @@ class Library:
 
     def additive_IFFT_dev(self, d_evals, basis, shift, d_out, words=3):
         basis, shift = _as_u64(basis, words), _as_u64(shift, words)
-        fn = self.c.iopx_add_ifft_gf128_dev if words == 2 else self.c.iopx_add_ifft_gf192_dev
+        fn = self.c.iopx_add_ifft_gf128_dev if words == 2 else self.c.iopx_add_ifft_gf256_dev if words == 4 else self.c.iopx_add_ifft_gf192_dev
         self._check(fn(_vp(d_evals), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), _vp(d_out)))
 
     def fri_fold_dev(self, d_f, basis, shift, coset_size, x_i, d_next, words=3):
         basis, shift, x = _as_u64(basis, words), _as_u64(shift, words), _as_u64(x_i, words)
-        fn = self.c.iopx_fri_fold_add_gf128_dev if words == 2 else self.c.iopx_fri_fold_add_gf192_dev
+        fn = self.c.iopx_fri_fold_add_gf128_dev if words == 2 else self.c.iopx_fri_fold_add_gf256_dev if words == 4 else self.c.iopx_fri_fold_add_gf192_dev
         self._check(fn(_vp(d_f), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), int(coset_size), x.ctypes.data_as(_u64p), _vp(d_next)))
 
     def merkle_tree_dev(self, d_oracles, elem_bytes, n, coset_size, d_nodes, domain_type=DOMAIN_ADDITIVE, d_salts=0, salt_bytes=0):
@@ -1406,11 +1411,11 @@ class Library:
         return out
 
     def field_add_dev(self, d_a, d_b, d_out, count, words=3):
-        fn = self.c.iopx_gf64_add_dev if words == 1 else self.c.iopx_gf128_add_dev if words == 2 else self.c.iopx_gf192_add_dev
+        fn = self.c.iopx_gf64_add_dev if words == 1 else self.c.iopx_gf128_add_dev if words == 2 else self.c.iopx_gf256_add_dev if words == 4 else self.c.iopx_gf192_add_dev
         self._check(fn(_vp(d_a), _vp(d_b), _vp(d_out), int(count)))
 
     def field_inv_dev(self, d_a, d_out, count, prime_field=False, words=3):
-        fn = self.c.iopx_gf128_inv_dev if words == 2 else self.c.iopx_fp3_inv_dev if prime_field else self.c.iopx_gf192_inv_dev
+        fn = self.c.iopx_gf128_inv_dev if words == 2 else self.c.iopx_gf256_inv_dev if words == 4 else self.c.iopx_fp3_inv_dev if prime_field else self.c.iopx_gf192_inv_dev
         self._check(fn(_vp(d_a), _vp(d_out), int(count)))
 
     def fp3_mul_dev(self, d_a, d_b, d_out, count):
@@ -1769,6 +1774,106 @@ class Library:
         self._check(self.c.iopx_gf128_inverse_host(x.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
         return out
 
+    # ---- GF(2^256): four uint64 words per element, arrays of shape (n, 4).  The device forms are the gf192 `_dev` methods with words=4. ----
+    def additive_FFT_gf256(self, poly_coeffs, basis, shift):
+        """additive_FFT(poly_coeffs, affine_subspace(basis, shift)) over gf256 — fft.tcc:39-124."""
+        coeffs, basis, shift = _as_u64(poly_coeffs, 4), _as_u64(basis, 4), _as_u64(shift, 4)
+        m = basis.shape[0]
+        out = np.empty((1 << m, 4), dtype=np.uint64)
+        self._check(self.c.iopx_add_fft_gf256(coeffs.ctypes.data_as(_u64p), coeffs.shape[0], basis.ctypes.data_as(_u64p), m,
+                                              shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def additive_IFFT_gf256(self, evals, basis, shift):
+        """additive_IFFT(evals, affine_subspace(basis, shift)) over gf256 — fft.tcc:126-204."""
+        evals, basis, shift = _as_u64(evals, 4), _as_u64(basis, 4), _as_u64(shift, 4)
+        m = basis.shape[0]
+        if evals.shape[0] != 1 << m:
+            raise ValueError("additive IFFT: %d evaluations for a domain of size %d" % (evals.shape[0], 1 << m))
+        out = np.empty((1 << m, 4), dtype=np.uint64)
+        self._check(self.c.iopx_add_ifft_gf256(evals.ctypes.data_as(_u64p), basis.ctypes.data_as(_u64p), m,
+                                               shift.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def IFFT_of_known_degree_gf256(self, evals, degree, basis, shift):
+        """IFFT_of_known_degree_over_field_subset, additive overload — fft.tcc:458-475."""
+        evals, basis = _as_u64(evals, 4), _as_u64(basis, 4)
+        k = max(int(degree) - 1, 0).bit_length()
+        return self.additive_IFFT_gf256(evals[: 1 << k], basis[:k], shift)
+
+    def evaluate_next_f_i_over_entire_domain_gf256(self, f_i_evals, basis, shift, coset_size, x_i):
+        """fri_aux.tcc:5-34 -> additive_evaluate_next_f_i_over_entire_domain (:36-103) over gf256."""
+        f, basis, shift, x = _as_u64(f_i_evals, 4), _as_u64(basis, 4), _as_u64(shift, 4), _as_u64(x_i, 4)
+        m = basis.shape[0]
+        if f.shape[0] != 1 << m:
+            raise ValueError("f_i has %d evaluations for a domain of size %d" % (f.shape[0], 1 << m))
+        out = np.empty(((1 << m) // max(int(coset_size), 1), 4), dtype=np.uint64)
+        self._check(self.c.iopx_fri_fold_add_gf256(f.ctypes.data_as(_u64p), basis.ctypes.data_as(_u64p), m,
+                                                   shift.ctypes.data_as(_u64p), int(coset_size), x.ctypes.data_as(_u64p),
+                                                   out.ctypes.data_as(_u64p)))
+        return out
+
+    def fri_additive_domains_gf256(self, basis, shift, localization):
+        """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338) over gf256: [(basis_i, shift_i)] for L^(0), L^(1), ..."""
+        basis, shift = _as_u64(basis, 4), _as_u64(shift, 4)
+        m = basis.shape[0]
+        dims, d = [], m
+        for eta in localization:
+            d -= int(eta)
+            dims.append(d)
+        ob = np.zeros((max(sum(dims), 1), 4), dtype=np.uint64)
+        osh = np.zeros((max(len(dims), 1), 4), dtype=np.uint64)
+        loc = (_sz * max(len(localization), 1))(*[int(e) for e in localization])
+        self._check(self.c.iopx_fri_domains_gf256(basis.ctypes.data_as(_u64p), m, shift.ctypes.data_as(_u64p), loc, len(localization),
+                                                  ob.ctypes.data_as(_u64p), osh.ctypes.data_as(_u64p)))
+        out, off = [(basis, shift.reshape(4))], 0
+        for i, dm in enumerate(dims):
+            out.append((ob[off:off + dm].copy(), osh[i].copy()))
+            off += dm
+        return out
+
+    def _gf256_host_arrays(self, arrays, n_out, call):
+        """h2d the (n, 4) arrays, call(*device pointers, output pointer), d2h the (n_out, 4) result"""
+        ptrs = [self.malloc(32 * max(a.shape[0], 1)) for a in arrays] + [self.malloc(32 * max(n_out, 1))]
+        try:
+            for p, a in zip(ptrs, arrays):
+                self.h2d(p, a)
+            call(*ptrs)
+            out = np.empty((n_out, 4), dtype=np.uint64)
+            self.d2h(out, ptrs[-1])
+        finally:
+            for p in ptrs:
+                self.free(p)
+        return out
+
+    def ldt_combine_gf256(self, evals, degrees, random_coefficients, basis, shift):
+        """Host-array form of ldt_combine_dev(..., words=4): evals is a list of (2^m, 4) arrays."""
+        evals = [_as_u64(e, 4) for e in evals]
+        return self._gf256_host_arrays(evals, evals[0].shape[0],
+                                       lambda *p: self.ldt_combine_dev(list(p[:-1]), degrees, random_coefficients, basis, shift, p[-1], words=4))
+
+    def gf256_mul(self, a, b):
+        """Elementwise a[i] * b[i] over gf256 (host arrays)."""
+        a, b = _as_u64(a, 4), _as_u64(b, 4)
+        return self._gf256_host_arrays([a, b], a.shape[0], lambda da, db, do: self.gf192_mul_dev(da, db, do, a.shape[0], words=4))
+
+    def gf256_inv(self, a):
+        """Elementwise inverse over gf256 (host arrays); zero maps to zero."""
+        a = _as_u64(a, 4)
+        return self._gf256_host_arrays([a], a.shape[0], lambda da, do: self.field_inv_dev(da, do, a.shape[0], words=4))
+
+    def gf256_host_mul(self, a, b):
+        a, b = _as_u64(a, 4), _as_u64(b, 4)
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.c.iopx_gf256_host_mul(a.ctypes.data_as(_u64p), b.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
+    def gf256_inverse_host(self, x):
+        x = _as_u64(x, 4)
+        out = np.zeros(4, dtype=np.uint64)
+        self._check(self.c.iopx_gf256_inverse_host(x.ctypes.data_as(_u64p), out.ctypes.data_as(_u64p)))
+        return out
+
     def set_option(self, name, value):
         """A named integer option of the library (schedule switches such as IOPX_HEAD_EVAL, tile geometries): include/libiop_amd.h."""
         self.c.iopx_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
@@ -1830,7 +1935,7 @@ class Library:
         self._check(self.c.iopx_gf192_mul_halves_dev(_vp(d_a), _vp(d_c2), _vp(d_out), _vp(d_active), count, int(lane_mask)))
 
     def gf192_mul_dev(self, d_a, d_b, d_out, count, words=3):
-        fn = self.c.iopx_gf128_mul_dev if words == 2 else self.c.iopx_gf192_mul_dev
+        fn = self.c.iopx_gf128_mul_dev if words == 2 else self.c.iopx_gf256_mul_dev if words == 4 else self.c.iopx_gf192_mul_dev
         self._check(fn(_vp(d_a), _vp(d_b), _vp(d_out), count))
 
     def gf192_mul(self, a, b):

@@ -115,7 +115,7 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
 // FFT_over_field_subset(IFFT_over_field_subset(v, H), L) for `batch` vectors stored back to back.  When H is spanned by the first basis
 // vectors of L the coefficient form is skipped (iopx_add_reextend_gf192_batch_dev); otherwise the two transforms run one after the other.
 // H_is_first_coset: H is the first coset of its span inside L (same shift), so the first |H| entries of each codeword are the input itself.
-// An 8- or 16-byte field (gf64, gf128) has no fused or batched re-extension: here and in the two forms below its transforms run one after the other.
+// A subspace-only field (gf64, gf128, gf256) has no fused or batched re-extension: here and in the two forms below its transforms run one after the other.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &packed, std::size_t batch, const field_subset<FieldT> &H,
                                                    const field_subset<FieldT> &L, bool H_is_first_coset = false)
@@ -324,7 +324,7 @@ inline bool head_evaluation_enabled()
 {
     return iopx_get_option("IOPX_HEAD_EVAL", 1) != 0;   // looked up per proof (iopx_set_option): tests and bench.py prove the same instance both ways
 }
-// ... for FieldT: an 8- or 16-byte field (gf64, gf128) always runs the reference's schedule, whatever the option says — its re-extensions have no fused form and its
+// ... for FieldT: a subspace-only field (gf64, gf128, gf256) always runs the reference's schedule, whatever the option says — its re-extensions have no fused form and its
 // pointwise division by Z_I no entry, so nothing of the head route is built over it
 template<typename FieldT>
 bool head_evaluation()

@@ -65,6 +65,13 @@ inline constexpr vector_ops gf128 = {
     iopx_gf128_add_dev, iopx_gf128_mul_dev, iopx_gf128_inv_dev, nullptr, nullptr,
     nullptr, nullptr, nullptr, nullptr, nullptr,
 };
+// libff::gf256: the vector helpers of csrc/gf256.hip; as gf128, no protocol-layer entries
+inline constexpr vector_ops gf256 = {
+    "gf256", 256, false,
+    iopx_gf256_host_mul, iopx_gf256_inverse_host,
+    iopx_gf256_add_dev, iopx_gf256_mul_dev, iopx_gf256_inv_dev, nullptr, nullptr,
+    nullptr, nullptr, nullptr, nullptr, nullptr,
+};
 inline constexpr subspace_ops gf192_subspace = {
     iopx_add_fft_gf192_dev, iopx_add_lde_gf192_dev, iopx_add_ifft_gf192_dev,
     iopx_fri_fold_add_gf192_dev, iopx_fri_domains_gf192, iopx_ldt_combine_gf192_dev,
@@ -82,6 +89,13 @@ inline constexpr subspace_ops gf64_subspace = {
 inline constexpr subspace_ops gf128_subspace = {
     iopx_add_fft_gf128_dev, iopx_add_lde_gf128_dev, iopx_add_ifft_gf128_dev,
     iopx_fri_fold_add_gf128_dev, iopx_fri_domains_gf128, iopx_ldt_combine_gf128_dev,
+    nullptr, nullptr, nullptr,
+    nullptr, nullptr,
+    nullptr, nullptr,
+};
+inline constexpr subspace_ops gf256_subspace = {
+    iopx_add_fft_gf256_dev, iopx_add_lde_gf256_dev, iopx_add_ifft_gf256_dev,
+    iopx_fri_fold_add_gf256_dev, iopx_fri_domains_gf256, iopx_ldt_combine_gf256_dev,
     nullptr, nullptr, nullptr,
     nullptr, nullptr,
     nullptr, nullptr,
@@ -123,6 +137,7 @@ template<const vector_ops *Vec, const subspace_ops *Sub> struct binary_field {
 template<> struct field<24, true> : binary_field<&gf192, &gf192_subspace> {};
 template<> struct field<8, true> : binary_field<&gf64, &gf64_subspace> {};
 template<> struct field<16, true> : binary_field<&gf128, &gf128_subspace> {};
+template<> struct field<32, true> : binary_field<&gf256, &gf256_subspace> {};
 template<> struct field<24, false> { static constexpr const prime_field_ops *vec = &edwards_Fr, *prime = &edwards_Fr; static constexpr const subspace_ops *sub = nullptr; static constexpr bool additive = false; };
 template<> struct field<32, false> { static constexpr const prime_field_ops *vec = &alt_bn128_Fr, *prime = &alt_bn128_Fr; static constexpr const subspace_ops *sub = nullptr; static constexpr bool additive = false; };
 // by size alone, for reference_binding.hpp (it does not see field_kind): the prime field of that size; the domain's kind tells gf192 from edwards Fr

@@ -1,4 +1,4 @@
-// Plain field-element types for C++ callers that do not link libff: 8 raw bytes with the layout of libff::gf64, 16 with that of libff::gf128, 24 raw bytes with the layout of libff::gf192 (three
+// Plain field-element types for C++ callers that do not link libff: 8 raw bytes with the layout of libff::gf64, 16 with that of libff::gf128, 32 with that of libff::gf256, 24 raw bytes with the layout of libff::gf192 (three
 // little-endian words, polynomial basis) / libff::edwards_Fr (three Montgomery limbs), 32 with that of libff::alt_bn128_Fr (four).
 // They provide what the mirror asks of a FieldT — construction from an integer, ==, + — through the library's host helpers; a libiop
 // integration uses libff's own types instead.
@@ -41,6 +41,18 @@ struct gf128 {
     gf128 &operator+=(const gf128 &o) { w[0] ^= o.w[0]; w[1] ^= o.w[1]; return *this; }
 };
 template<> struct field_kind<gf128> { static const field_subset_type type = affine_subspace_type; };
+
+// 32 raw bytes with the layout of libff::gf256 (four little-endian words, polynomial basis, x^256 + x^10 + x^5 + x^2 + 1)
+struct gf256 {
+    uint64_t w[4];
+    gf256() : w{ 0, 0, 0, 0 } {}
+    explicit gf256(uint64_t v) : w{ v, 0, 0, 0 } {}
+    bool operator==(const gf256 &o) const { return w[0] == o.w[0] && w[1] == o.w[1] && w[2] == o.w[2] && w[3] == o.w[3]; }
+    bool operator!=(const gf256 &o) const { return !(*this == o); }
+    gf256 operator+(const gf256 &o) const { gf256 r; for (int i = 0; i < 4; ++i) r.w[i] = w[i] ^ o.w[i]; return r; }
+    gf256 &operator+=(const gf256 &o) { for (int i = 0; i < 4; ++i) w[i] ^= o.w[i]; return *this; }
+};
+template<> struct field_kind<gf256> { static const field_subset_type type = affine_subspace_type; };
 
 struct edwards_Fr_element {
     uint64_t w[3];

@@ -51,8 +51,16 @@ enum field_subset_type { affine_subspace_type = 1, multiplicative_coset_type = 2
 template<typename FieldT> struct field_kind;
 
 namespace detail {
-// a field with affine subspaces only, told by its size: libff::gf64 (8 bytes) and gf128 (16); 24 bytes is gf192 or edwards_Fr, 32 alt_bn128_Fr
-template<typename FieldT> constexpr bool binary_only() { return sizeof(FieldT) == 8 || sizeof(FieldT) == 16; }
+// 32 bytes are libff::gf256 or alt_bn128_Fr: field_kind<FieldT> tells them apart (looked at for a 32-byte type only)
+template<typename FieldT> constexpr bool binary32()
+{
+    if constexpr (sizeof(FieldT) == 32) return field_kind<FieldT>::type == affine_subspace_type;
+    else return false;
+}
+// a field with affine subspaces only: libff::gf64 (8 bytes), gf128 (16) and gf256 (32 bytes and additive); 24 bytes is gf192 or edwards_Fr
+template<typename FieldT> constexpr bool binary_only() { return sizeof(FieldT) == 8 || sizeof(FieldT) == 16 || binary32<FieldT>(); }
+// alt_bn128_Fr's layout: 32 bytes and multiplicative
+template<typename FieldT> constexpr bool bn128_layout() { return sizeof(FieldT) == 32 && !binary32<FieldT>(); }
 inline std::size_t log2_ceil(std::size_t n) { std::size_t d = 0; while (((std::size_t)1 << d) < n) ++d; return d; }
 } // namespace detail
 
@@ -109,13 +117,14 @@ class multiplicative_coset {
     std::size_t order_;
     FieldT g_, shift_;
     static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 32 || detail::binary_only<FieldT>(), "libiop_amd accelerates prime fields with libff::edwards_Fr's or alt_bn128_Fr's layout");
-    // by size: the mirror asks nothing of FieldT beyond its bytes.  An 8- or 16-byte field (gf64, gf128) is binary: field_subset<FieldT> names this
-    // class, but no coset of it can be built (the constructors refuse), so F is never used for it
+    // by size: the mirror asks nothing of FieldT beyond its bytes.  An 8- or 16-byte field (gf64, gf128) and a 32-byte additive one (gf256) are
+    // binary: field_subset<FieldT> names this class, but no coset of it can be built (the constructors refuse), so F is never used for it
     typedef ops::layout<detail::binary_only<FieldT>() ? 24 : sizeof(FieldT)> F;
     static void refuse_binary()
     {
         if constexpr (sizeof(FieldT) == 8) throw std::invalid_argument("gf64: affine subspaces only");
         if constexpr (sizeof(FieldT) == 16) throw std::invalid_argument("gf128: affine subspaces only");
+        if constexpr (detail::binary32<FieldT>()) throw std::invalid_argument("gf256: affine subspaces only");
     }
     typedef ops::prime_field_ops P;
     static FieldT host_mul(const FieldT &a, const FieldT &b)
@@ -290,8 +299,8 @@ std::vector<FieldT> multiplicative_IFFT(const std::vector<FieldT> &evals, const 
 template<typename FieldT>
 std::vector<FieldT> FFT_over_field_subset(const std::vector<FieldT> coeffs, field_subset<FieldT> domain)
 {
-    if constexpr (sizeof(FieldT) == 32) return multiplicative_FFT<FieldT>(coeffs, domain.coset());     // alt_bn128_Fr: cosets only
-    else if constexpr (detail::binary_only<FieldT>()) return additive_FFT<FieldT>(coeffs, domain.subspace());    // gf64, gf128: subspaces only
+    if constexpr (detail::bn128_layout<FieldT>()) return multiplicative_FFT<FieldT>(coeffs, domain.coset());     // alt_bn128_Fr: cosets only
+    else if constexpr (detail::binary_only<FieldT>()) return additive_FFT<FieldT>(coeffs, domain.subspace());    // gf64, gf128, gf256: subspaces only
     else {
         if (domain.type() == multiplicative_coset_type) return multiplicative_FFT<FieldT>(coeffs, domain.coset());
         return additive_FFT<FieldT>(coeffs, domain.subspace());
@@ -301,7 +310,7 @@ std::vector<FieldT> FFT_over_field_subset(const std::vector<FieldT> coeffs, fiel
 template<typename FieldT>
 std::vector<FieldT> IFFT_over_field_subset(const std::vector<FieldT> evals, field_subset<FieldT> domain)
 {
-    if constexpr (sizeof(FieldT) == 32) return multiplicative_IFFT<FieldT>(evals, domain.coset());
+    if constexpr (detail::bn128_layout<FieldT>()) return multiplicative_IFFT<FieldT>(evals, domain.coset());
     else if constexpr (detail::binary_only<FieldT>()) return additive_IFFT<FieldT>(evals, domain.subspace());
     else {
         if (domain.type() == multiplicative_coset_type) return multiplicative_IFFT<FieldT>(evals, domain.coset());
@@ -316,7 +325,7 @@ std::vector<FieldT> IFFT_of_known_degree_over_field_subset(const std::vector<Fie
 {
     const std::size_t pow2 = (std::size_t)1 << detail::log2_ceil(degree);
     const field_subset<FieldT> minimal = domain.get_subset_of_order(pow2);
-    if constexpr (detail::binary_only<FieldT>()) {                                          // gf64, gf128: subspaces only
+    if constexpr (detail::binary_only<FieldT>()) {                                          // gf64, gf128, gf256: subspaces only
         const std::vector<FieldT> head(evals.begin(), evals.begin() + pow2);
         return additive_IFFT<FieldT>(head, minimal.subspace());
     } else
@@ -326,7 +335,7 @@ std::vector<FieldT> IFFT_of_known_degree_over_field_subset(const std::vector<Fie
         for (std::size_t i = 0; i < domain.num_elements(); i += freq) sub.emplace_back(evals[i]);
         return multiplicative_IFFT<FieldT>(sub, minimal.coset());
     }
-    if constexpr (sizeof(FieldT) == 32) throw std::invalid_argument("alt_bn128_Fr: multiplicative cosets only");
+    if constexpr (detail::bn128_layout<FieldT>()) throw std::invalid_argument("alt_bn128_Fr: multiplicative cosets only");
     else {
         const std::vector<FieldT> head(evals.begin(), evals.begin() + pow2);
         return additive_IFFT<FieldT>(head, minimal.subspace());
@@ -356,7 +365,7 @@ std::shared_ptr<std::vector<FieldT>> evaluate_next_f_i_over_entire_domain(
     const std::shared_ptr<std::vector<FieldT>> &f_i_evals, const field_subset<FieldT> &f_i_domain,
     const std::size_t coset_size, const FieldT x_i)
 {
-    if constexpr (sizeof(FieldT) != 32) {
+    if constexpr (!detail::bn128_layout<FieldT>()) {
         if (f_i_domain.type() == affine_subspace_type) return additive_evaluate_next_f_i_over_entire_domain<FieldT>(f_i_evals, f_i_domain, coset_size, x_i);
     }
     if constexpr (!detail::binary_only<FieldT>())
@@ -453,7 +462,7 @@ public:
         : num_leaves_(num_leaves), leaf_hasher_(leaf_hasher), node_hasher_(node_hasher), digest_len_bytes_(digest_len_bytes), make_zk_(make_zk),
           constructed_(false), salt_bytes_(algebraic ? 32 : (security_parameter * 2 + 7) / 8)
     {
-        static_assert(!algebraic || sizeof(FieldT) == 32, "algebraic digests: FieldT must have libff::alt_bn128_Fr's 32-byte layout");
+        static_assert(!algebraic || detail::bn128_layout<FieldT>(), "algebraic digests: FieldT must have libff::alt_bn128_Fr's 32-byte layout");
         if (num_leaves < 2 || (num_leaves & (num_leaves - 1)))
             throw std::invalid_argument("Merkle tree size must be a power of two, and at least 2.");
         if (!leaf_hasher) throw std::invalid_argument("merkle_tree: null leaf hasher");

@@ -118,7 +118,7 @@ std::vector<FieldT> seeded_elements(uint64_t seed, std::size_t count)
     const FieldT R2 = H::additive() ? H::one() : H::pow(H::from_uint(2), 64 * H::WORDS);      // the element R = 2^192 / 2^256: its stored words are R^2 mod p
     for (std::size_t i = 0; i < count; ++i) {
         uint64_t w[H::WORDS] = {};
-        if (H::WORDS <= 2) for (std::size_t k = 0; k < H::WORDS; ++k) w[k] = splitmix64_at(seed, H::WORDS * i + k);     // gf64, gf128
+        if (H::additive()) for (std::size_t k = 0; k < H::WORDS; ++k) w[k] = splitmix64_at(seed, H::WORDS * i + k);     // a binary field: every word raw
         else for (std::size_t k = 0; k < 3 && k < H::WORDS; ++k) w[k] = splitmix64_at(seed, 3 * i + k);
         out[i] = H::from_words(w);
         if (!H::additive()) out[i] = H::mul(out[i], R2);

@@ -53,13 +53,15 @@ namespace binding {
 template<typename FieldT, typename Subspace>
 std::vector<FieldT> additive_FFT(const std::vector<FieldT> &poly_coeffs, const Subspace &domain)
 {
-    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 16 || sizeof(FieldT) == 8,
-                  "libiop_amd accelerates binary fields with libff::gf192's (three 64-bit words), gf128's (two) or gf64's (one) layout");
+    static_assert(sizeof(FieldT) == 32 || sizeof(FieldT) == 24 || sizeof(FieldT) == 16 || sizeof(FieldT) == 8,
+                  "libiop_amd accelerates binary fields with libff::gf256's (four 64-bit words), gf192's (three), gf128's (two) or gf64's (one) layout");
     const FieldT shift = domain.shift();
     std::vector<FieldT> out(domain.num_elements(), FieldT(0));
     if constexpr (sizeof(FieldT) == 8) check(iopx_add_fft_gf64(detail::words(poly_coeffs.data()), poly_coeffs.size(), detail::words(domain.basis().data()),
                                                                domain.dimension(), detail::words(&shift), detail::words(out.data())));
     else if constexpr (sizeof(FieldT) == 16) check(iopx_add_fft_gf128(detail::words(poly_coeffs.data()), poly_coeffs.size(), detail::words(domain.basis().data()),
+                                                                      domain.dimension(), detail::words(&shift), detail::words(out.data())));
+    else if constexpr (sizeof(FieldT) == 32) check(iopx_add_fft_gf256(detail::words(poly_coeffs.data()), poly_coeffs.size(), detail::words(domain.basis().data()),
                                                                       domain.dimension(), detail::words(&shift), detail::words(out.data())));
     else check(iopx_add_fft_gf192(detail::words(poly_coeffs.data()), poly_coeffs.size(), detail::words(domain.basis().data()),
                              domain.dimension(), detail::words(&shift), detail::words(out.data())));
@@ -70,14 +72,16 @@ std::vector<FieldT> additive_FFT(const std::vector<FieldT> &poly_coeffs, const S
 template<typename FieldT, typename Subspace>
 std::vector<FieldT> additive_IFFT(const std::vector<FieldT> &evals, const Subspace &domain)
 {
-    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 16 || sizeof(FieldT) == 8,
-                  "libiop_amd accelerates binary fields with libff::gf192's (three 64-bit words), gf128's (two) or gf64's (one) layout");
+    static_assert(sizeof(FieldT) == 32 || sizeof(FieldT) == 24 || sizeof(FieldT) == 16 || sizeof(FieldT) == 8,
+                  "libiop_amd accelerates binary fields with libff::gf256's (four 64-bit words), gf192's (three), gf128's (two) or gf64's (one) layout");
     if (evals.size() != domain.num_elements()) throw std::invalid_argument("additive_IFFT: evaluation count != domain size");
     const FieldT shift = domain.shift();
     std::vector<FieldT> out(domain.num_elements(), FieldT(0));
     if constexpr (sizeof(FieldT) == 8) check(iopx_add_ifft_gf64(detail::words(evals.data()), detail::words(domain.basis().data()), domain.dimension(),
                                                                 detail::words(&shift), detail::words(out.data())));
     else if constexpr (sizeof(FieldT) == 16) check(iopx_add_ifft_gf128(detail::words(evals.data()), detail::words(domain.basis().data()), domain.dimension(),
+                                                                       detail::words(&shift), detail::words(out.data())));
+    else if constexpr (sizeof(FieldT) == 32) check(iopx_add_ifft_gf256(detail::words(evals.data()), detail::words(domain.basis().data()), domain.dimension(),
                                                                        detail::words(&shift), detail::words(out.data())));
     else check(iopx_add_ifft_gf192(detail::words(evals.data()), detail::words(domain.basis().data()), domain.dimension(),
                               detail::words(&shift), detail::words(out.data())));
@@ -117,14 +121,16 @@ template<typename FieldT, typename Domain>
 std::shared_ptr<std::vector<FieldT>> additive_evaluate_next_f_i_over_entire_domain(
     const std::shared_ptr<std::vector<FieldT>> &f_i_evals, const Domain &f_i_domain, const std::size_t coset_size, const FieldT x_i)
 {
-    static_assert(sizeof(FieldT) == 24 || sizeof(FieldT) == 16 || sizeof(FieldT) == 8,
-                  "libiop_amd accelerates binary fields with libff::gf192's (three 64-bit words), gf128's (two) or gf64's (one) layout");
+    static_assert(sizeof(FieldT) == 32 || sizeof(FieldT) == 24 || sizeof(FieldT) == 16 || sizeof(FieldT) == 8,
+                  "libiop_amd accelerates binary fields with libff::gf256's (four 64-bit words), gf192's (three), gf128's (two) or gf64's (one) layout");
     if (f_i_evals->size() != f_i_domain.num_elements()) throw std::invalid_argument("f_i size != domain size");
     const FieldT shift = f_i_domain.shift();
     auto next = std::make_shared<std::vector<FieldT>>(f_i_domain.num_elements() / coset_size, FieldT(0));
     if constexpr (sizeof(FieldT) == 8) check(iopx_fri_fold_add_gf64(detail::words(f_i_evals->data()), detail::words(f_i_domain.basis().data()), f_i_domain.dimension(),
                                                                     detail::words(&shift), coset_size, detail::words(&x_i), detail::words(next->data())));
     else if constexpr (sizeof(FieldT) == 16) check(iopx_fri_fold_add_gf128(detail::words(f_i_evals->data()), detail::words(f_i_domain.basis().data()), f_i_domain.dimension(),
+                                                                           detail::words(&shift), coset_size, detail::words(&x_i), detail::words(next->data())));
+    else if constexpr (sizeof(FieldT) == 32) check(iopx_fri_fold_add_gf256(detail::words(f_i_evals->data()), detail::words(f_i_domain.basis().data()), f_i_domain.dimension(),
                                                                            detail::words(&shift), coset_size, detail::words(&x_i), detail::words(next->data())));
     else check(iopx_fri_fold_add_gf192(detail::words(f_i_evals->data()), detail::words(f_i_domain.basis().data()), f_i_domain.dimension(),
                                   detail::words(&shift), coset_size, detail::words(&x_i), detail::words(next->data())));

@@ -1626,6 +1626,7 @@ int iopx_clear_plans(void)
     clear_poseidon_sets();
     clear_gf64_plans();
     clear_gf128_plans();
+    clear_gf256_plans();
     clear_domain_tables();
     tmp_trim();
     return IOPX_OK;

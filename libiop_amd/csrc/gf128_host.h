@@ -83,25 +83,4 @@ struct hgf128 {
     }
 };
 
-// The subspace polynomial of span(basis[0..dim)): prod_{v in span} (X - v), a linearized polynomial (coeff[i] multiplies X^(2^i)), built
-// factor by factor as Z <- Z(X) (Z(X) + Z(b)) (libiop/algebra/polynomials/vanishing_polynomial.tcc:373-395).
-struct SubspacePoly128 {
-    std::vector<hgf128> coeff;
-    SubspacePoly128(const hgf128 *basis, size_t dim) : coeff(1, hgf128::one())
-    {
-        for (size_t k = 0; k < dim; ++k) {
-            const hgf128 zb = eval(basis[k]);
-            std::vector<hgf128> nxt(coeff.size() + 1, hgf128::zero());
-            for (size_t i = 0; i < coeff.size(); ++i) { nxt[i + 1] += coeff[i].squared(); nxt[i] += coeff[i] * zb; }
-            coeff.swap(nxt);
-        }
-    }
-    hgf128 eval(const hgf128 &x) const
-    {
-        hgf128 r = hgf128::zero(), xp = x;
-        for (size_t i = 0; i < coeff.size(); ++i) { r += coeff[i] * xp; xp = xp.squared(); }
-        return r;
-    }
-};
-
 } // namespace iopx

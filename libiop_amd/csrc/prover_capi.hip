@@ -203,8 +203,11 @@ int fri_entry(int field, int bcs_hash_type, iopx_comm *comm, const uint64_t *d_p
     if (field == IOPX_FIELD_GF64 && bcs_hash_type != IOPX_HASH_BLAKE2B && (bcs_hash_type == IOPX_HASH_POSEIDON_STARKWARE || bcs_hash_type == IOPX_HASH_POSEIDON_HIGH_ALPHA))
         return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf64 proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
     if (field == IOPX_FIELD_GF128 && comm) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf128 has no distributed prover: pass no communicator");
+    if (field == IOPX_FIELD_GF256 && comm) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf256 has no distributed prover: pass no communicator");
     if (field == IOPX_FIELD_GF128 && bcs_hash_type != IOPX_HASH_BLAKE2B && (bcs_hash_type == IOPX_HASH_POSEIDON_STARKWARE || bcs_hash_type == IOPX_HASH_POSEIDON_HIGH_ALPHA))
         return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf128 proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
+    if (field == IOPX_FIELD_GF256 && bcs_hash_type != IOPX_HASH_BLAKE2B && (bcs_hash_type == IOPX_HASH_POSEIDON_STARKWARE || bcs_hash_type == IOPX_HASH_POSEIDON_HIGH_ALPHA))
+        return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "gf256 proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
     if (field == IOPX_FIELD_ALT_BN128_FR && codeword_domain_dim > 28)
         return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "codeword domain dimension %zu: alt_bn128 Fr has subgroups of order up to 2^28", codeword_domain_dim);
     if (field == IOPX_FIELD_ALT_BN128_FR && comm) return iopx::fail(IOPX_ERR_INVALID_ARGUMENT, "alt_bn128 Fr has no distributed prover: pass no communicator");
@@ -219,6 +222,7 @@ int fri_entry(int field, int bcs_hash_type, iopx_comm *comm, const uint64_t *d_p
         else if (field == IOPX_FIELD_EDWARDS_FR) t = fri_prove<edwards_Fr_element>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_GF64) t = fri_prove<libiop_amd::gf64>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_GF128) t = fri_prove<libiop_amd::gf128>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
+        else if (field == IOPX_FIELD_GF256) t = fri_prove<libiop_amd::gf256>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_ALT_BN128_FR && bcs_hash_type == IOPX_HASH_BLAKE2B) t = fri_prove<alt_bn128_Fr_element>(comm, d_poly_coeffs, n_coeffs, params, blake2b());
         else if (field == IOPX_FIELD_ALT_BN128_FR) t = fri_prove<alt_bn128_Fr_element>(comm, d_poly_coeffs, n_coeffs, params, poseidon(bcs_hash_type));
         else throw std::invalid_argument("unknown field");
@@ -248,6 +252,7 @@ int iopx_aurora_instance_create(const iopx_r1cs *r1cs, const uint64_t *assignmen
         else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<alt_bn128_Fr_element>(r1cs, assignment));
         else if (field == IOPX_FIELD_GF64) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<libiop_amd::gf64>(r1cs, assignment));
         else if (field == IOPX_FIELD_GF128) throw std::invalid_argument("iopx_aurora_instance_create: only the FRI-only SNARK is built over gf128 (no protocol-layer kernels)");
+        else if (field == IOPX_FIELD_GF256) throw std::invalid_argument("iopx_aurora_instance_create: only the FRI-only SNARK is built over gf256 (no protocol-layer kernels)");
         else throw std::invalid_argument("unknown field");
     });
 }
@@ -263,6 +268,7 @@ int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_
         else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<alt_bn128_Fr_element>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_GF64) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<libiop_amd::gf64>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_GF128) throw std::invalid_argument("iopx_aurora_example_instance_create: only the FRI-only SNARK is built over gf128 (no protocol-layer kernels)");
+        else if (field == IOPX_FIELD_GF256) throw std::invalid_argument("iopx_aurora_example_instance_create: only the FRI-only SNARK is built over gf256 (no protocol-layer kernels)");
         else throw std::invalid_argument("unknown field");
     });
 }

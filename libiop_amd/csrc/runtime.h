@@ -196,6 +196,7 @@ void clear_dist_plans();           // fft_add_dist.hip: the sharded transforms' 
 void clear_poseidon_sets();
 void clear_gf64_plans();           // gf64.hip: the GF(2^64) transforms' per-basis plans
 void clear_gf128_plans();          // gf128.hip: the GF(2^128) transforms' per-basis plans
+void clear_gf256_plans();          // gf256.hip: the GF(2^256) transforms' per-basis plans
 
 // comm.hip: the communicator bound for transforms (iopx_comm_bind_transforms), or null; its rank / world; collectives for library-internal
 // use (same semantics as the C entry points)

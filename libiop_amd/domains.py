@@ -403,6 +403,74 @@ class GF128(GF64):
         return [domain] + [Domain(self, ADDITIVE, basis=b, shift=s) for b, s in chain[1:]]
 
 
+class GF256(GF128):
+    """libff::gf256 (x^256 + x^10 + x^5 + x^2 + 1, four little-endian words), additive arm: the FRI-only SNARK.  Host scalars are (4,) uint64
+    arrays; the host-side products run on Python integers, as GF64's do."""
+    name, additive, elem_bytes, words, soundness_bits = "gf256", True, 32, 4, 256
+    # the transforms, the fold, the LDT combination and the vector helpers: the gf192 methods with four words per element
+    entries = {
+        "FFT": ("additive_FFT_dev", {"words": 4}),
+        "IFFT": ("additive_IFFT_dev", {"words": 4}),
+        "LDE": ("additive_LDE_dev", {"words": 4}),
+        "fold": ("fri_fold_dev", {"words": 4}),
+        "ldt_combine": ("ldt_combine_dev", {"words": 4}),
+        "sub": ("field_add_dev", {"words": 4}),
+        "mul": ("gf192_mul_dev", {"words": 4}),
+        "inv": ("field_inv_dev", {"words": 4}),
+    }
+
+    @staticmethod
+    def standard_basis(m):
+        """subspace.tcc:93-108 — basis element i is FieldT(1 << i)."""
+        return np.array([GF256._elem(1 << i) for i in range(m)], dtype=np.uint64).reshape(m, 4)
+
+    def domain(self, num_elements, shift=None):
+        d = _log2(num_elements)
+        return Domain(self, ADDITIVE, basis=self.standard_basis(d), shift=np.zeros(4, dtype=np.uint64) if shift is None else shift)
+
+    @staticmethod
+    def _int(a):
+        w = np.asarray(a, dtype=np.uint64).reshape(-1)
+        return sum(int(w[k]) << (64 * k) for k in range(4))
+
+    @staticmethod
+    def _elem(v):
+        return np.array([(v >> (64 * k)) & GF128._MASK for k in range(4)], dtype=np.uint64)
+
+    @staticmethod
+    def _mul(a, b):
+        r = 0
+        while b:
+            if b & 1:
+                r ^= a
+            b >>= 1
+            a <<= 1
+            if a >> 256:
+                a ^= (1 << 256) | 0x425
+        return r
+
+    def zero(self):
+        return np.zeros(4, dtype=np.uint64)
+
+    def inv(self, a, lib):
+        return lib.gf256_inverse_host(a)
+
+    def squeeze(self, hashchain, n):
+        """blake2b_FieldT_randomness_extractor for a binary field of 32 bytes (blake2b.tcc:162-185, 231-257): element i = keyed
+        BLAKE2b(state || index, key = i, 32 bytes), the four raw words."""
+        hashchain.squeeze_index += 1
+        msg = hashchain.state + hashchain.squeeze_index.to_bytes(8, "little")
+        out = np.zeros((n, 4), dtype=np.uint64)
+        for i in range(n):
+            out[i] = np.frombuffer(hashlib.blake2b(msg, digest_size=32, key=i.to_bytes(8, "little")).digest(), dtype="<u8")
+        return out
+
+    def fri_domains(self, domain, localization, lib):
+        """FRI_protocol::compute_domains, additive branch (fri_ldt.tcc:310-338), by the library's host-side helper."""
+        chain = lib.fri_additive_domains_gf256(domain.basis, domain.shift, localization)
+        return [domain] + [Domain(self, ADDITIVE, basis=b, shift=s) for b, s in chain[1:]]
+
+
 class EdwardsFr:
     """libff::edwards_Fr (181 bits, 3 Montgomery limbs), multiplicative arm."""
     name, additive, elem_bytes, words, soundness_bits = "edwards_Fr", False, 24, 3, 180
@@ -585,10 +653,13 @@ class DeviceOps:
     call enqueues on the library's stream and returns without synchronising."""
 
     def __new__(cls, lib, torch, device, field, *args, **kwargs):
-        # alt_bn128 Fr, GF(2^64) and GF(2^128) have a class of their own (below); GF(2^192) and edwards_Fr run this class as it is.  Only DeviceOps itself is
-        # redirected: a subclass (the sharded operators of libiop_amd/dist.py) is built as asked, and __init__ refuses the field there
-        if cls is DeviceOps and field.words == 4:
+        # alt_bn128 Fr, GF(2^64), GF(2^128) and GF(2^256) have a class of their own (below); GF(2^192) and edwards_Fr run this class as it is.  Four words
+        # are alt_bn128 Fr or GF(2^256): field.additive tells them apart.  Only DeviceOps itself is redirected: a subclass (the sharded operators of
+        # libiop_amd/dist.py) is built as asked, and __init__ refuses the field there
+        if cls is DeviceOps and field.words == 4 and not field.additive:
             cls = AltBn128DeviceOps
+        if cls is DeviceOps and field.words == 4 and field.additive:
+            cls = GF256DeviceOps
         if cls is DeviceOps and field.words == 1:
             cls = GF64DeviceOps
         if cls is DeviceOps and field.words == 2:
@@ -597,7 +668,9 @@ class DeviceOps:
 
     def __init__(self, lib, torch, device, field):
         self.lib, self.torch, self.device, self.field = lib, torch, device, field
-        if field.words == 4 and not isinstance(self, AltBn128DeviceOps):
+        if field.words == 4 and field.additive and not isinstance(self, GF256DeviceOps):
+            raise NotImplementedError("%s: no operators over a four-word binary field (gf256 runs on one GPU, through DeviceOps)" % type(self).__name__)
+        if field.words == 4 and not field.additive and not isinstance(self, AltBn128DeviceOps):
             raise NotImplementedError("%s: no operators over a four-word field (alt_bn128 Fr runs on one GPU, through DeviceOps)" % type(self).__name__)
         if field.words == 1 and not isinstance(self, GF64DeviceOps):
             raise NotImplementedError("%s: no operators over a one-word field (gf64 runs on one GPU, through DeviceOps)" % type(self).__name__)
@@ -897,6 +970,11 @@ class GF128DeviceOps(DeviceOps):
     (libiop_amd/fri.py) calls; every other operator of DeviceOps raises NotImplementedError."""
 
 
+class GF256DeviceOps(DeviceOps):
+    """DeviceOps over GF256: (count, 4) int64 vectors, the iopx_*_gf256 entries through GF256.entries.  It allows what the FRI-only SNARK
+    (libiop_amd/fri.py) calls; every other operator of DeviceOps raises NotImplementedError."""
+
+
 class GF64AuroraOps(GF64DeviceOps):
     """GF64DeviceOps plus what the Aurora prover (libiop_amd/aurora.py, libiop_amd/bcs.py) calls: the iopx_*_gf64_dev entries of
     libiop_amd/csrc/gf64_ops.hip.  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  The operators only Fractal
@@ -928,6 +1006,7 @@ _GF64_WHY = "gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK and, t
 _allow_only(GF64DeviceOps, _GF64_FRI, _GF64_WHY)
 _allow_only(GF64AuroraOps, _GF64_AURORA, _GF64_WHY)
 _allow_only(GF128DeviceOps, _GF64_FRI, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK is the prover over this field)")
+_allow_only(GF256DeviceOps, _GF64_FRI, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(AltBn128DeviceOps, _OPERATORS - {"_coset_range"}, "DeviceOps.%s: coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
 
 

@@ -74,11 +74,9 @@ def _splitmix64(seed, index):
 def seeded_elements(field, seed, count):
     """count field elements from the seed: element i takes stream outputs 3 i .. 3 i + 2 as its words (GF(2^192): the raw
     words; the prime field: the 192-bit draw reduced mod p, then Montgomery form)."""
-    if field.words <= 2:               # GF(2^64): element i is stream output i; GF(2^128): outputs 2 i, 2 i + 1
+    if field.additive:                 # a binary field of w words: element i is stream outputs w i .. w i + w - 1, the raw words
         return _splitmix64(seed, np.arange(field.words * count, dtype=np.uint64)).reshape(count, field.words)
     w = _splitmix64(seed, np.arange(3 * count, dtype=np.uint64)).reshape(count, 3)
-    if field.additive:
-        return w
     vals = [(int(a) | (int(b) << 64) | (int(c) << 128)) % field.P for a, b, c in w]
     return la.edwards_to_montgomery(vals)
 

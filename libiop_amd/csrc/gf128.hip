@@ -1,11 +1,8 @@
 // GF(2^128) on gfx950: additive FFT / IFFT / low-degree extension, FRI fold and domain chain, LDT combination, vector helpers.
 //
 // The transforms replace additive_FFT / additive_IFFT of the reference (libiop/algebra/fft.tcc:39-124, 126-204) for FieldT = libff::gf128
-// with the two-phase schedule of gf64.hip (phase 1: twist + Taylor network in place on 2^d elements; phase 2: the butterflies in block
-// order once per coset of span(basis[0..d)), the bit reversal folded into the last pass; the IFFT is the inverse schedule).
-//
-// The kernels, the host driver and the bodies of the entries are gfx_additive.h, written once over an element trait F and instantiated here
-// for Elem128; an element travels as F::mem, a 16-byte block (one 128-bit access when every pointer of the launch is 16-byte aligned,
+// (x^128 + x^7 + x^2 + x + 1, two words).  The kernels, the host driver and the bodies of the entries are gfx_additive.h, instantiated here
+// for Elem128: an element travels as F::mem, a 16-byte block (one 128-bit access when every pointer of the launch is 16-byte aligned,
 // two 64-bit words otherwise: the profile reports the latter as k128_*_w64).
 #include <hip/hip_runtime.h>
 #include "gf128_dev.h"
@@ -56,6 +53,8 @@ struct Elem128 {
     static constexpr int TILE_DEFAULT = 11, TILE_MAX = 11;      // 2^11 elements = 32 KiB of LDS
     static constexpr int P1_COLS_DEFAULT = 3, P2_COLS_DEFAULT = 3, P2_TOP_DEFAULT = 3;      // 8 x 16 B = one line
     static constexpr int UPPER_WAVES = 6;                       // kx_bfly_upper: 80 registers
+    static constexpr int STAGE_BITS = 24;                       // 256 MiB of staging
+    static constexpr bool SPLIT_ACCESS = true;                  // 128-bit accesses where the pointers allow them
     static const char *cold_plan() { return "gf128_plan"; }
     static const char *cold_pow() { return "gf128_pow_tables"; }
     static constexpr uint64_t LDT_TAG = 0x6c6474313238;         // "ldt128"

@@ -1,8 +1,8 @@
 // GF(2^256) on gfx950: additive FFT / IFFT / low-degree extension, FRI fold and domain chain, LDT combination, vector helpers.
 //
 // The transforms replace additive_FFT / additive_IFFT of the reference (libiop/algebra/fft.tcc:39-124, 126-204) for FieldT = libff::gf256
-// (x^256 + x^10 + x^5 + x^2 + 1, four words).  The kernels, the host driver and the bodies of the entries are gfx_additive.h, the text that
-// gf128.hip instantiates, here for Elem256: an element travels as F::mem, a 32-byte block (two 128-bit accesses when every pointer of the
+// (x^256 + x^10 + x^5 + x^2 + 1, four words).  The kernels, the host driver and the bodies of the entries are gfx_additive.h, instantiated
+// here for Elem256: an element travels as F::mem, a 32-byte block (two 128-bit accesses when every pointer of the
 // launch is 16-byte aligned, four 64-bit words otherwise: the profile reports the latter as k256_*_w64).  The LDS tile is an array of
 // 32-byte elements.
 #include <hip/hip_runtime.h>
@@ -69,6 +69,8 @@ struct Elem256 {
     static constexpr int P1_COLS_DEFAULT = 2, P2_TOP_DEFAULT = 2;       // 4 x 32 B = one line
     static constexpr int P2_COLS_DEFAULT = 3;                   // the upper passes gain from runs of two lines
     static constexpr int UPPER_WAVES = 6;                       // kx_bfly_upper: 74 registers, gf128's bound holds
+    static constexpr int STAGE_BITS = 24;                       // 512 MiB of staging
+    static constexpr bool SPLIT_ACCESS = true;                  // 128-bit accesses where the pointers allow them
     static const char *cold_plan() { return "gf256_plan"; }
     static const char *cold_pow() { return "gf256_pow_tables"; }
     static constexpr uint64_t LDT_TAG = 0x6c6474323536;         // "ldt256"

@@ -1,1045 +1,127 @@
 // GF(2^64) on gfx950: additive FFT / IFFT / low-degree extension, FRI fold and domain chain, LDT combination, vector helpers.
 //
-// The transforms replace additive_FFT / additive_IFFT of the reference (libiop/algebra/fft.tcc:39-124, 126-204) for FieldT = libff::gf64 and
-// keep the two-phase structure of fft_add.hip:
-//
-//   phase 1  (coefficients -> Gao–Mateer basis), in place on 2^d elements, d = ceil(log2 n_coeffs): per level j the twist by
-//            beta_j^(idx >> j) (power table in HBM, built once per basis) and the Taylor-expansion XOR network on index bits (k+1, k),
-//            k = d-2 .. j (fft.tcc:62-83), in LDS tiles of 2^c contiguous columns x 2^A rows on consecutive index bits;
-//   phase 2  (the unwind butterflies, fft.tcc:102-120) without the bit reversal of fft.tcc:99: pair bit p = d-1 .. 0 in block order, the
-//            bit reversal folded into the addressing of the last pass.  It runs once per coset of span(basis[0..d)): the twiddles of two
-//            cosets differ by a per-level additive constant (the recursed shift is GF(2)-linear in the coset shift).
+// The transforms replace additive_FFT / additive_IFFT of the reference (libiop/algebra/fft.tcc:39-124, 126-204) for FieldT = libff::gf64
+// (x^64 + x^4 + x^3 + x + 1, one word).  The kernels, the host driver and the bodies of the entries are gfx_additive.h, instantiated here
+// for Elem64: an element is one uint64_t, so there is one access path (no 128-bit instantiation, no k64_*_w64 rows in the profile).
 //
 // A gf64 product is ~0.13k VALU ops (three word products) and an element is 8 bytes: unlike the gf192 transform this one is bound by its
-// HBM passes, so the schedule is chosen for few of them — 4096-element tiles (32 KiB of LDS) carry 8 butterfly levels per upper pass and
-// 8 + the bit reversal in the last one; no wave-uniform multiplier form is used (the general product is cheap enough to hide).
-// The IFFT runs the exact inverse schedule.
+// HBM passes, so the tile is chosen for few of them — 4096 elements (32 KiB of LDS) carry 8 butterfly levels per upper pass and
+// 8 + the bit reversal in the last one.  The vector add lives in gf64_ops.hip (k64_add).
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <vector>
 #include "gf64_dev.h"
 #include "gf64_host.h"
 #include "runtime.h"
 
 namespace iopx {
 
-// Tile geometry: options of runtime.h's table, looked up when a plan is built (a plan keeps the geometry it was built with and the plan key
-// carries it).  The tests set small values with iopx_set_option to reach the multi-pass schedules at small transform sizes.
-struct Tuning64 { int tile_bits, p1_cols, p2_cols, p2_top; };
-static Tuning64 tuning64()
-{
-    Tuning64 u;
-    u.tile_bits = opt_range("IOPX_GF64_TILE_BITS", 12, 3, 12);                 // 2^12 elements = 32 KiB of LDS
-    u.p1_cols = opt_range("IOPX_GF64_P1_COLS", 4, 0, u.tile_bits - 2);         // phase-1 tiles: 2^c contiguous columns (16 x 8 B = one line)
-    u.p2_cols = opt_range("IOPX_GF64_P2_COLS", 4, 0, u.tile_bits - 2);         // phase-2 upper tiles
-    u.p2_top = opt_range("IOPX_GF64_P2_TOP", 4, 0, u.tile_bits - 2);           // last pass: 2^top natural-order runs
-    return u;
-}
-
-static int grid64(size_t work, int threads)
-{
-    size_t g = (work + threads - 1) / threads;
-    if (g > 16384) g = 16384;
-    return (int)(g ? g : 1);
-}
-
-__device__ __forceinline__ uint32_t bitrev64(uint32_t x, int bits)
-{
-    return bits == 0 ? 0u : (__brev(x) >> (32 - bits));
-}
-
 // ---------------------------------------------------------------------------------------------
-// plan construction, padding
+// the element trait
 // ---------------------------------------------------------------------------------------------
-// out[q] = prod_{k : bit k of q} sq[k]  for q < count   (sq[k] = beta^(2^k))
-__global__ void k64_pow_direct(uint64_t *out, const uint64_t *sq, int nbits, size_t count)
-{
-    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < count; q += (size_t)gridDim.x * blockDim.x) {
-        gf64 acc = g64_from(1);
-        for (int k = 0; k < nbits; ++k) {
-            if ((q >> k) & 1) acc = g64_mul(acc, g64_from(sq[k]));
-        }
-        out[q] = g64_word(acc);
-    }
-}
+struct Elem64 {
+    static constexpr int W = 1;                     // uint64 words per element
+    typedef uint64_t mem;                           // the form in HBM and LDS
+    typedef gf64 reg;
 
-// Twiddle table in block order: pair bit p owns the 2^(d-1-p) entries at offset 2^(d-1-p) - 1; entry t is sum_k bit_{l-1-k}(t) * B_p[k],
-// l = d-1-p, B_p = the l recursed basis vectors of recursion level p (fft.tcc:87-92, popped at :104-110) — sums[rev_l(t)] without the shift term.
-__global__ void k64_build_ltab(uint64_t *ltab, const uint64_t *rec_betas, int d, size_t count)
-{
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < count; e += (size_t)gridDim.x * blockDim.x) {
-        int l = 0;
-        while (((size_t)2 << l) <= e + 1) ++l;          // l = floor(log2(e + 1))
-        const size_t t = e + 1 - ((size_t)1 << l);
-        const int p = d - 1 - l;
-        const size_t off = (size_t)p * (d - 1) - (size_t)p * (p - 1) / 2;       // level p has d-1-p entries, levels back to back
-        uint64_t acc = 0;
-        for (int k = 0; k < l; ++k) {
-            if ((t >> (l - 1 - k)) & 1) acc ^= rec_betas[off + k];
-        }
-        ltab[e] = acc;
-    }
-}
+    template<bool A16> static __device__ __forceinline__ mem load(const uint64_t *p, size_t idx) { return p[idx]; }
+    template<bool A16> static __device__ __forceinline__ void store(uint64_t *p, size_t idx, mem v) { p[idx] = v; }
+    static __device__ __forceinline__ mem zero() { return 0; }
+    static __device__ __forceinline__ mem one() { return 1; }
+    static __device__ __forceinline__ mem add(mem a, mem b) { return a ^ b; }
+    static __device__ __forceinline__ reg unpack(mem a) { return g64_from(a); }
+    static __device__ __forceinline__ mem pack(const reg &a) { return g64_word(a); }
+    static __device__ __forceinline__ reg rmul(const reg &a, const reg &b) { return g64_mul(a, b); }
+    static __device__ __forceinline__ mem mul(mem a, mem b) { return g64_word(g64_mul(g64_from(a), g64_from(b))); }
+    static __device__ __forceinline__ mem inv(mem a) { return g64_word(g64_inv(g64_from(a))); }
 
-__global__ void k64_pad_copy(uint64_t *dst, const uint64_t *src, size_t n_src, size_t n_dst)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst; i += (size_t)gridDim.x * blockDim.x) dst[i] = i < n_src ? src[i] : 0;
-}
-
-// out[i] = c for every i (degree-0 polynomial: n_coeffs <= 1)
-__global__ void k64_fill(uint64_t *dst, const uint64_t *src, int have_src, size_t n)
-{
-    const uint64_t a = have_src ? src[0] : 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = a;
-}
-
-// ---------------------------------------------------------------------------------------------
-// phase 1: twist + Taylor-expansion network on an LDS tile
-// ---------------------------------------------------------------------------------------------
-struct P1Params64 {
-    uint64_t *S;            // 2^d elements, updated in place
-    const uint64_t *pow;    // power tables, level j at offset 2^(d+1) - 2^(d+1-j), 2^(d-j) entries (inverse: powers of 1 / beta_j)
-    int d;
-    int c, h, A;            // tile = columns on bits [0,c) x rows on bits [h, h+A)
-    int j0, j1;             // levels handled by this pass
-    int k_start, k_end;     // first op of level j0, last op of level j1 (ops run k = d-2 .. j)
-    int twist_first;        // 1: level j0's twist belongs to this pass (the levels after j0 always bring theirs)
-};
-
-template<bool INV>
-__global__ void __launch_bounds__(512) k64_phase1(P1Params64 p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
-    uint64_t *s = iopx_smem;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int E = 1 << (p.c + p.A);
-    const int midbits = p.h - p.c;
-    const size_t o = blockIdx.x;
-    const size_t mid = o & (((size_t)1 << midbits) - 1), hi = o >> midbits;
-    const size_t base = (hi << (p.h + p.A)) | (mid << p.c);
-    const int cmask = (1 << p.c) - 1;
-
-    for (int li = tid; li < E; li += nt) s[li] = p.S[base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask)];
-    __syncthreads();
-
-    const int jb = INV ? p.j1 : p.j0, je = INV ? p.j0 - 1 : p.j1 + 1, js = INV ? -1 : 1;
-    for (int j = jb; j != je; j += js) {
-        const int ks = (j == p.j0) ? p.k_start : p.d - 2;
-        const int ke = (j == p.j1) ? p.k_end : j;
-        const bool twist = (j > p.j0) || p.twist_first;
-        const uint64_t *powj = p.pow + ((((size_t)2) << p.d) - (((size_t)2) << (p.d - j)));
-        if (!INV && twist) {
-            for (int li = tid; li < E; li += nt) {
-                const size_t gi = base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask);
-                s[li] = g64_word(g64_mul(g64_from(s[li]), g64_from(powj[gi >> j])));
-            }
-            __syncthreads();
-        }
-        const int nops = ks - ke + 1;                   // forward: k = ks down to ke; inverse: k = ke up to ks
-        for (int t = 0; t < nops; ++t) {
-            const int k = INV ? ke + t : ks - t;
-            const int kl = k - p.h + p.c;               // tile-local bit of global bit k
-            for (int qd = tid; qd < (E >> 2); qd += nt) {
-                const int low = qd & ((1 << kl) - 1), high = qd >> kl;
-                const int b0 = (high << (kl + 2)) | low;
-                const int e1 = b0 | (1 << kl), e2 = b0 | (2 << kl), e3 = b0 | (3 << kl);
-                if (!INV) {                             // S[2s+i] += S[3s+i]; S[s+i] += S[2s+i]            (fft.tcc:79-80)
-                    const uint64_t v2 = s[e2] ^ s[e3];
-                    s[e2] = v2;
-                    s[e1] ^= v2;
-                } else {                                // S[q+i] += S[2q+i]; S[2q+i] += S[3q+i]            (fft.tcc:183-184)
-                    const uint64_t v2 = s[e2];
-                    s[e1] ^= v2;
-                    s[e2] = v2 ^ s[e3];
-                }
-            }
-            __syncthreads();
-        }
-        if (INV && twist) {
-            for (int li = tid; li < E; li += nt) {
-                const size_t gi = base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask);
-                s[li] = g64_word(g64_mul(g64_from(s[li]), g64_from(powj[gi >> j])));
-            }
-            __syncthreads();
-        }
-    }
-
-    for (int li = tid; li < E; li += nt) p.S[base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask)] = s[li];
-}
-
-// ---------------------------------------------------------------------------------------------
-// phase 2: butterflies in block order
-// ---------------------------------------------------------------------------------------------
-struct BfParams64 {
-    const uint64_t *src;    // forward: W (2^d, shared by all cosets) when src_shared, else the layout of dst
-    uint64_t *dst;          // cosets * 2^d elements
-    const uint64_t *ltab;   // 2^d - 1 twiddles (no shift term)
-    const uint64_t *rs;     // (1 + nhi) * d shift terms: rs[v * d + p], v = 0 the shift, v = 1 + k coset basis vector k
-    int src_shared;
-    int d, nhi;
-    int c, h, A;            // upper pass tile geometry
-    int p_hi, p_lo;         // pair bits handled (forward: p_hi down to p_lo)
-    int a_low, c_top;       // last/first pass tile: low a_low bits x top c_top bits
-    int g_bits;             // last/first pass: 2^g_bits tiles per workgroup
-    size_t total_units;     // cosets (of this launch) * tiles per coset
-    size_t coset_base;      // global index of the first coset of this launch (src/dst are pre-offset)
-};
-
-// shift term of the twiddles of pair bit pbit in coset `coset` of the launch
-__device__ __forceinline__ uint64_t bf64_shift_term(const BfParams64 &p, size_t coset, int pbit)
-{
-    const size_t gc = p.coset_base + coset;
-    uint64_t tw = p.rs[pbit];
-    for (int v = 0; v < p.nhi; ++v) {
-        if ((gc >> v) & 1) tw ^= p.rs[(size_t)(1 + v) * p.d + pbit];
-    }
-    return tw;
-}
-
-template<bool INV>
-__device__ __forceinline__ void bf64_apply(uint64_t *s, int ia, int ib, uint64_t tw)
-{
-    uint64_t a = s[ia], b = s[ib];
-    if (!INV) {
-        a ^= g64_word(g64_mul(g64_from(b), g64_from(tw)));     // S[a] += S[b] * t ; S[b] += S[a]  (fft.tcc:116-117)
-        b ^= a;
-    } else {
-        b ^= a;                                                 // S[b] += S[a] ; S[a] += S[b] * t  (fft.tcc:164-165)
-        a ^= g64_word(g64_mul(g64_from(b), g64_from(tw)));
-    }
-    s[ia] = a;
-    s[ib] = b;
-}
-
-template<bool INV>
-__global__ void __launch_bounds__(512) k64_bfly_upper(BfParams64 p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
-    uint64_t *s = iopx_smem;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int E = 1 << (p.c + p.A);
-    const int tpc_bits = p.d - p.c - p.A;
-    const size_t unit = blockIdx.x;
-    const size_t coset = unit >> tpc_bits, o = unit & (((size_t)1 << tpc_bits) - 1);
-    const int midbits = p.h - p.c;
-    const size_t mid = o & (((size_t)1 << midbits) - 1), hi = o >> midbits;
-    const size_t base = (hi << (p.h + p.A)) | (mid << p.c);
-    const int cmask = (1 << p.c) - 1;
-    const uint64_t *src = p.src_shared ? p.src : p.src + (coset << p.d);
-    uint64_t *dst = p.dst + (coset << p.d);
-
-    for (int li = tid; li < E; li += nt) s[li] = src[base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask)];
-    __syncthreads();
-
-    const int nlev = p.p_hi - p.p_lo + 1;
-    for (int t = 0; t < nlev; ++t) {
-        const int pbit = INV ? p.p_lo + t : p.p_hi - t;
-        const int pl = pbit - p.h + p.c;
-        const uint64_t sh = bf64_shift_term(p, coset, pbit);           // uniform over the workgroup
-        const uint64_t *lt = p.ltab + ((((size_t)1) << (p.d - 1 - pbit)) - 1);
-        for (int bf = tid; bf < (E >> 1); bf += nt) {
-            const int ia = ((bf >> pl) << (pl + 1)) | (bf & ((1 << pl) - 1));
-            const size_t u = base | ((size_t)(ia >> p.c) << p.h) | (size_t)(ia & cmask);
-            bf64_apply<INV>(s, ia, ia | (1 << pl), lt[u >> (pbit + 1)] ^ sh);
-        }
-        __syncthreads();
-    }
-
-    for (int li = tid; li < E; li += nt) dst[base | ((size_t)(li >> p.c) << p.h) | (size_t)(li & cmask)] = s[li];
-}
-
-// Forward: last pass — pair bits a_low-1 .. 0, then natural-order (bit-reversed) store.
-// Inverse: first pass — natural-order load, pair bits 0 .. a_low-1, block-order store.
-// natural-order side: slot sidx -> (tile g, lo, t' = rev(top)); consecutive sidx = consecutive addresses
-// block-order side  : slot e    -> (tile g, top, lo)
-template<bool INV>
-__global__ void __launch_bounds__(512) k64_bfly_edge(BfParams64 p)
-{
-    extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
-    uint64_t *s = iopx_smem;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int tb = p.a_low + p.c_top;                   // bits of one tile
-    const int E = 1 << (tb + p.g_bits);                 // elements in LDS (2^g_bits tiles)
-    const int midbits = p.d - tb;                       // tile index bits inside a coset
-    const size_t unit0 = (size_t)blockIdx.x << p.g_bits;
-    const int lomask = (1 << p.a_low) - 1, tmask = (1 << p.c_top) - 1;
-
-    if (!INV) {
-        for (int e = tid; e < E; e += nt) {
-            const size_t unit = unit0 + (size_t)(e >> tb);
-            if (unit >= p.total_units) continue;
-            const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
-            const int li = e & ((1 << tb) - 1), top = li >> p.a_low, lo = li & lomask;
-            const size_t u = ((size_t)top << (p.d - p.c_top)) | (mid << p.a_low) | (size_t)lo;
-            s[e] = (p.src_shared ? p.src : p.src + (coset << p.d))[u];
-        }
-    } else {
-        for (int sidx = tid; sidx < E; sidx += nt) {
-            const size_t unit = unit0 + (size_t)(sidx >> tb);
-            if (unit >= p.total_units) continue;
-            const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
-            const int tp = sidx & tmask, lo = (sidx >> p.c_top) & lomask;
-            const int top = (int)bitrev64((uint32_t)tp, p.c_top);
-            const size_t v = ((size_t)bitrev64((uint32_t)lo, p.a_low) << (p.d - p.a_low)) |
-                             ((size_t)bitrev64((uint32_t)mid, midbits) << p.c_top) | (size_t)tp;
-            s[((sidx >> tb) << tb) | (top << p.a_low) | lo] = p.src[(coset << p.d) + v];
-        }
-    }
-    __syncthreads();
-
-    for (int t = 0; t < p.a_low; ++t) {
-        const int pbit = INV ? t : p.a_low - 1 - t;
-        const uint64_t *lt = p.ltab + ((((size_t)1) << (p.d - 1 - pbit)) - 1);
-        // one tile per workgroup: the coset, and with it the level's shift term, is uniform over the workgroup
-        const uint64_t sh0 = p.g_bits == 0 ? bf64_shift_term(p, unit0 >> midbits, pbit) : 0;
-        for (int bf = tid; bf < (E >> 1); bf += nt) {
-            const int low = bf & ((1 << pbit) - 1), high = bf >> pbit;
-            const int ia = (high << (pbit + 1)) | low, ib = ia | (1 << pbit);
-            const size_t unit = unit0 + (size_t)(ia >> tb);
-            if (unit >= p.total_units) continue;
-            const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
-            const int li = ia & ((1 << tb) - 1), top = li >> p.a_low, lo = li & lomask;
-            const size_t u = ((size_t)top << (p.d - p.c_top)) | (mid << p.a_low) | (size_t)lo;
-            const uint64_t sh = p.g_bits == 0 ? sh0 : bf64_shift_term(p, coset, pbit);
-            bf64_apply<INV>(s, ia, ib, lt[u >> (pbit + 1)] ^ sh);
-        }
-        __syncthreads();
-    }
-
-    if (!INV) {
-        for (int sidx = tid; sidx < E; sidx += nt) {
-            const size_t unit = unit0 + (size_t)(sidx >> tb);
-            if (unit >= p.total_units) continue;
-            const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
-            const int tp = sidx & tmask, lo = (sidx >> p.c_top) & lomask;
-            const int top = (int)bitrev64((uint32_t)tp, p.c_top);
-            const size_t v = ((size_t)bitrev64((uint32_t)lo, p.a_low) << (p.d - p.a_low)) |
-                             ((size_t)bitrev64((uint32_t)mid, midbits) << p.c_top) | (size_t)tp;
-            p.dst[(coset << p.d) + v] = s[((sidx >> tb) << tb) | (top << p.a_low) | lo];
-        }
-    } else {
-        for (int e = tid; e < E; e += nt) {
-            const size_t unit = unit0 + (size_t)(e >> tb);
-            if (unit >= p.total_units) continue;
-            const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
-            const int li = e & ((1 << tb) - 1), top = li >> p.a_low, lo = li & lomask;
-            p.dst[(coset << p.d) + (((size_t)top << (p.d - p.c_top)) | (mid << p.a_low) | (size_t)lo)] = s[e];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// FRI fold (fri_aux.tcc:36-103) in the inversion-free nested form of fri_add.hip: a coset of 2^eta is folded eta times by two,
-//     g[J] = f[2J] + (f[2J] + f[2J+1]) * (x + v_{2J}) / b_0 ,
-// each time over the domain derived by q(X) = X^2 + b_0 X.  (x + v_{2J}) / b_0 is GF(2)-affine in the bits of J.  One launch folds up to
-// three levels in registers: a lane reads its 2^ETA consecutive elements and writes one.
-// ---------------------------------------------------------------------------------------------
-#define FOLD64_MAX_ETA 3
-struct FoldParams64 {
-    const uint64_t *src;
-    uint64_t *dst;
-    const uint64_t *consts[FOLD64_MAX_ETA];   // level e: [0] = (x + s) / b0, [1 + k] = b_{k+1} / b0 of that level's domain
-    int nbits[FOLD64_MAX_ETA];                // number of [1 + k] entries: log2 of the level's output size
-    size_t n_out;
-};
-
-template<int ETA>
-__global__ void __launch_bounds__(256) k64_fri_fold(FoldParams64 p)
-{
-    for (size_t C = (size_t)blockIdx.x * blockDim.x + threadIdx.x; C < p.n_out; C += (size_t)gridDim.x * blockDim.x) {
-        uint64_t v[1 << ETA];
-#pragma unroll
-        for (int i = 0; i < (1 << ETA); ++i) v[i] = p.src[(C << ETA) + i];
-#pragma unroll
-        for (int e = 0; e < ETA; ++e) {
-            const int skip = ETA - 1 - e;               // pair J = C 2^skip + q: the low `skip` index bits belong to the in-coset pair q
-            uint64_t m = p.consts[e][0];
-            for (int k = skip; k < p.nbits[e]; ++k) if ((C >> (k - skip)) & 1) m ^= p.consts[e][1 + k];
-#pragma unroll
-            for (int q = 0; q < (1 << skip); ++q) {
-                uint64_t mq = m;
-#pragma unroll
-                for (int k = 0; k < skip; ++k) if ((q >> k) & 1) mq ^= p.consts[e][1 + k];
-                v[q] = v[2 * q] ^ g64_word(g64_mul(g64_from(v[2 * q] ^ v[2 * q + 1]), g64_from(mq)));
-            }
-        }
-        p.dst[C] = v[0];
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// LDT combination (ldt_reducer_aux.tcc:39-131) over an affine subspace: x^(2^i) is GF(2)-linear, so x_j^(2^i) is a subset sum of
-// basis[k]^(2^i) over the bits of j (exponentiation.tcc:3-19) and x_j^e the product over the set bits of e.  The host orders the oracles
-// by their bump exponent: a lane computes x_j^e once per distinct exponent.
-// ---------------------------------------------------------------------------------------------
-struct LdtParams64 {
-    const uint64_t *const *oracles; // device array of num_oracles device pointers, grouped by exponent
-    uint64_t *out;
-    const uint64_t *tab;            // [bit i][0] = shift^(2^i), [bit i][1 + k] = basis[k]^(2^i); (m + 1) elements per bit
-    const uint64_t *coef;           // per oracle: c[k], then the coefficient of its shifted copy (unused when maximal)
-    const uint64_t *expo;           // per oracle: max_degree - degree_k (0 = maximal)
-    size_t n;
-    int m, num_oracles;
-};
-
-__global__ void __launch_bounds__(256) k64_ldt_combine(LdtParams64 p)
-{
-    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < p.n; j += (size_t)gridDim.x * blockDim.x) {
-        uint64_t acc = 0, have_e = 0;
-        gf64 xe = g64_from(1);
-        for (int o = 0; o < p.num_oracles; ++o) {
-            const uint64_t f = p.oracles[o][j];
-            uint64_t c = p.coef[2 * o];
-            const uint64_t e = p.expo[o];
-            if (e) {
-                if (e != have_e) {                      // uniform: x_j^e for this group of oracles
-                    xe = g64_from(1);
-                    bool first = true;
-                    uint64_t r = e;
-                    for (int i = 0; r; ++i, r >>= 1) {
-                        if (!(r & 1)) continue;
-                        const uint64_t *t = p.tab + (size_t)i * (p.m + 1);
-                        uint64_t v = t[0];
-                        for (int k = 0; k < p.m; ++k) if ((j >> k) & 1) v ^= t[1 + k];
-                        xe = first ? g64_from(v) : g64_mul(xe, g64_from(v));
-                        first = false;
-                    }
-                    have_e = e;
-                }
-                c ^= g64_word(g64_mul(g64_from(p.coef[2 * o + 1]), xe));
-            }
-            acc ^= g64_word(g64_mul(g64_from(c), g64_from(f)));
-        }
-        p.out[j] = acc;
-    }
-}
-
-__global__ void k64_mul(const uint64_t *a, const uint64_t *b, uint64_t *out, size_t count)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
-        out[i] = g64_word(g64_mul(g64_from(a[i]), g64_from(b[i])));
-}
-
-__global__ void k64_inv(const uint64_t *a, uint64_t *out, size_t count)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
-        out[i] = g64_word(g64_inv(g64_from(a[i])));
-}
-
-// ---------------------------------------------------------------------------------------------
-// host: plans
-// ---------------------------------------------------------------------------------------------
-struct P1Pass64 { int c, h, A, j0, j1, k_start, k_end, twist_first; };
-struct P2Pass64 { int c, h, A, p_hi, p_lo; };
-
-struct AddPlan64 {
-    int d = 0;
-    std::vector<hgf64> betainv;             // 1 / beta_j of recursion level j (fft.tcc:86)
-    std::vector<uint64_t> sq, sq_inv;       // level j: beta_j^(2^k) (and of the inverse), d entries per level
-    DevBuf ltab, pow, pow_inv;
-    bool have_pow = false, have_pow_inv = false;
-    std::vector<P1Pass64> p1;
-    std::vector<P2Pass64> p2_upper;         // forward order
-    int a_low = 0, c_top = 0, g_bits = 0;
-
-    // the d recursed values of a shift (or of a coset basis vector: the recursion is GF(2)-linear), fft.tcc:94-96
-    void recurse(hgf64 v, uint64_t *out) const
+    // the host side
+    typedef hgf64 host;
+    static const char *stem() { return "k64_"; }
+    static const char *option(int i)
     {
-        for (int j = 0; j < d; ++j) {
-            const hgf64 ns = v * betainv[j];
-            out[j] = ns.v;
-            v = ns.squared() + ns;
-        }
+        static const char *const names[4] = { "IOPX_GF64_TILE_BITS", "IOPX_GF64_P1_COLS", "IOPX_GF64_P2_COLS", "IOPX_GF64_P2_TOP" };
+        return names[i];
     }
+    static constexpr int TILE_DEFAULT = 12, TILE_MAX = 12;      // 2^12 elements = 32 KiB of LDS
+    static constexpr int P1_COLS_DEFAULT = 4, P2_COLS_DEFAULT = 4, P2_TOP_DEFAULT = 4;      // 16 x 8 B = one line
+    static constexpr int UPPER_WAVES = 1;                       // kx_bfly_upper: 66 registers, no occupancy to bound them to
+    static constexpr int STAGE_BITS = 25;                       // 256 MiB of staging
+    static constexpr bool SPLIT_ACCESS = false;                 // an element is one 64-bit word
+    static const char *cold_plan() { return "gf64_plan"; }
+    static const char *cold_pow() { return "gf64_pow_tables"; }
+    static constexpr uint64_t LDT_TAG = 0x6c64743634;           // "ldt64"
+    static constexpr size_t CACHE_BYTES = (size_t)3 << 30;
 };
 
-// Plans are handed out as shared_ptr: a caller keeps its plan alive while another thread's insertion evicts the cache.  A plan of dimension d
-// holds 8 * 2^d bytes of twiddles and, once a direction has run, 16 * 2^d bytes of twist powers for it (40 * 2^d bytes with both: 1.25 GiB
-// at d = 25); the cache is bounded by PLAN64_CACHE_BYTES of such tables (and 64 entries), and cleared as a whole when an insertion would pass that.
-static const size_t PLAN64_CACHE_BYTES = (size_t)3 << 30;
-static std::mutex g_plan64_mu;
-static std::map<std::vector<uint64_t>, std::shared_ptr<AddPlan64>> g_plans64;
-static size_t plan64_bytes(const AddPlan64 &pl) { return pl.ltab.bytes + pl.pow.bytes + pl.pow_inv.bytes; }
+} // namespace iopx
 
-void clear_gf64_plans()
-{
-    std::lock_guard<std::mutex> lk(g_plan64_mu);
-    g_plans64.clear();
-}
+#include "gfx_additive.h"
 
-static void schedule64(AddPlan64 &pl, const Tuning64 &tu)
-{
-    const int d = pl.d, T = tu.tile_bits;
-    // phase 1: a level whose index bits [j, d) fit one tile runs there with every level after it; a level before that takes one pass per
-    // run of A - 1 network steps (a tile of 2^A rows holds the steps whose two bits lie inside it)
-    const int cp = std::min(tu.p1_cols, T - 2);
-    for (int j = 0; j < d; ++j) {
-        if (d - j <= T) {
-            const int A = d - j;
-            pl.p1.push_back({ std::min(T - A, j), j, A, j, d - 1, d - 2, d - 1, 1 });
-            break;
-        }
-        int top = d - 1, first = 1;
-        for (;;) {
-            const int h = std::max(j, top + 1 - (T - cp)), c = std::min(cp, h), A = top + 1 - h;
-            pl.p1.push_back({ c, h, A, j, j, top - 1, h, first });
-            first = 0;
-            if (h == j) break;
-            top = h;
-        }
-    }
-    // phase 2: the last pass holds the low a_low pair bits (and 2^c_top natural-order runs), upper passes the rest from the top down
-    if (d <= T) { pl.a_low = d; pl.c_top = 0; pl.g_bits = T - d; return; }
-    pl.c_top = std::min(tu.p2_top, T - 1);
-    pl.a_low = T - pl.c_top;
-    pl.g_bits = 0;
-    const int c = std::min(tu.p2_cols, pl.a_low), amax = T - c;
-    for (int top = d - 1; top >= pl.a_low;) {
-        const int h = std::max(pl.a_low, top + 1 - amax);
-        pl.p2_upper.push_back({ c, h, top + 1 - h, top, h });
-        top = h - 1;
-    }
-}
-
-static int get_plan64(const uint64_t *basis, int d, std::shared_ptr<AddPlan64> *out)
-{
-    const Tuning64 tu = tuning64();
-    std::vector<uint64_t> key(basis, basis + d);
-    key.push_back((uint64_t)d);
-    key.push_back((uint64_t)tu.tile_bits | ((uint64_t)tu.p1_cols << 8) | ((uint64_t)tu.p2_cols << 16) | ((uint64_t)tu.p2_top << 24));
-    std::lock_guard<std::mutex> lk(g_plan64_mu);
-    auto it = g_plans64.find(key);
-    if (it != g_plans64.end()) { *out = it->second; return IOPX_OK; }
-    size_t resident = ((size_t)8) << d;
-    for (const auto &kv : g_plans64) resident += plan64_bytes(*kv.second);
-    if (g_plans64.size() >= 64 || resident > PLAN64_CACHE_BYTES) { (void)hipStreamSynchronize(stream()); g_plans64.clear(); }
-    ColdScope cs_("gf64_plan");
-    std::shared_ptr<AddPlan64> pl(new AddPlan64);
-    pl->d = d;
-    std::vector<hgf64> b2(d);
-    for (int i = 0; i < d; ++i) b2[i] = hgf64(basis[i]);
-    std::vector<uint64_t> rec;                      // recursed basis vectors, level j has d-1-j
-    for (int j = 0; j < d; ++j) {
-        const hgf64 beta = b2[d - 1 - j];
-        if (beta.is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "additive FFT: basis vectors are linearly dependent");
-        const hgf64 binv = beta.inverse();
-        pl->betainv.push_back(binv);
-        hgf64 s = beta, si = binv;
-        for (int k = 0; k < d; ++k) { pl->sq.push_back(s.v); pl->sq_inv.push_back(si.v); s = s.squared(); si = si.squared(); }
-        for (int i = 0; i < d - 1 - j; ++i) {
-            const hgf64 nb = b2[i] * binv;
-            rec.push_back(nb.v);
-            b2[i] = nb.squared() + nb;
-        }
-    }
-    schedule64(*pl, tu);
-    int rc = pl->ltab.alloc(((size_t)8) << d);
-    if (rc != IOPX_OK) return rc;
-    if (d > 1) {
-        TmpBuf drec;
-        if ((rc = drec.alloc(rec.size() * 8)) != IOPX_OK) return rc;
-        if ((rc = upload(drec.p, rec.data(), rec.size() * 8)) != IOPX_OK) return rc;
-        const size_t count = ((size_t)1 << d) - 1;
-        hipLaunchKernelGGL(k64_build_ltab, dim3(grid64(count, 256)), dim3(256), 0, stream(), pl->ltab.u64(), drec.u64(), d, count);
-        IOPX_HIP(hipGetLastError());
-    } else {
-        if ((rc = fill_bytes(pl->ltab.p, 0, 16)) != IOPX_OK) return rc;
-    }
-    *out = pl;
-    g_plans64[key] = std::move(pl);
-    return IOPX_OK;
-}
-
-// twist-power tables of one direction, built on first use
-static int ensure_pow64(AddPlan64 &pl, bool inverse)
-{
-    std::lock_guard<std::mutex> lk(g_plan64_mu);       // the tables of a shared plan are built once
-    if (inverse ? pl.have_pow_inv : pl.have_pow) return IOPX_OK;
-    ColdScope cs_("gf64_pow_tables");
-    DevBuf &buf = inverse ? pl.pow_inv : pl.pow;
-    const std::vector<uint64_t> &sq = inverse ? pl.sq_inv : pl.sq;
-    const int d = pl.d;
-    int rc = buf.alloc(((size_t)16) << d);
-    if (rc != IOPX_OK) return rc;
-    TmpBuf dsq;
-    if ((rc = dsq.alloc(sq.size() * 8)) != IOPX_OK) return rc;
-    if ((rc = upload(dsq.p, sq.data(), sq.size() * 8)) != IOPX_OK) return rc;
-    for (int j = 0; j < d; ++j) {
-        const size_t off = (((size_t)2) << d) - (((size_t)2) << (d - j)), count = (size_t)1 << (d - j);
-        hipLaunchKernelGGL(k64_pow_direct, dim3(grid64(count, 256)), dim3(256), 0, stream(), buf.u64() + off, dsq.u64() + (size_t)j * d, d - j, count);
-    }
-    IOPX_HIP(hipGetLastError());
-    (inverse ? pl.have_pow_inv : pl.have_pow) = true;
-    return IOPX_OK;
-}
-
-template<bool INV>
-static int run_phase1_64(AddPlan64 &pl, uint64_t *S)
-{
-    int rc = ensure_pow64(pl, INV);
-    if (rc != IOPX_OK) return rc;
-    const size_t np = pl.p1.size();
-    for (size_t i = 0; i < np; ++i) {
-        const P1Pass64 &ps = pl.p1[INV ? np - 1 - i : i];
-        P1Params64 p;
-        p.S = S; p.pow = (INV ? pl.pow_inv : pl.pow).u64(); p.d = pl.d;
-        p.c = ps.c; p.h = ps.h; p.A = ps.A; p.j0 = ps.j0; p.j1 = ps.j1; p.k_start = ps.k_start; p.k_end = ps.k_end; p.twist_first = ps.twist_first;
-        const int tb = ps.c + ps.A;
-        const size_t E = (size_t)1 << tb, grid = (size_t)1 << (pl.d - tb);
-        const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 4));
-        ProfScope ps_(INV ? "k64_phase1_inv" : "k64_phase1", ((size_t)16) << pl.d);
-        hipLaunchKernelGGL(k64_phase1<INV>, dim3((unsigned)grid), dim3(threads), E * 8, stream(), p);
-    }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
-}
-
-// rs[v * d + p] for the shift (v = 0) and the nhi coset basis vectors, on the device
-static int upload_rs64(const AddPlan64 &pl, uint64_t shift, const uint64_t *hi_basis, int nhi, TmpBuf &drs)
-{
-    std::vector<uint64_t> rs((size_t)(1 + nhi) * pl.d);
-    pl.recurse(hgf64(shift), rs.data());
-    for (int v = 0; v < nhi; ++v) pl.recurse(hgf64(hi_basis[v]), rs.data() + (size_t)(1 + v) * pl.d);
-    int rc = drs.alloc(rs.size() * 8);
-    if (rc != IOPX_OK) return rc;
-    return upload(drs.p, rs.data(), rs.size() * 8);
-}
-
-static BfParams64 bf_params64(const AddPlan64 &pl, const uint64_t *rs, int nhi)
-{
-    BfParams64 p;
-    memset(&p, 0, sizeof(p));
-    p.ltab = pl.ltab.u64(); p.rs = rs; p.d = pl.d; p.nhi = nhi;
-    p.a_low = pl.a_low; p.c_top = pl.c_top; p.g_bits = pl.g_bits;
-    return p;
-}
-
-static void launch_upper64(bool inv, BfParams64 p, const P2Pass64 &ps, size_t cosets)
-{
-    p.c = ps.c; p.h = ps.h; p.A = ps.A; p.p_hi = ps.p_hi; p.p_lo = ps.p_lo;
-    const int tb = ps.c + ps.A;
-    const size_t E = (size_t)1 << tb, grid = cosets << (p.d - tb);
-    const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 2));
-    ProfScope ps_(inv ? "k64_bfly_upper_inv" : "k64_bfly_upper", (cosets * 16) << p.d);
-    if (inv) hipLaunchKernelGGL(k64_bfly_upper<true>, dim3((unsigned)grid), dim3(threads), E * 8, stream(), p);
-    else hipLaunchKernelGGL(k64_bfly_upper<false>, dim3((unsigned)grid), dim3(threads), E * 8, stream(), p);
-}
-
-static void launch_edge64(bool inv, BfParams64 p, size_t cosets)
-{
-    const int tb = p.a_low + p.c_top;
-    p.total_units = cosets << (p.d - tb);
-    const size_t E = (size_t)1 << (tb + p.g_bits), grid = (p.total_units + (((size_t)1) << p.g_bits) - 1) >> p.g_bits;
-    const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 2));
-    ProfScope ps_(inv ? "k64_bfly_edge_inv" : "k64_bfly_edge", (cosets * 16) << p.d);
-    if (inv) hipLaunchKernelGGL(k64_bfly_edge<true>, dim3((unsigned)grid), dim3(threads), E * 8, stream(), p);
-    else hipLaunchKernelGGL(k64_bfly_edge<false>, dim3((unsigned)grid), dim3(threads), E * 8, stream(), p);
-}
-
-// forward phase 2 of cosets [coset_begin, +coset_count): W (2^d, block order after phase 1, overwritten when it is the only coset) -> out
-static int run_phase2_fwd64(AddPlan64 &pl, uint64_t *W, uint64_t *out, const uint64_t *rs, int nhi, size_t coset_begin, size_t coset_count)
-{
-    const int d = pl.d;
-    BfParams64 p = bf_params64(pl, rs, nhi);
-    if (pl.p2_upper.empty()) {                      // one tile per coset: W -> out in one pass
-        // the unit count of a launch stays below 2^31 workgroups
-        const size_t step = (size_t)1 << 30;
-        for (size_t c0 = 0; c0 < coset_count; c0 += step) {
-            const size_t cnt = std::min(step, coset_count - c0);
-            p.src = W; p.src_shared = 1; p.dst = out + (c0 << d); p.coset_base = coset_begin + c0;
-            launch_edge64(false, p, cnt);
-        }
-        IOPX_HIP(hipGetLastError());
-        return IOPX_OK;
-    }
-    if (coset_count == 1) {
-        p.src = W; p.dst = W; p.src_shared = 0; p.coset_base = coset_begin;
-        for (const P2Pass64 &ps : pl.p2_upper) launch_upper64(false, p, ps, 1);
-        p.dst = out;
-        launch_edge64(false, p, 1);
-        IOPX_HIP(hipGetLastError());
-        return IOPX_OK;
-    }
-    // block-order staging for a group of cosets (the last pass permutes: it cannot run in place), at most 2^25 elements
-    const size_t group = std::min(coset_count, std::max<size_t>(1, ((size_t)1 << 25) >> d));
-    TmpBuf stage;
-    int rc = stage.alloc((group * 8) << d);
-    if (rc != IOPX_OK) return rc;
-    for (size_t c0 = 0; c0 < coset_count; c0 += group) {
-        const size_t cnt = std::min(group, coset_count - c0);
-        p.coset_base = coset_begin + c0;
-        p.dst = stage.u64();
-        for (size_t i = 0; i < pl.p2_upper.size(); ++i) {
-            p.src = i == 0 ? W : stage.u64(); p.src_shared = i == 0;
-            launch_upper64(false, p, pl.p2_upper[i], cnt);
-        }
-        p.src = stage.u64(); p.src_shared = 0; p.dst = out + (c0 << d);
-        launch_edge64(false, p, cnt);
-    }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
-}
-
-static int check_basis_args64(const uint64_t *basis, size_t m, const uint64_t *shift)
-{
-    if (m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension %zu too large", m);
-    if ((m > 0 && !basis) || !shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null basis/shift");
-    return IOPX_OK;
-}
-
+namespace iopx {
+void clear_gf64_plans() { clear_plans_x<Elem64>(); }
 } // namespace iopx
 
 using namespace iopx;
 
 extern "C" {
 
-// Cosets [coset_begin, coset_begin + coset_count) of span(basis[0..d)), d = ceil(log2 n_coeffs): the
-// contiguous output block [coset_begin * 2^d, (coset_begin + coset_count) * 2^d) of the full transform.
 int iopx_add_lde_gf64_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                           const uint64_t *shift, size_t coset_begin, size_t coset_count, uint64_t *d_out)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    rc = check_basis_args64(basis, m, shift);
-    if (rc != IOPX_OK) return rc;
-    const size_t n = (size_t)1 << m;
-    if (n_coeffs > n) return fail(IOPX_ERR_INVALID_ARGUMENT, "additive FFT: %zu coefficients exceed the domain size %zu", n_coeffs, n);
-    if (!d_out || (n_coeffs && !d_coeffs)) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
-    const int d = n_coeffs <= 1 ? 0 : (int)ceil_log2(n_coeffs);
-    const int nhi = (int)m - d;
-    const size_t all_cosets = (size_t)1 << nhi;
-    if (coset_count == 0 || coset_begin >= all_cosets || coset_count > all_cosets - coset_begin)
-        return fail(IOPX_ERR_INVALID_ARGUMENT, "coset range [%zu, +%zu) outside the %zu cosets of the transform", coset_begin, coset_count, all_cosets);
-    if (n_coeffs <= 1) {
-        { ProfScope ps_("k64_fill"); hipLaunchKernelGGL(k64_fill, dim3(grid64(coset_count, 256)), dim3(256), 0, stream(), d_out, d_coeffs, (int)(n_coeffs == 1), coset_count); }
-        IOPX_HIP(hipGetLastError());
-        return IOPX_OK;
-    }
-    std::shared_ptr<AddPlan64> pl;
-    rc = get_plan64(basis, d, &pl);
-    if (rc != IOPX_OK) return rc;
-    TmpBuf drs;
-    rc = upload_rs64(*pl, shift[0], basis + d, nhi, drs);
-    if (rc != IOPX_OK) return rc;
-
-    // phase 1 runs in a work buffer: the last pass permutes into natural order and therefore writes out of place
-    const size_t nd = (size_t)1 << d;
-    TmpBuf work;
-    rc = work.alloc(nd * 8);
-    if (rc != IOPX_OK) return rc;
-    uint64_t *W = work.u64();
-    { ProfScope ps_("k64_pad_copy"); hipLaunchKernelGGL(k64_pad_copy, dim3(grid64(nd, 256)), dim3(256), 0, stream(), W, d_coeffs, n_coeffs, nd); }
-    rc = run_phase1_64<false>(*pl, W);
-    if (rc != IOPX_OK) return rc;
-    return run_phase2_fwd64(*pl, W, d_out, drs.u64(), nhi, coset_begin, coset_count);      // temporaries are released in stream order
+    return x_add_lde_dev<Elem64>(d_coeffs, n_coeffs, basis, m, shift, coset_begin, coset_count, d_out);
 }
 
 int iopx_add_fft_gf64_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                           const uint64_t *shift, uint64_t *d_out)
 {
-    if (m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension %zu too large", m);
-    const size_t n = (size_t)1 << m;
-    if (n_coeffs > n) return fail(IOPX_ERR_INVALID_ARGUMENT, "additive FFT: %zu coefficients exceed the domain size %zu", n_coeffs, n);
-    const int d = n_coeffs <= 1 ? 0 : (int)ceil_log2(n_coeffs);
-    return iopx_add_lde_gf64_dev(d_coeffs, n_coeffs, basis, m, shift, 0, (size_t)1 << ((int)m - d), d_out);
+    return x_add_fft_dev<Elem64>(d_coeffs, n_coeffs, basis, m, shift, d_out);
 }
 
 int iopx_add_ifft_gf64_dev(const uint64_t *d_evals, const uint64_t *basis, size_t m, const uint64_t *shift,
                            uint64_t *d_out)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    rc = check_basis_args64(basis, m, shift);
-    if (rc != IOPX_OK) return rc;
-    if (!d_evals || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
-    if (m == 0) return copy_d2d(d_out, d_evals, 8);
-    std::shared_ptr<AddPlan64> pl;
-    rc = get_plan64(basis, (int)m, &pl);
-    if (rc != IOPX_OK) return rc;
-    TmpBuf drs;
-    rc = upload_rs64(*pl, shift[0], nullptr, 0, drs);
-    if (rc != IOPX_OK) return rc;
-    // the first pass permutes: in place, the transform runs in a work buffer and is copied back
-    TmpBuf work;
-    uint64_t *W = d_out;
-    if (d_evals == d_out) {
-        rc = work.alloc(((size_t)8) << m);
-        if (rc != IOPX_OK) return rc;
-        W = work.u64();
-    }
-    BfParams64 p = bf_params64(*pl, drs.u64(), 0);
-    p.src = d_evals; p.dst = W;
-    launch_edge64(true, p, 1);
-    p.src = W;
-    for (size_t i = pl->p2_upper.size(); i-- > 0;) launch_upper64(true, p, pl->p2_upper[i], 1);
-    IOPX_HIP(hipGetLastError());
-    rc = run_phase1_64<true>(*pl, W);
-    if (rc != IOPX_OK) return rc;
-    if (W != d_out) return copy_d2d(d_out, W, ((size_t)8) << m);
-    return IOPX_OK;
+    return x_add_ifft_dev<Elem64>(d_evals, basis, m, shift, d_out);
 }
 
 int iopx_add_fft_gf64(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                       const uint64_t *shift, uint64_t *out)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    rc = check_basis_args64(basis, m, shift);
-    if (rc != IOPX_OK) return rc;
-    const size_t n = (size_t)1 << m;
-    if (n_coeffs > n) return fail(IOPX_ERR_INVALID_ARGUMENT, "additive FFT: %zu coefficients exceed the domain size %zu", n_coeffs, n);
-    if (!out || (n_coeffs && !coeffs)) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
-    DevBuf din, dout;
-    if ((rc = din.alloc(n_coeffs * 8)) != IOPX_OK) return rc;
-    if ((rc = dout.alloc(n * 8)) != IOPX_OK) return rc;
-    if (n_coeffs) IOPX_HIP(copy_h2d(din.p, coeffs, n_coeffs * 8, stream()));
-    rc = iopx_add_fft_gf64_dev(n_coeffs ? din.u64() : nullptr, n_coeffs, basis, m, shift, dout.u64());
-    if (rc != IOPX_OK) return rc;
-    IOPX_HIP(copy_d2h(out, dout.p, n * 8, stream()));
-    IOPX_HIP(hipStreamSynchronize(stream()));
-    return IOPX_OK;
+    return x_add_fft_host<Elem64>(coeffs, n_coeffs, basis, m, shift, out);
 }
 
 int iopx_add_ifft_gf64(const uint64_t *evals, const uint64_t *basis, size_t m, const uint64_t *shift,
                        uint64_t *out)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    rc = check_basis_args64(basis, m, shift);
-    if (rc != IOPX_OK) return rc;
-    if (!evals || !out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
-    const size_t n = (size_t)1 << m;
-    DevBuf din, dout;
-    if ((rc = din.alloc(n * 8)) != IOPX_OK) return rc;
-    if ((rc = dout.alloc(n * 8)) != IOPX_OK) return rc;
-    IOPX_HIP(copy_h2d(din.p, evals, n * 8, stream()));
-    rc = iopx_add_ifft_gf64_dev(din.u64(), basis, m, shift, dout.u64());
-    if (rc != IOPX_OK) return rc;
-    IOPX_HIP(copy_d2h(out, dout.p, n * 8, stream()));
-    IOPX_HIP(hipStreamSynchronize(stream()));
-    return IOPX_OK;
+    return x_add_ifft_host<Elem64>(evals, basis, m, shift, out);
 }
 
-// evaluate_next_f_i_over_entire_domain for affine subspaces over gf64 (fri_aux.tcc:5-34 -> :36-103)
 int iopx_fri_fold_add_gf64_dev(const uint64_t *d_f_i, const uint64_t *basis, size_t m, const uint64_t *shift,
                                size_t coset_size, const uint64_t *x_i, uint64_t *d_next)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension %zu too large", m);
-    if (!d_f_i || !d_next || !shift || !x_i || (m && !basis)) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (coset_size == 0 || (coset_size & (coset_size - 1))) return fail(IOPX_ERR_INVALID_ARGUMENT, "coset size %zu is not a power of two", coset_size);
-    const int eta = (int)ceil_log2(coset_size);
-    if ((size_t)eta > m) return fail(IOPX_ERR_INVALID_ARGUMENT, "coset size %zu exceeds the domain size", coset_size);
-    const size_t n = (size_t)1 << m;
-    if (eta == 0) return copy_d2d(d_next, d_f_i, n * 8);      // cosets of one element: the interpolant is the constant f(v)
-
-    std::vector<hgf64> b(m);
-    for (size_t i = 0; i < m; ++i) b[i] = hgf64(basis[i]);
-    hgf64 s(shift[0]), x(x_i[0]);
-    // constants of all eta levels, uploaded once
-    std::vector<uint64_t> hc;
-    std::vector<size_t> off(eta);
-    for (int e = 0; e < eta; ++e) {
-        if (b[0].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "FRI fold: basis vectors are linearly dependent");
-        const hgf64 b0 = b[0], b0inv = b0.inverse();
-        off[e] = hc.size();
-        hc.push_back(((x + s) * b0inv).v);
-        for (size_t k = 1; k < b.size(); ++k) hc.push_back((b[k] * b0inv).v);
-        // derived domain: q(X) = X^2 + b0 X
-        std::vector<hgf64> nb;
-        for (size_t k = 1; k < b.size(); ++k) nb.push_back(b[k].squared() + b0 * b[k]);
-        s = s.squared() + b0 * s;
-        x = x.squared() + b0 * x;
-        b.swap(nb);
-    }
-    TmpBuf dc;
-    if ((rc = dc.alloc(hc.size() * 8)) != IOPX_OK) return rc;
-    if ((rc = upload(dc.p, hc.data(), hc.size() * 8)) != IOPX_OK) return rc;
-
-    // launches of up to three levels each; intermediate vectors in temporaries
-    TmpBuf tmp[2];
-    const uint64_t *src = d_f_i;
-    size_t cur = n;
-    int which = 0;
-    for (int e = 0; e < eta;) {
-        const int step = std::min(FOLD64_MAX_ETA, eta - e);
-        const size_t n_out = cur >> step;
-        uint64_t *dst = d_next;
-        if (e + step != eta) {
-            if ((rc = tmp[which].alloc(n_out * 8)) != IOPX_OK) return rc;
-            dst = tmp[which].u64();
-            which ^= 1;
-        }
-        FoldParams64 fp;
-        memset(&fp, 0, sizeof(fp));
-        fp.src = src; fp.dst = dst; fp.n_out = n_out;
-        for (int t = 0; t < step; ++t) { fp.consts[t] = dc.u64() + off[e + t]; fp.nbits[t] = (int)m - 1 - (e + t); }
-        const int grid = grid64(n_out, 256);
-        ProfScope ps_("k64_fri_fold", (cur + n_out) * 8);
-        if (step == 1) hipLaunchKernelGGL(k64_fri_fold<1>, dim3(grid), dim3(256), 0, stream(), fp);
-        else if (step == 2) hipLaunchKernelGGL(k64_fri_fold<2>, dim3(grid), dim3(256), 0, stream(), fp);
-        else hipLaunchKernelGGL(k64_fri_fold<3>, dim3(grid), dim3(256), 0, stream(), fp);
-        src = dst;
-        cur = n_out;
-        e += step;
-    }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;                                 // constants / temporaries are released in stream order
+    return x_fri_fold_add_dev<Elem64>(d_f_i, basis, m, shift, coset_size, x_i, d_next);
 }
 
 int iopx_fri_fold_add_gf64(const uint64_t *f_i, const uint64_t *basis, size_t m, const uint64_t *shift,
                            size_t coset_size, const uint64_t *x_i, uint64_t *next)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension %zu too large", m);
-    if (!f_i || !next) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (coset_size == 0 || (coset_size & (coset_size - 1)) || coset_size > ((size_t)1 << m))
-        return fail(IOPX_ERR_INVALID_ARGUMENT, "bad coset size %zu", coset_size);
-    const size_t n = (size_t)1 << m, n_out = n / coset_size;
-    DevBuf din, dout;
-    if ((rc = din.alloc(n * 8)) != IOPX_OK) return rc;
-    if ((rc = dout.alloc(n_out * 8)) != IOPX_OK) return rc;
-    IOPX_HIP(copy_h2d(din.p, f_i, n * 8, stream()));
-    rc = iopx_fri_fold_add_gf64_dev(din.u64(), basis, m, shift, coset_size, x_i, dout.u64());
-    if (rc != IOPX_OK) return rc;
-    IOPX_HIP(copy_d2h(next, dout.p, n_out * 8, stream()));
-    IOPX_HIP(hipStreamSynchronize(stream()));
-    return IOPX_OK;
+    return x_fri_fold_add_host<Elem64>(f_i, basis, m, shift, coset_size, x_i, next);
 }
 
-// FRI_protocol::compute_domains, additive branch (libiop/protocols/ldt/fri/fri_ldt.tcc:310-338): L^(i+1) has basis q(basis[eta_i..])
-// and shift q(shift), q = the subspace polynomial of span(basis[0..eta_i)).  Host-only metadata.
 int iopx_fri_domains_gf64(const uint64_t *basis, size_t m, const uint64_t *shift, const size_t *localization, size_t num_reductions,
                           uint64_t *out_bases, uint64_t *out_shifts)
 {
-    if ((m > 0 && !basis) || !shift || (num_reductions > 0 && (!localization || !out_bases || !out_shifts))) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    std::vector<hgf64> b(m);
-    for (size_t i = 0; i < m; ++i) b[i] = hgf64(basis[i]);
-    hgf64 s(shift[0]);
-    size_t off = 0;
-    for (size_t r = 0; r < num_reductions; ++r) {
-        const size_t eta = localization[r];
-        if (eta > b.size()) return fail(IOPX_ERR_INVALID_ARGUMENT, "localization parameters exceed the domain dimension");
-        const SubspacePoly64 q(b.data(), eta);
-        std::vector<hgf64> nb;
-        for (size_t k = eta; k < b.size(); ++k) nb.push_back(q.eval(b[k]));
-        s = q.eval(s);
-        b.swap(nb);
-        for (const hgf64 &v : b) out_bases[off++] = v.v;
-        out_shifts[r] = s.v;
-    }
-    return IOPX_OK;
+    return x_fri_domains<Elem64>(basis, m, shift, localization, num_reductions, out_bases, out_shifts);
 }
 
-// combined_LDT_virtual_oracle::evaluated_contents over the affine subspace (ldt_reducer_aux.tcc:39-131; constructor and
-// set_random_coefficients :3-37)
 int iopx_ldt_combine_gf64_dev(const void *const *d_oracles, size_t num_oracles, const size_t *degrees,
                               const uint64_t *random_coefficients, const uint64_t *basis, size_t m, const uint64_t *shift,
                               uint64_t *d_out)
 {
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (!d_oracles || !random_coefficients || !d_out || (m > 0 && !basis) || !shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension %zu too large", m);
-    if (!degrees || num_oracles == 0) return fail(IOPX_ERR_INVALID_ARGUMENT, "Expected same number of evaluations as in registration.");
-    // the bookkeeping of the constructor + set_random_coefficients: c = {1, random...}; oracle k takes c[k] and, as the i-th submaximal
-    // one, c[num + i] on its copy shifted by x^(max_degree - degree_k)
-    const size_t max_degree = *std::max_element(degrees, degrees + num_oracles);
-    auto coef = [&](size_t t) { return t == 0 ? (uint64_t)1 : random_coefficients[t - 1]; };
-    struct Entry { uint64_t ptr, own, shifted, expo; };
-    std::vector<Entry> ent;
-    uint64_t all = 0;
-    size_t sub = 0;
-    for (size_t k = 0; k < num_oracles; ++k) {
-        Entry e;
-        e.ptr = (uint64_t)(uintptr_t)d_oracles[k];
-        e.own = coef(k);
-        e.expo = max_degree - degrees[k];
-        e.shifted = e.expo ? coef(num_oracles + sub++) : 0;
-        all |= e.expo;
-        ent.push_back(e);
-    }
-    std::stable_sort(ent.begin(), ent.end(), [](const Entry &a, const Entry &b) { return a.expo < b.expo; });      // groups of one exponent
-    int nbits = 0;
-    while (nbits < 64 && (all >> nbits)) ++nbits;
-    // basis[k]^(2^i), shift^(2^i) by repeated squaring (exponentiation.tcc:10-18): depends on the domain and the exponent bits only, kept per domain
-    TmpBuf dtab, dmeta;
-    {
-        std::vector<uint64_t> key(basis, basis + m);
-        key.push_back(shift[0]); key.push_back(m); key.push_back((uint64_t)nbits); key.push_back(0x6c64743634);      // "ldt64"
-        rc = cached_domain_table(key, [&](std::vector<uint64_t> &htab) -> int {
-            std::vector<hgf64> cur;
-            cur.push_back(hgf64(shift[0]));
-            for (size_t k = 0; k < m; ++k) cur.push_back(hgf64(basis[k]));
-            for (int i = 0; i < (nbits ? nbits : 1); ++i) {
-                for (const hgf64 &v : cur) htab.push_back(v.v);
-                for (hgf64 &v : cur) v = v.squared();
-            }
-            return IOPX_OK;
-        }, dtab);
-        if (rc != IOPX_OK) return rc;
-    }
-    // the per-call tables travel in one block: oracle pointers, coefficient pairs, exponents
-    std::vector<uint64_t> meta(4 * num_oracles);
-    for (size_t k = 0; k < num_oracles; ++k) {
-        meta[k] = ent[k].ptr;
-        meta[num_oracles + 2 * k] = ent[k].own;
-        meta[num_oracles + 2 * k + 1] = ent[k].shifted;
-        meta[3 * num_oracles + k] = ent[k].expo;
-    }
-    if ((rc = dmeta.alloc(meta.size() * 8)) != IOPX_OK) return rc;
-    if ((rc = upload(dmeta.p, meta.data(), meta.size() * 8)) != IOPX_OK) return rc;
-    LdtParams64 p;
-    p.oracles = (const uint64_t *const *)dmeta.u64();
-    p.coef = dmeta.u64() + num_oracles; p.expo = dmeta.u64() + 3 * num_oracles;
-    p.out = d_out; p.tab = dtab.u64();
-    p.n = (size_t)1 << m; p.m = (int)m; p.num_oracles = (int)num_oracles;
-    { ProfScope ps_("k64_ldt_combine", (num_oracles + 1) * 8 * p.n); hipLaunchKernelGGL(k64_ldt_combine, dim3(grid64(p.n, 256)), dim3(256), 0, stream(), p); }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
+    return x_ldt_combine_dev<Elem64>(d_oracles, num_oracles, degrees, random_coefficients, basis, m, shift, d_out);
 }
 
-int iopx_gf64_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count)
-{
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (count == 0) return IOPX_OK;
-    if (!d_a || !d_b || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    { ProfScope ps_("k64_mul"); hipLaunchKernelGGL(k64_mul, dim3(grid64(count, 256)), dim3(256), 0, stream(), d_a, d_b, d_out, count); }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
-}
-
-int iopx_gf64_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count)
-{
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (count == 0) return IOPX_OK;
-    if (!d_a || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    { ProfScope ps_("k64_inv"); hipLaunchKernelGGL(k64_inv, dim3(grid64(count, 256)), dim3(256), 0, stream(), d_a, d_out, count); }
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
-}
-
-int iopx_gf64_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out)
-{
-    if (!a || !b || !out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    out[0] = (hgf64(a[0]) * hgf64(b[0])).v;
-    return IOPX_OK;
-}
-
-int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out)
-{
-    if (!x || !out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    if (x[0] == 0) return fail(IOPX_ERR_INVALID_ARGUMENT, "inverse of zero");
-    out[0] = hgf64(x[0]).inverse().v;
-    return IOPX_OK;
-}
+int iopx_gf64_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return x_mul_dev<Elem64>(d_a, d_b, d_out, count); }
+int iopx_gf64_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count) { return x_inv_dev<Elem64>(d_a, d_out, count); }
+int iopx_gf64_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) { return x_host_mul<Elem64>(a, b, out); }
+int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out) { return x_inverse_host<Elem64>(x, out); }
 
 } // extern "C"

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+#include "subspace_poly.h"
 
 namespace iopx {
 
@@ -12,6 +13,8 @@ struct hgf64 {
 
     hgf64() : v(0) {}
     explicit hgf64(uint64_t x) : v(x) {}
+    explicit hgf64(const uint64_t *w) : v(w[0]) {}     // from an element's words, as the wider fields' host types
+    void store(uint64_t *out) const { out[0] = v; }
     static hgf64 zero() { return hgf64(); }
     static hgf64 one() { return hgf64(1); }
 
@@ -71,25 +74,6 @@ struct hgf64 {
     }
 };
 
-// The subspace polynomial of span(basis[0..dim)): prod_{v in span} (X - v), a linearized polynomial (coeff[i] multiplies X^(2^i)), built
-// factor by factor as Z <- Z(X) (Z(X) + Z(b)) (libiop/algebra/polynomials/vanishing_polynomial.tcc:373-395).
-struct SubspacePoly64 {
-    std::vector<hgf64> coeff;
-    SubspacePoly64(const hgf64 *basis, size_t dim) : coeff(1, hgf64::one())
-    {
-        for (size_t k = 0; k < dim; ++k) {
-            const hgf64 zb = eval(basis[k]);
-            std::vector<hgf64> nxt(coeff.size() + 1, hgf64::zero());
-            for (size_t i = 0; i < coeff.size(); ++i) { nxt[i + 1] += coeff[i].squared(); nxt[i] += coeff[i] * zb; }
-            coeff.swap(nxt);
-        }
-    }
-    hgf64 eval(const hgf64 &x) const
-    {
-        hgf64 r = hgf64::zero(), xp = x;
-        for (size_t i = 0; i < coeff.size(); ++i) { r += coeff[i] * xp; xp = xp.squared(); }
-        return r;
-    }
-};
+typedef SubspacePolyX<hgf64> SubspacePoly64;
 
 } // namespace iopx

@@ -1,20 +1,31 @@
-// The additive arm over a wide binary field on gfx950, written once: additive FFT / IFFT / low-degree extension, FRI fold and domain chain,
-// LDT combination, vector helpers — kernels, host driver and the bodies of the C entries.  gf128.hip and gf256.hip include this text and
-// instantiate it for their element trait.
+// The additive arm over a binary field on gfx950, written once: additive FFT / IFFT / low-degree extension, FRI fold and domain chain,
+// LDT combination, vector helpers — kernels, host driver and the bodies of the C entries.  gf64.hip, gf128.hip and gf256.hip include this
+// text and instantiate it for their element trait.
 //
-// The transforms replace additive_FFT / additive_IFFT of the reference (libiop/algebra/fft.tcc:39-124, 126-204) with the two-phase schedule
-// of gf64.hip (phase 1: twist + Taylor network in place on 2^d elements; phase 2: the butterflies in block order once per coset of
-// span(basis[0..d)), the bit reversal folded into the last pass; the IFFT is the inverse schedule).
+// The transforms replace additive_FFT / additive_IFFT of the reference (libiop/algebra/fft.tcc:39-124, 126-204) in two phases:
+//
+//   phase 1  (coefficients -> Gao–Mateer basis), in place on 2^d elements, d = ceil(log2 n_coeffs): per level j the twist by
+//            beta_j^(idx >> j) (power table in HBM, built once per basis) and the Taylor-expansion XOR network on index bits (k+1, k),
+//            k = d-2 .. j (fft.tcc:62-83), in LDS tiles of 2^c contiguous columns x 2^A rows on consecutive index bits;
+//   phase 2  (the unwind butterflies, fft.tcc:102-120) without the bit reversal of fft.tcc:99: pair bit p = d-1 .. 0 in block order, the
+//            bit reversal folded into the addressing of the last pass.  It runs once per coset of span(basis[0..d)): the twiddles of two
+//            cosets differ by a per-level additive constant (the recursed shift is GF(2)-linear in the coset shift).
+//
+// A tile of 2^T elements carries T - c butterfly levels per upper pass and the low T - c_top levels + the bit reversal in the last one
+// (schedule_x); the pass structure does not depend on the element's width, only T does.  No wave-uniform multiplier form is used: the
+// general product is issued per element.  The IFFT runs the exact inverse schedule.
 //
 // An element trait F gives
-//   W, mem (the form in HBM and LDS, 16-byte aligned), reg, load<A16> / store<A16>, zero, one, add, unpack, pack, rmul, mul, inv      (device)
+//   W, mem (the form in HBM and LDS), reg, load<A16> / store<A16>, zero, one, add, unpack, pack, rmul, mul, inv                        (device)
 //   host (the portable twin: construction from words, store, is_zero, +, *, squared, inverse, zero, one)                               (host)
 //   stem() (the profile-name stem), option(i) (the four tile options' names), TILE_DEFAULT / TILE_MAX / P1_COLS_DEFAULT / P2_COLS_DEFAULT / P2_TOP_DEFAULT,
-//   UPPER_WAVES (the occupancy the upper butterfly passes are bounded to), cold_plan() / cold_pow() (cold-cost labels), LDT_TAG,
-//   CACHE_BYTES (the bound of the plan cache).
-// The C ABI hands arrays over as uint64_t *: they are 8-byte aligned and no more.  Every kernel therefore has two instantiations: A16
-// (128-bit accesses) is launched only when the host has found every pointer of the launch 16-byte aligned, the other one reads and writes an
-// element as 64-bit words.  The profile tells them apart: the 64-bit instantiation reports under the kernel's name with "_w64" appended.
+//   UPPER_WAVES (the occupancy the upper butterfly passes are bounded to), STAGE_BITS (log2 of the elements the block-order staging of
+//   an LDE's coset group may hold), SPLIT_ACCESS (below), cold_plan() / cold_pow() (cold-cost labels), LDT_TAG, CACHE_BYTES (the bound
+//   of the plan cache).
+// The C ABI hands arrays over as uint64_t *: they are 8-byte aligned and no more.  Where an element is wider than that (SPLIT_ACCESS), every
+// kernel has two instantiations: A16 (128-bit accesses) is launched only when the host has found every pointer of the launch 16-byte
+// aligned, the other one reads and writes an element as 64-bit words.  The profile tells them apart: the 64-bit instantiation reports under
+// the kernel's name with "_w64" appended.  A one-word element has the 64-bit instantiation alone, under the plain name.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -25,6 +36,7 @@
 #include <string>
 #include <vector>
 #include "runtime.h"
+#include "subspace_poly.h"
 
 namespace iopx {
 
@@ -53,26 +65,31 @@ static bool al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
 // the profile name of a kernel: the field's stem + the kernel's name (+ "_w64"); built once per name, the pointer stays valid
 template<class F>
-static const char *kernel_name(const char *kernel, bool a16)
+static const char *kernel_name(const char *kernel, bool w64)
 {
     static std::mutex mu;
     static std::map<std::string, std::string> names[2];
     std::lock_guard<std::mutex> lk(mu);
-    std::string &s = names[a16 ? 1 : 0][kernel];
-    if (s.empty()) s = std::string(F::stem()) + kernel + (a16 ? "" : "_w64");
+    std::string &s = names[w64 ? 1 : 0][kernel];
+    if (s.empty()) s = std::string(F::stem()) + kernel + (w64 ? "_w64" : "");
     return s.c_str();
 }
 
-// launch the A16 instantiation when `a16`, the 64-bit one otherwise, under the matching profile name
+// launch the A16 instantiation when `a16`, the 64-bit one otherwise, under the matching profile name; a field without the split has
+// (and names) the 64-bit one only
 #define IOPX_LAUNCHX(a16, name, bytes, K, grid, threads, lds, ...)                                                     \
     do {                                                                                                               \
         const bool a16_ = (a16);                                                                                       \
-        ProfScope ps_(kernel_name<F>(name, a16_), bytes);                                                              \
-        if (a16_) hipLaunchKernelGGL((K<F, true>), grid, threads, lds, stream(), __VA_ARGS__);                         \
-        else hipLaunchKernelGGL((K<F, false>), grid, threads, lds, stream(), __VA_ARGS__);                             \
+        ProfScope ps_(kernel_name<F>(name, F::SPLIT_ACCESS && !a16_), bytes);                                          \
+        if constexpr (F::SPLIT_ACCESS) {                                                                               \
+            if (a16_) hipLaunchKernelGGL((K<F, true>), grid, threads, lds, stream(), __VA_ARGS__);                     \
+            else hipLaunchKernelGGL((K<F, false>), grid, threads, lds, stream(), __VA_ARGS__);                         \
+        } else {                                                                                                       \
+            hipLaunchKernelGGL((K<F, false>), grid, threads, lds, stream(), __VA_ARGS__);                              \
+        }                                                                                                              \
     } while (0)
 
-__device__ __forceinline__ uint32_t bitrev128(uint32_t x, int bits)
+__device__ __forceinline__ uint32_t bitrev_low(uint32_t x, int bits)
 {
     return bits == 0 ? 0u : (__brev(x) >> (32 - bits));
 }
@@ -320,9 +337,9 @@ __device__ __forceinline__ void bfly_edge_body(const BfParamsX &p)
             if (unit >= p.total_units) continue;
             const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
             const int tp = sidx & tmask, lo = (sidx >> p.c_top) & lomask;
-            const int top = (int)bitrev128((uint32_t)tp, p.c_top);
-            const size_t v = ((size_t)bitrev128((uint32_t)lo, p.a_low) << (p.d - p.a_low)) |
-                             ((size_t)bitrev128((uint32_t)mid, midbits) << p.c_top) | (size_t)tp;
+            const int top = (int)bitrev_low((uint32_t)tp, p.c_top);
+            const size_t v = ((size_t)bitrev_low((uint32_t)lo, p.a_low) << (p.d - p.a_low)) |
+                             ((size_t)bitrev_low((uint32_t)mid, midbits) << p.c_top) | (size_t)tp;
             s[((sidx >> tb) << tb) | (top << p.a_low) | lo] = F::template load<A16>(p.src, (coset << p.d) + v);
         }
     }
@@ -353,9 +370,9 @@ __device__ __forceinline__ void bfly_edge_body(const BfParamsX &p)
             if (unit >= p.total_units) continue;
             const size_t coset = unit >> midbits, mid = unit & (((size_t)1 << midbits) - 1);
             const int tp = sidx & tmask, lo = (sidx >> p.c_top) & lomask;
-            const int top = (int)bitrev128((uint32_t)tp, p.c_top);
-            const size_t v = ((size_t)bitrev128((uint32_t)lo, p.a_low) << (p.d - p.a_low)) |
-                             ((size_t)bitrev128((uint32_t)mid, midbits) << p.c_top) | (size_t)tp;
+            const int top = (int)bitrev_low((uint32_t)tp, p.c_top);
+            const size_t v = ((size_t)bitrev_low((uint32_t)lo, p.a_low) << (p.d - p.a_low)) |
+                             ((size_t)bitrev_low((uint32_t)mid, midbits) << p.c_top) | (size_t)tp;
             F::template store<A16>(p.dst, (coset << p.d) + v, s[((sidx >> tb) << tb) | (top << p.a_low) | lo]);
         }
     } else {
@@ -496,28 +513,6 @@ static void push_words(std::vector<uint64_t> &v, const H &x)
     v.insert(v.end(), w, w + W);
 }
 
-// The subspace polynomial of span(basis[0..dim)): prod_{v in span} (X - v), a linearized polynomial (coeff[i] multiplies X^(2^i)), built
-// factor by factor as Z <- Z(X) (Z(X) + Z(b)) (libiop/algebra/polynomials/vanishing_polynomial.tcc:373-395).
-template<class H>
-struct SubspacePolyX {
-    std::vector<H> coeff;
-    SubspacePolyX(const H *basis, size_t dim) : coeff(1, H::one())
-    {
-        for (size_t k = 0; k < dim; ++k) {
-            const H zb = eval(basis[k]);
-            std::vector<H> nxt(coeff.size() + 1, H::zero());
-            for (size_t i = 0; i < coeff.size(); ++i) { nxt[i + 1] += coeff[i].squared(); nxt[i] += coeff[i] * zb; }
-            coeff.swap(nxt);
-        }
-    }
-    H eval(const H &x) const
-    {
-        H r = H::zero(), xp = x;
-        for (size_t i = 0; i < coeff.size(); ++i) { r += coeff[i] * xp; xp = xp.squared(); }
-        return r;
-    }
-};
-
 // ---------------------------------------------------------------------------------------------
 // host: plans
 // ---------------------------------------------------------------------------------------------
@@ -549,7 +544,7 @@ struct AddPlanX {
 
 // Plans are handed out as shared_ptr: a caller keeps its plan alive while another thread's insertion evicts the cache.  A plan of dimension d
 // holds EB * 2^d bytes of twiddles (EB = the element's bytes) and, once a direction has run, 2 EB * 2^d bytes of twist powers for it
-// (5 EB * 2^d bytes with both: 2.5 GiB over gf128 and 5 GiB over gf256 at d = 25); the cache is bounded by F::CACHE_BYTES of such tables
+// (5 EB * 2^d bytes with both: 1.25 GiB over gf64, 2.5 GiB over gf128 and 5 GiB over gf256 at d = 25); the cache is bounded by F::CACHE_BYTES of such tables
 // (and 64 entries), and cleared as a whole when an insertion would pass that.
 template<class F>
 struct PlanCacheX {
@@ -567,7 +562,7 @@ static void clear_plans_x()
     PlanCacheX<F>::plans.clear();
 }
 
-// gf64.hip's schedule64 at this field's tile: the pass structure does not depend on the element's width
+// the passes of both phases for 2^d elements in tiles of 2^tile_bits
 template<class F>
 static void schedule_x(AddPlanX<F> &pl, const TuningX &tu)
 {
@@ -782,8 +777,8 @@ static int run_phase2_fwd_x(AddPlanX<F> &pl, uint64_t *W, uint64_t *out, const u
         IOPX_HIP(hipGetLastError());
         return IOPX_OK;
     }
-    // block-order staging for a group of cosets (the last pass permutes: it cannot run in place), at most 2^24 elements
-    const size_t group = std::min(coset_count, std::max<size_t>(1, ((size_t)1 << 24) >> d));
+    // block-order staging for a group of cosets (the last pass permutes: it cannot run in place), at most 2^STAGE_BITS elements
+    const size_t group = std::min(coset_count, std::max<size_t>(1, ((size_t)1 << F::STAGE_BITS) >> d));
     TmpBuf stage;
     int rc = stage.alloc((group * EB) << d);
     if (rc != IOPX_OK) return rc;
@@ -810,7 +805,7 @@ static int check_basis_args_x(const uint64_t *basis, size_t m, const uint64_t *s
 }
 
 // ---------------------------------------------------------------------------------------------
-// the bodies of the C entries (iopx_*_gf128*, iopx_*_gf256*)
+// the bodies of the C entries (iopx_*_gf64*, iopx_*_gf128*, iopx_*_gf256*)
 // ---------------------------------------------------------------------------------------------
 // Cosets [coset_begin, coset_begin + coset_count) of span(basis[0..d)), d = ceil(log2 n_coeffs): the
 // contiguous output block [coset_begin * 2^d, (coset_begin + coset_count) * 2^d) of the full transform.

@@ -194,9 +194,10 @@ int side_stream_current();
 void clear_mul_plans();           // fft_mul.hip: both prime fields' twiddle caches and power tables
 void clear_dist_plans();           // fft_add_dist.hip: the sharded transforms' per-rank twist tables
 void clear_poseidon_sets();
-void clear_gf64_plans();           // gf64.hip: the GF(2^64) transforms' per-basis plans
-void clear_gf128_plans();          // gf128.hip: the GF(2^128) transforms' per-basis plans
-void clear_gf256_plans();          // gf256.hip: the GF(2^256) transforms' per-basis plans
+// gfx_additive.h's plan cache, one per element trait (clear_plans_x<F>): the transforms' per-basis plans
+void clear_gf64_plans();           // gf64.hip, Elem64
+void clear_gf128_plans();          // gf128.hip, Elem128
+void clear_gf256_plans();          // gf256.hip, Elem256
 
 // comm.hip: the communicator bound for transforms (iopx_comm_bind_transforms), or null; its rank / world; collectives for library-internal
 // use (same semantics as the C entry points)

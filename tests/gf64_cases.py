@@ -198,6 +198,71 @@ def check_schedules(lib):
     assert ran == 2 * len(SCHEDULES)
 
 
+# ---- the single access path ----
+K64_ARM_ROWS = {"k64_build_ltab", "k64_pow_direct", "k64_pad_copy", "k64_fill", "k64_phase1", "k64_phase1_inv", "k64_bfly_upper",
+                "k64_bfly_upper_inv", "k64_bfly_edge", "k64_bfly_edge_inv", "k64_fri_fold", "k64_ldt_combine", "k64_mul", "k64_inv"}
+
+
+def check_placement_and_profile(lib):
+    """2^5 elements under the second geometry of SCHEDULES (three phase-1 launches of which two are the chunks of level 0, one k64_bfly_upper
+    pass, k64_bfly_edge), every device buffer at an address 8 mod 16, the profile on: FFT and IFFT as a round trip, the LDE of the same
+    coefficients onto cosets [1, 3) of the four of a domain of dimension 7 (the staged group), folds with cosets of 2, 4 (one launch each)
+    and 16 (two launches), and an LDT combination of one maximal and two submaximal oracles of one exponent.  Every result equals the
+    oracle's; a one-word element has one access path, so every k64_ row of the profile is one of the arm's plain names and none ends
+    in _w64 wherever the buffers lie."""
+    names = ["IOPX_GF64_TILE_BITS", "IOPX_GF64_P1_COLS", "IOPX_GF64_P2_COLS", "IOPX_GF64_P2_TOP"]
+    m, big = 5, 7
+    n = 1 << m
+    basis, shift, x = std_basis(big), elem((1 << 63) | 0x51), elem(int(seeded("place x", 1)[0, 0]))
+    b5 = basis[:m]
+    coeffs = seeded("place coeffs", n)
+    evals = [seeded("place evals %d" % k, n) for k in range(3)]
+    degrees, coef = [n, n - 3, n - 3], seeded("place coef", 6)
+    raw = [lib.malloc(8 * (2 << m) + 16) for _ in range(4)]
+    at = [p + (8 - p) % 16 for p in raw]
+    assert all(p % 16 == 8 for p in at)
+
+    def read(p, count):
+        out = np.empty((count, 1), dtype=np.uint64)
+        lib.d2h(out, p)
+        return out
+
+    try:
+        for k, v in zip(names, (4, 1, 1, 1)):
+            lib.set_option(k, v)
+        lib.clear_plans()
+        lib.profile_begin()
+        lib.h2d(at[0], coeffs)
+        lib.additive_FFT_gf64_dev(at[0], n, b5, shift, at[3])
+        assert np.array_equal(read(at[3], n), oracle.additive_fft(coeffs, b5, shift))
+        lib.additive_IFFT_gf64_dev(at[3], b5, shift, at[1])
+        assert np.array_equal(read(at[1], n), coeffs)
+        lib.additive_LDE_gf64_dev(at[0], n, basis, shift, 1, 2, at[3])
+        assert np.array_equal(read(at[3], 2 << m), oracle.additive_fft(coeffs, basis, shift)[1 << m:3 << m])
+        lib.h2d(at[0], evals[0])
+        for coset in (2, 4, 16):
+            lib.evaluate_next_f_i_over_entire_domain_gf64_dev(at[0], b5, shift, coset, x, at[3])
+            assert np.array_equal(read(at[3], n // coset), oracle.fri_fold_additive(evals[0], b5, shift, coset, x)), coset
+        for p, e in zip(at, evals):
+            lib.h2d(p, e)
+        lib.ldt_combine_gf64_dev(at[:3], degrees, coef, b5, shift, at[3])
+        assert np.array_equal(read(at[3], n), oracle.ldt_combine_additive(evals, degrees, coef, b5, shift))
+        report = lib.profile_report()
+    finally:
+        for k in names:
+            lib.clear_option(k)
+        lib.clear_plans()
+        for p in raw:
+            lib.free(p)
+    rows = {k: v[0] for k, v in report.items() if k.startswith("k64_")}
+    assert set(rows) <= K64_ARM_ROWS, sorted(set(rows) - K64_ARM_ROWS)
+    assert not [k for k in report if k.endswith("_w64")], sorted(report)
+    # FFT + LDE forward, one IFFT; the LDE's upper pass and last pass take its two cosets in one launch
+    want = {"k64_pad_copy": 2, "k64_phase1": 6, "k64_bfly_upper": 2, "k64_bfly_edge": 2, "k64_bfly_edge_inv": 1, "k64_bfly_upper_inv": 1,
+            "k64_phase1_inv": 3, "k64_fri_fold": 4, "k64_ldt_combine": 1}
+    assert {k: rows.get(k, 0) for k in want} == want, rows
+
+
 # ---- 3. LDE coset ranges ----
 def check_lde_ranges(lib):
     m, d = 12, 7

@@ -522,7 +522,7 @@ def _gf64_other_rows():
         return Case([coeffs], [oracle.additive_fft(coeffs, basis, shift)[5 << d:8 << d]],
                     lambda lib, i, o: lib.additive_LDE_gf64_dev(i[0], coeffs.shape[0], basis, shift, 5, 3, o[0]))
     rows.append(Row("additive_LDE_gf64_dev", "gf64 LDE m=12 d=7 cosets 5..7", build_lde))
-    # the smallest coefficient dimension whose plan has an upper pass (4096-element tiles): 13, with 3 cosets through run_phase2_fwd64's staging
+    # the smallest coefficient dimension whose plan has an upper pass (4096-element tiles): 13, with 3 cosets through run_phase2_fwd_x's staging
     b15, s15 = G64.std_basis(15), G64.elem((1 << 63) | 3)
 
     def build_staged():

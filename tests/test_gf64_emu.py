@@ -20,6 +20,10 @@ def test_fft_schedules():
     C.check_schedules(emu())
 
 
+def test_placement_and_profile():
+    C.check_placement_and_profile(emu())
+
+
 def test_lde_coset_ranges():
     C.check_lde_ranges(emu())
 

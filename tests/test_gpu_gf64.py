@@ -35,6 +35,10 @@ def test_fft_schedules(lib):
     C.check_schedules(lib)
 
 
+def test_placement_and_profile(lib):
+    C.check_placement_and_profile(lib)
+
+
 def test_lde_coset_ranges(lib):
     C.check_lde_ranges(lib)
 

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
-"""Times each GF(2^256) device entry against its GF(2^128) and GF(2^192) twins at the same m, in one process, the three fields alternating:
-the transforms at m = 22 full size, the 2^20 -> 2^25 LDE and the 2^25 IFFT, folds with cosets of 2 and 4 at m = 22, and a 7-oracle LDT
-combination at m = 22 (Aurora-like degree gaps).  Wall time per call from HIP events (torch.cuda.Event on the stream the library uses) after
-warm-up; plans and tables are built during warm-up.  Per case and field: median, min and max over --reps, the launches that ran and their
-algorithmic bytes as counted by the library's own profile of one call (not a copy of the schedule), and those bytes over the median as a
-share of 8 TB/s; the sub-millisecond cases time --calls calls per window.  --kernel-ms adds each kernel's summed time in that one profiled
-call.  The yardstick of a gf256 entry is its gf192 twin in the same run: a gf256 element is 4/3 of the bytes, so
-`gf256_above_four_thirds_of_gf192_beyond_spread` holds when the whole gf256 range lies above 4/3 of the whole gf192 range.
---set NAME=VALUE sets a library option (a tile geometry: IOPX_GF256_TILE_BITS, IOPX_GF256_P1_COLS, IOPX_GF256_P2_COLS, IOPX_GF256_P2_TOP)
-before any plan is built, and --fields / --cases narrow the run, for comparing neighbouring settings, one process per setting.  Kernel-only
-times: run this under `rocprofv3 --kernel-trace --stats -- python tools/gf256_fft_bench.py` in a separate run.
+"""Times each device entry of the additive arm over GF(2^64), GF(2^128), GF(2^192) and GF(2^256) at the same m, in one process, the fields
+alternating: the transforms at m = 22 full size, the 2^20 -> 2^25 LDE and the 2^25 IFFT, folds with cosets of 2 and 4 at m = 22, and a
+7-oracle LDT combination at m = 22 (Aurora-like degree gaps).  Wall time per call from HIP events (torch.cuda.Event on the stream the library
+uses) after warm-up; plans and tables are built during warm-up.  Per case and field: median, min and max over --reps, the launches that ran
+and their algorithmic bytes, in total and by kernel, as counted by the library's own profile of one call (not a copy of the schedule), and the
+total over the median as a share of 8 TB/s; the sub-millisecond cases time --calls calls per window.  --kernel-ms adds each kernel's summed
+time in that one profiled call.  The yardstick of every other field is its gf192 twin in the same run; a comparison holds only when the two
+ranges do not overlap:
+    gf64_faster_beyond_spread                        the whole gf64 range lies below the gf192 range;
+    gf128_below_gf192_beyond_spread                  the whole gf128 range lies below the gf192 range;
+    gf256_above_four_thirds_of_gf192_beyond_spread   a gf256 element is 4/3 of the bytes: the whole gf256 range lies above 4/3 of the whole
+                                                     gf192 range.
+--set NAME=VALUE sets a library option (a tile geometry: IOPX_GF64_TILE_BITS, IOPX_GF128_P1_COLS, IOPX_GF256_P2_COLS, ...) before any plan
+is built, and --fields / --cases narrow the run, for comparing neighbouring settings, one process per setting.  Kernel-only times: run this
+under `rocprofv3 --kernel-trace --stats -- python tools/additive_fft_bench.py` in a separate run.
 
-    python tools/gf256_fft_bench.py [--reps 9] [--set IOPX_GF256_TILE_BITS=11] [--fields gf256] [--cases fft_2^22,ifft_2^22]
+    python tools/additive_fft_bench.py [--reps 9] [--set IOPX_GF128_TILE_BITS=10] [--fields gf64,gf192] [--cases fft_2^22,ifft_2^22]
 """
 import argparse
 import json
@@ -26,17 +30,20 @@ sys.path.insert(0, ROOT)
 
 import libiop_amd  # noqa: E402
 
-WORDS = {"gf128": 2, "gf192": 3, "gf256": 4}
-PREFIX = {"gf128": "k128_", "gf192": "k_", "gf256": "k256_"}
+WORDS = {"gf64": 1, "gf128": 2, "gf192": 3, "gf256": 4}
+PREFIX = {"gf64": "k64_", "gf128": "k128_", "gf192": "k_", "gf256": "k256_"}
+# the binding's method per entry: gf64 has methods of its own, gf128 and gf256 are the gf192 method with words=2 and words=4
+GF64_METHOD = {"additive_FFT_dev": "additive_FFT_gf64_dev", "additive_IFFT_dev": "additive_IFFT_gf64_dev", "additive_LDE_dev": "additive_LDE_gf64_dev",
+               "fri_fold_dev": "evaluate_next_f_i_over_entire_domain_gf64_dev", "ldt_combine_dev": "ldt_combine_gf64_dev"}
 
 
 def launches_and_bytes(lib, fn, f):
-    """One profiled call: (launches by kernel, their algorithmic bytes) as the library's own ProfScope counters report them — the schedule that
+    """One profiled call: (launches, algorithmic bytes, ms) by kernel as the library's own ProfScope counters report them — the schedule that
     actually ran, whatever the tile options are (the padding copy and the table reads are not in the byte count)."""
     lib.profile_begin()
     fn(f)
     rep = {k: v for k, v in lib.profile_report().items() if k.startswith(PREFIX[f])}
-    return {k: v[0] for k, v in rep.items()}, sum(v[2] for v in rep.values()), {k: round(v[1], 4) for k, v in rep.items()}
+    return {k: v[0] for k, v in rep.items()}, {k: int(v[2]) for k, v in rep.items()}, {k: round(v[1], 4) for k, v in rep.items()}
 
 
 def main():
@@ -45,10 +52,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--calls", type=int, default=8, help="calls per timed window for the sub-millisecond cases (folds, LDT combination)")
     ap.add_argument("--set", action="append", default=[], metavar="NAME=VALUE", help="a library option, set before any plan is built")
-    ap.add_argument("--fields", default="gf128,gf192,gf256")
+    ap.add_argument("--fields", default="gf64,gf128,gf192,gf256")
     ap.add_argument("--cases", default="")
     ap.add_argument("--kernel-ms", action="store_true", help="also print each kernel's summed time in the one profiled call (HIP events around every launch)")
     args = ap.parse_args()
+    unknown = [f for f in args.fields.split(",") if f not in WORDS]
+    if unknown:
+        ap.error("unknown field(s) %s: any of %s" % (",".join(unknown), ",".join(WORDS)))
     import torch
     lib = libiop_amd.lib()
     lib.init(0)
@@ -76,7 +86,8 @@ def main():
     coef = {f: rng.integers(0, 1 << 63, size=(14, WORDS[f]), dtype=np.uint64) for f in fields}
 
     def call(f, name):
-        """gf128 and gf256 are the gf192 method with words=2 and words=4"""
+        if f == "gf64":
+            return getattr(lib, GF64_METHOD[name])
         method = getattr(lib, name)
         return method if f == "gf192" else (lambda *a: method(*a, words=WORDS[f]))
 
@@ -127,18 +138,24 @@ def main():
         row = {"case": k, "calls_per_window": calls, "options": args.set}
         for f in fields:
             t = sorted(times[(k, f)])
-            launches, nbytes, kernel_ms = sched[(k, f)]
+            launches, kernel_bytes, kernel_ms = sched[(k, f)]
+            nbytes = sum(kernel_bytes.values())
             med = statistics.median(t)
-            row[f] = {"median_ms": round(med, 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4), "launches": launches, "bytes": int(nbytes),
-                      "hbm_share_of_8TBps": round(nbytes / (med * 1e-3) / 8e12, 3)}
+            row[f] = {"median_ms": round(med, 4), "min_ms": round(t[0], 4), "max_ms": round(t[-1], 4), "launches": launches, "bytes": nbytes,
+                      "kernel_bytes": kernel_bytes, "hbm_share_of_8TBps": round(nbytes / (med * 1e-3) / 8e12, 3)}
             if args.kernel_ms:
                 row[f]["kernel_ms"] = kernel_ms
-        if "gf256" in row and "gf192" in row:
-            row["ratio_gf256_over_gf192"] = round(row["gf256"]["median_ms"] / row["gf192"]["median_ms"], 3)
-            # the comparison holds only when the two ranges do not overlap
-            row["gf256_above_four_thirds_of_gf192_beyond_spread"] = row["gf256"]["min_ms"] > 4.0 / 3.0 * row["gf192"]["max_ms"]
-        if "gf128" in row and "gf192" in row:
-            row["ratio_gf128_over_gf192"] = round(row["gf128"]["median_ms"] / row["gf192"]["median_ms"], 3)
+        if "gf192" in row:
+            for f in fields:
+                if f != "gf192":
+                    row["ratio_%s_over_gf192" % f] = round(row[f]["median_ms"] / row["gf192"]["median_ms"], 3)
+            # each comparison holds only when the two ranges do not overlap
+            if "gf64" in row:
+                row["gf64_faster_beyond_spread"] = row["gf64"]["max_ms"] < row["gf192"]["min_ms"]
+            if "gf128" in row:
+                row["gf128_below_gf192_beyond_spread"] = row["gf128"]["max_ms"] < row["gf192"]["min_ms"]
+            if "gf256" in row:
+                row["gf256_above_four_thirds_of_gf192_beyond_spread"] = row["gf256"]["min_ms"] > 4.0 / 3.0 * row["gf192"]["max_ms"]
         print(json.dumps(row), flush=True)
     lib.use_own_stream()
 

@@ -320,7 +320,7 @@ int iopx_poly_div_vanishing_gf64_dev(const uint64_t *d_poly, size_t n_coeffs, co
  * argument checks and cites the same reference lines.  Element arrays need only the 8-byte alignment of uint64_t: a launch whose
  * pointers are all 16-byte aligned moves an element in one 128-bit access, any other launch in two 64-bit ones (the profile reports
  * the latter under the kernel's name + "_w64").  Merkle trees, query responses, membership proofs and the proof of work take
- * elem_bytes = 16.  The protocol-layer kernels (Aurora, Fractal) are not built over gf128: only the FRI-only SNARK runs over it. */
+ * elem_bytes = 16.  The FRI-only SNARK and Aurora run over gf128; Fractal does not. */
 int iopx_add_fft_gf128_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                            const uint64_t *shift, uint64_t *d_out);
 int iopx_add_fft_gf128(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
@@ -354,7 +354,7 @@ int iopx_gf128_inverse_host(const uint64_t *x, uint64_t *out);
  * argument checks and cites the same reference lines.  Element arrays need only the 8-byte alignment of uint64_t: a launch whose
  * pointers are all 16-byte aligned moves an element in two 128-bit accesses, any other launch in four 64-bit ones (the profile reports
  * the latter under the kernel's name + "_w64").  Merkle trees, query responses, membership proofs and the proof of work take
- * elem_bytes = 32.  The protocol-layer kernels (Aurora, Fractal) are not built over gf256: only the FRI-only SNARK runs over it. */
+ * elem_bytes = 32.  The FRI-only SNARK and Aurora run over gf256; Fractal does not. */
 int iopx_add_fft_gf256_dev(const uint64_t *d_coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                            const uint64_t *shift, uint64_t *d_out);
 int iopx_add_fft_gf256(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
@@ -381,6 +381,12 @@ int iopx_gf256_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
 int iopx_gf256_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_gf256_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 int iopx_gf256_inverse_host(const uint64_t *x, uint64_t *out);
+
+/* ---- GF(2^128), GF(2^256): the protocol-layer steps of the encoded Aurora prover ------------------ */
+/* iopx_{rowcheck,fz,sumcheck_g,lincheck,lincomb,lincomb_affine,spmv,poly_div_vanishing}_gf128_dev and iopx_gf128_pow_table_dev, and their gf256
+ * twins: the gf64 entries of those names above at two and four words per element.  They are declared once for both fields, from one
+ * parameterised text, in libiop_amd_gfx.h (beside this file), as the kernels behind them are written once (libiop_amd/csrc/gfx_ops.h). */
+#include "libiop_amd_gfx.h"
 
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
@@ -745,10 +751,13 @@ int iopx_fp3_modulus(uint64_t *out);
  * transform entries — which is checked from the parameters before any device work. */
 #define IOPX_FIELD_GF64 4
 #define IOPX_GF64_MAX_DOMAIN_DIM 40
-/* libff::gf128: the FRI-only SNARK (iopx_fri_snark_prove, iopx_fri_snark_prove_hashed with IOPX_HASH_BLAKE2B) on one GPU, coefficients 2 words
- * per element.  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, and an Aurora instance
- * (iopx_aurora_instance_create, iopx_aurora_example_instance_create): the protocol-layer kernels are not built over gf128. */
+/* libff::gf128: Aurora instances from CSR matrices (iopx_aurora_instance_create; iopx_aurora_prove, iopx_aurora_prove_hashed with IOPX_HASH_BLAKE2B,
+ * iopx_aurora_instance_warm) and the FRI-only SNARK on one GPU, 2 words per element, in the reference's schedule (no head evaluation, no fused
+ * re-extension).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, iopx_fractal_index /
+ * iopx_fractal_prove, a codeword domain of more than 2^IOPX_GFX_MAX_DOMAIN_DIM points (checked from the parameters before any device work), and
+ * iopx_aurora_example_instance_create (the synthetic instance is not generated over this field: build it as CSR matrices plus an assignment). */
 #define IOPX_FIELD_GF128 5
+#define IOPX_GFX_MAX_DOMAIN_DIM 40
 /* libff::gf256: as gf128, coefficients 4 words per element; the refusals name gf256. */
 #define IOPX_FIELD_GF256 6
 /* bcs_hash_type (libiop/bcs/hashing/hash_enum.hpp:21-26), as iopx_poseidon_shipped_params takes it */

@@ -85,6 +85,12 @@ EXPORTED_SYMBOLS = [
     "iopx_mem_check_stats",
 ]
 
+# the declarations of include/libiop_amd_gfx.h (which libiop_amd.h includes): the protocol-layer entries of Aurora over gf128 and gf256, one
+# parameterised text for both fields
+GFX_OPS_SYMBOLS = [pattern % field for field in ("gf128", "gf256")
+                   for pattern in ("iopx_%s_pow_table_dev", "iopx_lincomb_%s_dev", "iopx_lincomb_affine_%s_dev", "iopx_spmv_%s_dev", "iopx_lincheck_%s_dev",
+                                   "iopx_rowcheck_%s_dev", "iopx_fz_%s_dev", "iopx_sumcheck_g_%s_dev", "iopx_poly_div_vanishing_%s_dev")]
+
 
 class NoDeviceError(RuntimeError):
     pass
@@ -135,8 +141,8 @@ def _ints_to_words4(values):
 
 FIELD_GF192, FIELD_EDWARDS_FR, FIELD_ALT_BN128_FR = 0, 1, 2                 # IOPX_FIELD_*
 FIELD_GF64 = 4                                                              # libff::gf64 (3 stays unknown to the C ABI)
-FIELD_GF128 = 5                                                             # libff::gf128: the FRI-only SNARK
-FIELD_GF256 = 6                                                             # libff::gf256: the FRI-only SNARK
+FIELD_GF128 = 5                                                             # libff::gf128: the FRI-only SNARK and Aurora
+FIELD_GF256 = 6                                                             # libff::gf256: the FRI-only SNARK and Aurora
 HASH_BLAKE2B, HASH_POSEIDON_STARKWARE, HASH_POSEIDON_HIGH_ALPHA = 1, 2, 3   # IOPX_HASH_*: the reference's bcs_hash_type
 
 
@@ -310,7 +316,9 @@ class Library:
             getattr(c, name).argtypes = list(getattr(c, twin).argtypes)
         # GF(2^128), GF(2^256): the prototypes of the gf64 entries, two and four words per element
         for name in ("add_fft_%s_dev", "add_fft_%s", "add_lde_%s_dev", "add_ifft_%s_dev", "add_ifft_%s", "fri_fold_add_%s_dev", "fri_fold_add_%s",
-                     "fri_domains_%s", "ldt_combine_%s_dev", "%s_mul_dev", "%s_inv_dev", "%s_add_dev", "%s_host_mul", "%s_inverse_host"):
+                     "fri_domains_%s", "ldt_combine_%s_dev", "%s_mul_dev", "%s_inv_dev", "%s_add_dev", "%s_host_mul", "%s_inverse_host",
+                     "%s_pow_table_dev", "lincomb_%s_dev", "lincomb_affine_%s_dev", "spmv_%s_dev", "lincheck_%s_dev", "rowcheck_%s_dev", "fz_%s_dev",
+                     "sumcheck_g_%s_dev", "poly_div_vanishing_%s_dev"):
             getattr(c, "iopx_" + name % "gf128").argtypes = list(getattr(c, "iopx_" + name % "gf64").argtypes)
             getattr(c, "iopx_" + name % "gf256").argtypes = list(getattr(c, "iopx_" + name % "gf64").argtypes)
 
@@ -739,9 +747,9 @@ class Library:
 
     # ---- R1CS row check (rowcheck.tcc:16-88) ----
     def rowcheck_dev(self, d_az, d_bz, d_cz, basis, shift, constraint_dim, constraint_shift, d_out, words=3):
-        """words: 3 over gf192, 1 over gf64 (iopx_rowcheck_gf64_dev) — here and in the other subspace-shaped and vector methods that take it"""
+        """words: 3 over gf192, 1 over gf64 (iopx_rowcheck_gf64_dev), 2 over gf128, 4 over gf256 — here and in the other subspace-shaped and vector methods that take it"""
         basis, shift, cs = _as_u64(basis, words), _as_u64(shift, words), _as_u64(constraint_shift, words)
-        fn = self.c.iopx_rowcheck_gf64_dev if words == 1 else self.c.iopx_rowcheck_gf192_dev
+        fn = self.c.iopx_rowcheck_gf64_dev if words == 1 else self.c.iopx_rowcheck_gf128_dev if words == 2 else self.c.iopx_rowcheck_gf256_dev if words == 4 else self.c.iopx_rowcheck_gf192_dev
         self._check(fn(_vp(d_az), _vp(d_bz), _vp(d_cz), basis.ctypes.data_as(_u64p), basis.shape[0],
                                                    shift.ctypes.data_as(_u64p), int(constraint_dim), cs.ctypes.data_as(_u64p), _vp(d_out)))
 
@@ -762,7 +770,7 @@ class Library:
     def fz_dev(self, d_fw, d_f1v, basis, shift, input_basis, input_shift, d_out, words=3):
         basis, shift, ish = _as_u64(basis, words), _as_u64(shift, words), _as_u64(input_shift, words)
         ib = np.ascontiguousarray(input_basis, dtype=np.uint64).reshape(-1, words)
-        fn = self.c.iopx_fz_gf64_dev if words == 1 else self.c.iopx_fz_gf192_dev
+        fn = self.c.iopx_fz_gf64_dev if words == 1 else self.c.iopx_fz_gf128_dev if words == 2 else self.c.iopx_fz_gf256_dev if words == 4 else self.c.iopx_fz_gf192_dev
         self._check(fn(_vp(d_fw), _vp(d_f1v), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
                                              ib.ctypes.data_as(_u64p), ib.shape[0], ish.ctypes.data_as(_u64p), _vp(d_out)))
 
@@ -781,7 +789,7 @@ class Library:
     def sumcheck_g_dev(self, d_f, d_h, basis, shift, summation_basis, summation_shift, claimed_sum, d_out, words=3):
         basis, shift, ssh, mu = _as_u64(basis, words), _as_u64(shift, words), _as_u64(summation_shift, words), _as_u64(claimed_sum, words)
         sb = np.ascontiguousarray(summation_basis, dtype=np.uint64).reshape(-1, words)
-        fn = self.c.iopx_sumcheck_g_gf64_dev if words == 1 else self.c.iopx_sumcheck_g_gf192_dev
+        fn = self.c.iopx_sumcheck_g_gf64_dev if words == 1 else self.c.iopx_sumcheck_g_gf128_dev if words == 2 else self.c.iopx_sumcheck_g_gf256_dev if words == 4 else self.c.iopx_sumcheck_g_gf192_dev
         self._check(fn(_vp(d_f), _vp(d_h), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
                                                      sb.ctypes.data_as(_u64p), sb.shape[0], ssh.ctypes.data_as(_u64p), mu.ctypes.data_as(_u64p), _vp(d_out)))
 
@@ -803,7 +811,7 @@ class Library:
         if r.shape[0] != len(d_mz):
             raise ValueError("Not enough random linear combination coefficients were provided")
         ptrs = (_vp * len(d_mz))(*d_mz)
-        fn = self.c.iopx_lincheck_gf64_dev if words == 1 else self.c.iopx_lincheck_fp3_dev if prime_field else self.c.iopx_lincheck_gf192_dev
+        fn = self.c.iopx_lincheck_gf64_dev if words == 1 else self.c.iopx_lincheck_fp3_dev if prime_field else self.c.iopx_lincheck_gf128_dev if words == 2 else self.c.iopx_lincheck_gf256_dev if words == 4 else self.c.iopx_lincheck_gf192_dev
         self._check(fn(_vp(d_fz), ptrs, len(d_mz), r.ctypes.data_as(_u64p), _vp(d_p1), _vp(d_p2), int(n), _vp(d_out)))
 
     def lincheck(self, fz, mz, r_mz, p1, p2, prime_field=False):
@@ -912,9 +920,9 @@ class Library:
     def aurora_instance(self, field_code, matrices, num_variables, num_inputs, assignment):
         """iopx_aurora_instance_create: an instance from the caller's own constraint system and variable assignment.  matrices = three
         (row_ptr, col, coeff) triples in CSR form (A, B, C; coeff: (entries, 3) uint64 words; column 0 is the constant 1), assignment =
-        (num_variables, 3) words, primary inputs first; four words per element over FIELD_ALT_BN128_FR (2), one over FIELD_GF64 (4).  Release with
+        (num_variables, 3) words, primary inputs first; four words per element over FIELD_ALT_BN128_FR (2) and FIELD_GF256 (6), one over FIELD_GF64 (4), two over FIELD_GF128 (5).  Release with
         aurora_instance_free."""
-        words = {FIELD_ALT_BN128_FR: 4, FIELD_GF64: 1}.get(int(field_code), 3)
+        words = {FIELD_ALT_BN128_FR: 4, FIELD_GF64: 1, FIELD_GF128: 2, FIELD_GF256: 4}.get(int(field_code), 3)
         class _R1CS(ctypes.Structure):
             _fields_ = [("num_constraints", _sz), ("num_variables", _sz), ("num_inputs", _sz), ("row_ptr", _u64p * 3),
                         ("col", ctypes.POINTER(ctypes.c_uint32) * 3), ("coeff", _u64p * 3)]
@@ -1278,7 +1286,7 @@ class Library:
 
     def pow_table_dev(self, d_out, count, base, init, words=3):
         base, init = _as_u64(base, words), _as_u64(init, words)
-        fn = self.c.iopx_gf64_pow_table_dev if words == 1 else self.c.iopx_gf192_pow_table_dev
+        fn = self.c.iopx_gf64_pow_table_dev if words == 1 else self.c.iopx_gf128_pow_table_dev if words == 2 else self.c.iopx_gf256_pow_table_dev if words == 4 else self.c.iopx_gf192_pow_table_dev
         self._check(fn(_vp(d_out), count, base.ctypes.data_as(_u64p), init.ctypes.data_as(_u64p)))
 
     def combine_dev(self, d_a, d_b, d_out, count, index_base, basis, shift_term, upper):
@@ -1315,14 +1323,14 @@ class Library:
     def spmv_dev(self, d_row_ptr, d_col, d_coeff, rows, d_vec, d_out, scale=None, accumulate=False, prime_field=False, words=3):
         """out[r] (+)= scale * sum_t coeff[t] * vec[col[t]] over CSR rows (r1cs.tcc:236-268; basic_lincheck_aux.tcc:64-88)."""
         sc = _as_u64(scale, words).ctypes.data_as(_u64p) if scale is not None else None
-        fn = self.c.iopx_spmv_gf64_dev if words == 1 else self.c.iopx_spmv_fp3_dev if prime_field else self.c.iopx_spmv_gf192_dev
+        fn = self.c.iopx_spmv_gf64_dev if words == 1 else self.c.iopx_spmv_fp3_dev if prime_field else self.c.iopx_spmv_gf128_dev if words == 2 else self.c.iopx_spmv_gf256_dev if words == 4 else self.c.iopx_spmv_gf192_dev
         self._check(fn(_vp(d_row_ptr), _vp(d_col), _vp(d_coeff), int(rows), _vp(d_vec), sc, int(bool(accumulate)), _vp(d_out)))
 
     def poly_div_vanishing_dev(self, d_poly, n_coeffs, basis, shift, d_quotient, words=3):
         """Quotient by the vanishing polynomial of the affine subspace (basis, shift): n_coeffs - 2^dim coefficients."""
         shift = _as_u64(shift, words)
         b = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, words)
-        fn = self.c.iopx_poly_div_vanishing_gf64_dev if words == 1 else self.c.iopx_poly_div_vanishing_gf192_dev
+        fn = self.c.iopx_poly_div_vanishing_gf64_dev if words == 1 else self.c.iopx_poly_div_vanishing_gf128_dev if words == 2 else self.c.iopx_poly_div_vanishing_gf256_dev if words == 4 else self.c.iopx_poly_div_vanishing_gf192_dev
         self._check(fn(_vp(d_poly), int(n_coeffs), b.ctypes.data_as(_u64p), b.shape[0],
                                                              shift.ctypes.data_as(_u64p), _vp(d_quotient)))
 
@@ -1336,7 +1344,7 @@ class Library:
         if co.shape[0] != len(d_oracles):
             raise ValueError("Random Linear Combination Oracle: Expected same number of random coefficients as oracles.")
         ptrs = (_vp * len(d_oracles))(*d_oracles)
-        fn = self.c.iopx_lincomb_gf64_dev if words == 1 else self.c.iopx_lincomb_fp3_dev if prime_field else self.c.iopx_lincomb_gf192_dev
+        fn = self.c.iopx_lincomb_gf64_dev if words == 1 else self.c.iopx_lincomb_fp3_dev if prime_field else self.c.iopx_lincomb_gf128_dev if words == 2 else self.c.iopx_lincomb_gf256_dev if words == 4 else self.c.iopx_lincomb_gf192_dev
         self._check(fn(ptrs, len(d_oracles), co.ctypes.data_as(_u64p), int(n), _vp(d_out)))
 
     def lincomb_affine_dev(self, d_oracles, coefficients, constant, n, d_out, prime_field=False, words=3):
@@ -1345,7 +1353,7 @@ class Library:
         if co.shape[0] != len(d_oracles):
             raise ValueError("Expected same number of coefficients as oracles.")
         ptrs = (_vp * len(d_oracles))(*d_oracles)
-        fn = self.c.iopx_lincomb_affine_gf64_dev if words == 1 else self.c.iopx_lincomb_affine_fp3_dev if prime_field else self.c.iopx_lincomb_affine_gf192_dev
+        fn = self.c.iopx_lincomb_affine_gf64_dev if words == 1 else self.c.iopx_lincomb_affine_fp3_dev if prime_field else self.c.iopx_lincomb_affine_gf128_dev if words == 2 else self.c.iopx_lincomb_affine_gf256_dev if words == 4 else self.c.iopx_lincomb_affine_gf192_dev
         self._check(fn(ptrs, len(d_oracles), co.ctypes.data_as(_u64p), c0.ctypes.data_as(_u64p), int(n), _vp(d_out)))
 
     def field_div_dev(self, d_num, d_den, d_out, count, prime_field=False):

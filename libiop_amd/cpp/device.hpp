@@ -56,7 +56,7 @@ struct field_host {
     static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
-            if (WORDS == 1) ops::missing("vanishing_eval", table::vec->name);               // gf64: no host form of Z_S (only the head route and Fractal ask)
+            if (WORDS != 3) ops::missing("vanishing_eval", table::vec->name);               // gf64, gf128, gf256: no host form of Z_S (only the head route and Fractal ask)
             uint64_t w[WORDS];
             const FieldT shift = S.shift();
             check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), w, nullptr));
@@ -68,7 +68,7 @@ struct field_host {
     static FieldT vanishing_derivative(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
-            if (WORDS == 1) ops::missing("vanishing_derivative", table::vec->name);
+            if (WORDS != 3) ops::missing("vanishing_derivative", table::vec->name);
             uint64_t w[WORDS];
             const FieldT shift = S.shift();
             check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), nullptr, w));

@@ -58,19 +58,19 @@ inline constexpr vector_ops gf64 = {
     iopx_gf64_add_dev, iopx_gf64_mul_dev, iopx_gf64_inv_dev, nullptr, iopx_gf64_pow_table_dev,
     iopx_lincomb_gf64_dev, iopx_lincomb_affine_gf64_dev, iopx_lincheck_gf64_dev, iopx_spmv_gf64_dev, nullptr,
 };
-// libff::gf128: the vector helpers of csrc/gf128.hip; the protocol-layer entries are not built over it (the FRI-only SNARK needs none)
+// libff::gf128: the vector helpers of csrc/gf128.hip and the Aurora prover's entries (csrc/gf128_ops.hip); as gf64, nothing that only Fractal calls
 inline constexpr vector_ops gf128 = {
     "gf128", 128, false,
     iopx_gf128_host_mul, iopx_gf128_inverse_host,
-    iopx_gf128_add_dev, iopx_gf128_mul_dev, iopx_gf128_inv_dev, nullptr, nullptr,
-    nullptr, nullptr, nullptr, nullptr, nullptr,
+    iopx_gf128_add_dev, iopx_gf128_mul_dev, iopx_gf128_inv_dev, nullptr, iopx_gf128_pow_table_dev,
+    iopx_lincomb_gf128_dev, iopx_lincomb_affine_gf128_dev, iopx_lincheck_gf128_dev, iopx_spmv_gf128_dev, nullptr,
 };
-// libff::gf256: the vector helpers of csrc/gf256.hip; as gf128, no protocol-layer entries
+// libff::gf256: the vector helpers of csrc/gf256.hip and the Aurora prover's entries (csrc/gf256_ops.hip); as gf128
 inline constexpr vector_ops gf256 = {
     "gf256", 256, false,
     iopx_gf256_host_mul, iopx_gf256_inverse_host,
-    iopx_gf256_add_dev, iopx_gf256_mul_dev, iopx_gf256_inv_dev, nullptr, nullptr,
-    nullptr, nullptr, nullptr, nullptr, nullptr,
+    iopx_gf256_add_dev, iopx_gf256_mul_dev, iopx_gf256_inv_dev, nullptr, iopx_gf256_pow_table_dev,
+    iopx_lincomb_gf256_dev, iopx_lincomb_affine_gf256_dev, iopx_lincheck_gf256_dev, iopx_spmv_gf256_dev, nullptr,
 };
 inline constexpr subspace_ops gf192_subspace = {
     iopx_add_fft_gf192_dev, iopx_add_lde_gf192_dev, iopx_add_ifft_gf192_dev,
@@ -89,15 +89,15 @@ inline constexpr subspace_ops gf64_subspace = {
 inline constexpr subspace_ops gf128_subspace = {
     iopx_add_fft_gf128_dev, iopx_add_lde_gf128_dev, iopx_add_ifft_gf128_dev,
     iopx_fri_fold_add_gf128_dev, iopx_fri_domains_gf128, iopx_ldt_combine_gf128_dev,
-    nullptr, nullptr, nullptr,
-    nullptr, nullptr,
+    iopx_rowcheck_gf128_dev, iopx_fz_gf128_dev, iopx_sumcheck_g_gf128_dev,
+    iopx_poly_div_vanishing_gf128_dev, nullptr,
     nullptr, nullptr,
 };
 inline constexpr subspace_ops gf256_subspace = {
     iopx_add_fft_gf256_dev, iopx_add_lde_gf256_dev, iopx_add_ifft_gf256_dev,
     iopx_fri_fold_add_gf256_dev, iopx_fri_domains_gf256, iopx_ldt_combine_gf256_dev,
-    nullptr, nullptr, nullptr,
-    nullptr, nullptr,
+    iopx_rowcheck_gf256_dev, iopx_fz_gf256_dev, iopx_sumcheck_g_gf256_dev,
+    iopx_poly_div_vanishing_gf256_dev, nullptr,
     nullptr, nullptr,
 };
 inline constexpr prime_field_ops edwards_Fr = {

@@ -145,7 +145,7 @@ public:
 // the host: the permutation is the library's host one over the same parameter tables as the device kernels.  FieldT: alt_bn128 Fr's layout.
 template<typename FieldT>
 class algebraic_hashchain {
-    static_assert(sizeof(FieldT) == 32, "the Poseidon hashchain runs over alt_bn128 Fr");
+    static_assert(detail::bn128_layout<FieldT>(), "the Poseidon hashchain runs over alt_bn128 Fr");      // 32 bytes are gf256 too: the kind tells them apart
     iopx_poseidon_params params_;
     std::vector<FieldT> state_;
     std::size_t rate_, next_unsqueezed_elem_ = 0;
@@ -289,9 +289,9 @@ struct poseidon {
     explicit poseidon(int type = IOPX_HASH_POSEIDON_STARKWARE) : bcs_hash_type(type) {}
     template<typename FieldT> std::shared_ptr<bcs_hash_family<FieldT>> family() const
     {
-        if (sizeof(FieldT) != 32) throw std::invalid_argument("Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
+        if (!detail::bn128_layout<FieldT>()) throw std::invalid_argument("Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
         if (bcs_hash_type != IOPX_HASH_POSEIDON_STARKWARE && bcs_hash_type != IOPX_HASH_POSEIDON_HIGH_ALPHA) throw std::invalid_argument("Not a poseidon hash type");
-        return make<FieldT>(std::integral_constant<bool, sizeof(FieldT) == 32>());
+        return make<FieldT>(std::integral_constant<bool, detail::bn128_layout<FieldT>()>());
     }
 private:
     template<typename FieldT> std::shared_ptr<bcs_hash_family<FieldT>> make(std::true_type) const { return std::make_shared<poseidon_family<FieldT>>(bcs_hash_type); }
@@ -321,7 +321,7 @@ public:
         for (auto &o : oracles) ptrs.push_back(o.data());
         const int type = domain.type() == affine_subspace_type ? IOPX_DOMAIN_ADDITIVE : IOPX_DOMAIN_MULTIPLICATIVE;
         if (poseidon) {
-            if (distributed_ || sizeof(FieldT) != 32) throw std::invalid_argument("Poseidon trees: alt_bn128 Fr on one GPU");
+            if (distributed_ || !detail::bn128_layout<FieldT>()) throw std::invalid_argument("Poseidon trees: alt_bn128 Fr on one GPU");
             num_leaves_ = global_leaves_;
             nodes_ = device_array<uint8_t>((2 * num_leaves_ - 1) * 32);
             check(iopx_merkle_poseidon_bn128_dev(poseidon, ptrs.data(), ptrs.size(), domain.num_elements(), coset_size, type, nullptr, reinterpret_cast<uint64_t *>(nodes_.data())));

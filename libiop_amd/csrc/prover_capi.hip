@@ -57,18 +57,25 @@ struct Instance : InstanceBase {
     iopx_comm *index_comm = nullptr;        // the index holds this rank's part of the twelve index oracles: it belongs to one communicator
 
     size_t num_constraints() const override { return cs.num_constraints(); }
-    static constexpr bool bn128 = sizeof(F) == 32;                // alt_bn128 Fr: Aurora only, on one GPU
-    static constexpr bool gf64 = sizeof(F) == 8;                  // gf64: Aurora only, on one GPU, BLAKE2b
+    static constexpr bool binary = field_kind<F>::type == affine_subspace_type;      // 32 bytes are alt_bn128 Fr or gf256: the kind tells them apart
+    static constexpr bool bn128 = !binary && sizeof(F) == 32;     // alt_bn128 Fr: Aurora only, on one GPU
+    static constexpr bool gf64 = binary && sizeof(F) == 8;        // gf64: Aurora only, on one GPU, BLAKE2b
+    static constexpr bool gf128 = binary && sizeof(F) == 16;      // gf128, gf256: as gf64
+    static constexpr bool gf256 = binary && sizeof(F) == 32;
+    static constexpr bool gfx = gf128 || gf256;
+    static const char *gfx_name() { return gf128 ? "gf128" : "gf256"; }
     std::vector<std::string> fractal_index(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
         if constexpr (bn128) throw std::invalid_argument("iopx_fractal_index: there is no Fractal prover over alt_bn128 Fr");
         else if constexpr (gf64) throw std::invalid_argument("iopx_fractal_index: there is no Fractal prover over gf64");
+        else if constexpr (gfx) throw std::invalid_argument(std::string("iopx_fractal_index: there is no Fractal prover over ") + gfx_name());
         else return fractal_index_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
     }
     std::string fractal_prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
         if constexpr (bn128) throw std::invalid_argument("iopx_fractal_prove: there is no Fractal prover over alt_bn128 Fr");
         else if constexpr (gf64) throw std::invalid_argument("iopx_fractal_prove: there is no Fractal prover over gf64");
+        else if constexpr (gfx) throw std::invalid_argument(std::string("iopx_fractal_prove: there is no Fractal prover over ") + gfx_name());
         else return fractal_prove_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
     }
     std::vector<std::string> fractal_index_(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter)
@@ -99,9 +106,12 @@ struct Instance : InstanceBase {
         if (bcs_hash_type != IOPX_HASH_BLAKE2B && bcs_hash_type != IOPX_HASH_POSEIDON_STARKWARE && bcs_hash_type != IOPX_HASH_POSEIDON_HIGH_ALPHA)
             throw std::invalid_argument("bcs_hash_type unknown");
         if (bcs_hash_type != IOPX_HASH_BLAKE2B && gf64) throw std::invalid_argument("gf64 proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
+        if (bcs_hash_type != IOPX_HASH_BLAKE2B && gfx)
+            throw std::invalid_argument(std::string(gfx_name()) + " proves with BLAKE2b: Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
         if (bcs_hash_type != IOPX_HASH_BLAKE2B && !bn128) throw std::invalid_argument("Poseidon is wired for alt_bn128 Fr only (hash_enum.tcc:12-24)");
         if (bn128 && comm) throw std::invalid_argument("alt_bn128 Fr has no distributed prover: pass no communicator");
         if (gf64 && comm) throw std::invalid_argument("gf64 has no distributed prover: pass no communicator");
+        if (gfx && comm) throw std::invalid_argument(std::string(gfx_name()) + " has no distributed prover: pass no communicator");
         require_supported_security(security_parameter);
         const dist::scope bound(comm);
         const aurora_snark_parameters<F> params(cs.num_constraints(), cs.num_variables(), cs.num_inputs(), security_parameter, RS_extra_dimensions,
@@ -111,6 +121,9 @@ struct Instance : InstanceBase {
         if (gf64 && params.codeword_domain_dim_ > IOPX_GF64_MAX_DOMAIN_DIM)            // before any device work
             throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": the gf64 transforms take domains of dimension up to " +
                                         std::to_string(IOPX_GF64_MAX_DOMAIN_DIM));
+        if (gfx && params.codeword_domain_dim_ > IOPX_GFX_MAX_DOMAIN_DIM)              // before any device work
+            throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": the " + gfx_name() +
+                                        " transforms take domains of dimension up to " + std::to_string(IOPX_GFX_MAX_DOMAIN_DIM));
         if constexpr (bn128) {
             if (bcs_hash_type != IOPX_HASH_BLAKE2B) return aurora_snark_prover_serialized<F, poseidon>(cs, primary, auxiliary, params, &d_assignment, poseidon(bcs_hash_type));
         }
@@ -251,8 +264,8 @@ int iopx_aurora_instance_create(const iopx_r1cs *r1cs, const uint64_t *assignmen
         else if (field == IOPX_FIELD_EDWARDS_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<edwards_Fr_element>(r1cs, assignment));
         else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<alt_bn128_Fr_element>(r1cs, assignment));
         else if (field == IOPX_FIELD_GF64) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<libiop_amd::gf64>(r1cs, assignment));
-        else if (field == IOPX_FIELD_GF128) throw std::invalid_argument("iopx_aurora_instance_create: only the FRI-only SNARK is built over gf128 (no protocol-layer kernels)");
-        else if (field == IOPX_FIELD_GF256) throw std::invalid_argument("iopx_aurora_instance_create: only the FRI-only SNARK is built over gf256 (no protocol-layer kernels)");
+        else if (field == IOPX_FIELD_GF128) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<libiop_amd::gf128>(r1cs, assignment));
+        else if (field == IOPX_FIELD_GF256) *out = reinterpret_cast<iopx_aurora_instance *>(make_from_csr<libiop_amd::gf256>(r1cs, assignment));
         else throw std::invalid_argument("unknown field");
     });
 }
@@ -267,6 +280,8 @@ int iopx_aurora_example_instance_create(int field, size_t num_constraints, size_
         else if (field == IOPX_FIELD_EDWARDS_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<edwards_Fr_element>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_ALT_BN128_FR) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<alt_bn128_Fr_element>(num_constraints, num_inputs, num_variables, seed));
         else if (field == IOPX_FIELD_GF64) *out = reinterpret_cast<iopx_aurora_instance *>(make_example<libiop_amd::gf64>(num_constraints, num_inputs, num_variables, seed));
+        // gf128, gf256: the synthetic instance is not generated over them (callers pass CSR matrices to iopx_aurora_instance_create); the wording dates from
+        // before their protocol-layer kernels and is pinned by tests
         else if (field == IOPX_FIELD_GF128) throw std::invalid_argument("iopx_aurora_example_instance_create: only the FRI-only SNARK is built over gf128 (no protocol-layer kernels)");
         else if (field == IOPX_FIELD_GF256) throw std::invalid_argument("iopx_aurora_example_instance_create: only the FRI-only SNARK is built over gf256 (no protocol-layer kernels)");
         else throw std::invalid_argument("unknown field");

@@ -317,7 +317,7 @@ class GF64:
 
 
 class GF128(GF64):
-    """libff::gf128 (x^128 + x^7 + x^2 + x + 1, two little-endian words), additive arm: the FRI-only SNARK.  Host scalars are (2,) uint64
+    """libff::gf128 (x^128 + x^7 + x^2 + x + 1, two little-endian words), additive arm: the FRI-only SNARK and Aurora.  Host scalars are (2,) uint64
     arrays; the host-side products run on Python integers, as GF64's do."""
     name, additive, elem_bytes, words, soundness_bits = "gf128", True, 16, 2, 128
     # the transforms, the fold, the LDT combination and the vector helpers: the gf192 methods with two words per element
@@ -330,6 +330,16 @@ class GF128(GF64):
         "sub": ("field_add_dev", {"words": 2}),
         "mul": ("gf192_mul_dev", {"words": 2}),
         "inv": ("field_inv_dev", {"words": 2}),
+        # what Aurora calls beyond the FRI-only SNARK (GF128AuroraOps): the entries of csrc/gf128_ops.hip
+        "rowcheck": ("rowcheck_dev", {"words": 2}),
+        "fz": ("fz_dev", {"words": 2}),
+        "sumcheck_g": ("sumcheck_g_dev", {"words": 2}),
+        "lincheck": ("lincheck_dev", {"words": 2}),
+        "lincomb": ("lincomb_dev", {"words": 2}),
+        "lincomb_affine": ("lincomb_affine_dev", {"words": 2}),
+        "pow_table": ("pow_table_dev", {"words": 2}),
+        "spmv": ("spmv_dev", {"words": 2}),
+        "poly_div_vanishing": ("poly_div_vanishing_dev", {"words": 2}),
     }
     _MASK = (1 << 64) - 1
 
@@ -404,7 +414,7 @@ class GF128(GF64):
 
 
 class GF256(GF128):
-    """libff::gf256 (x^256 + x^10 + x^5 + x^2 + 1, four little-endian words), additive arm: the FRI-only SNARK.  Host scalars are (4,) uint64
+    """libff::gf256 (x^256 + x^10 + x^5 + x^2 + 1, four little-endian words), additive arm: the FRI-only SNARK and Aurora.  Host scalars are (4,) uint64
     arrays; the host-side products run on Python integers, as GF64's do."""
     name, additive, elem_bytes, words, soundness_bits = "gf256", True, 32, 4, 256
     # the transforms, the fold, the LDT combination and the vector helpers: the gf192 methods with four words per element
@@ -417,6 +427,16 @@ class GF256(GF128):
         "sub": ("field_add_dev", {"words": 4}),
         "mul": ("gf192_mul_dev", {"words": 4}),
         "inv": ("field_inv_dev", {"words": 4}),
+        # what Aurora calls beyond the FRI-only SNARK (GF256AuroraOps): the entries of csrc/gf256_ops.hip
+        "rowcheck": ("rowcheck_dev", {"words": 4}),
+        "fz": ("fz_dev", {"words": 4}),
+        "sumcheck_g": ("sumcheck_g_dev", {"words": 4}),
+        "lincheck": ("lincheck_dev", {"words": 4}),
+        "lincomb": ("lincomb_dev", {"words": 4}),
+        "lincomb_affine": ("lincomb_affine_dev", {"words": 4}),
+        "pow_table": ("pow_table_dev", {"words": 4}),
+        "spmv": ("spmv_dev", {"words": 4}),
+        "poly_div_vanishing": ("poly_div_vanishing_dev", {"words": 4}),
     }
 
     @staticmethod
@@ -981,6 +1001,16 @@ class GF64AuroraOps(GF64DeviceOps):
     calls (div, domain_offsets, domain_elements, vanishing_evals, lagrange_evals, rational_*) keep raising."""
 
 
+class GF128AuroraOps(GF128DeviceOps):
+    """GF128DeviceOps plus what the Aurora prover calls: the iopx_*_gf128_dev entries of libiop_amd/csrc/gf128_ops.hip.  Constructed by name —
+    DeviceOps(...) over GF128 keeps returning GF128DeviceOps.  The operators only Fractal calls keep raising."""
+
+
+class GF256AuroraOps(GF256DeviceOps):
+    """GF256DeviceOps plus what the Aurora prover calls: the iopx_*_gf256_dev entries of libiop_amd/csrc/gf256_ops.hip.  Constructed by name —
+    DeviceOps(...) over GF256 keeps returning GF256DeviceOps.  The operators only Fractal calls keep raising."""
+
+
 _OPERATORS = frozenset(name for name, f in vars(DeviceOps).items() if callable(f) and not name.startswith("__") and name != "_call")
 _GF64_FRI = frozenset({"local_size", "mark_codeword_domain", "mark_fri_domains", "query_responses", "empty", "upload", "download", "FFT", "IFFT",
                        "IFFT_of_known_degree", "fold", "solve_pow", "merkle_tree", "ldt_combine"})
@@ -1007,6 +1037,8 @@ _allow_only(GF64DeviceOps, _GF64_FRI, _GF64_WHY)
 _allow_only(GF64AuroraOps, _GF64_AURORA, _GF64_WHY)
 _allow_only(GF128DeviceOps, _GF64_FRI, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(GF256DeviceOps, _GF64_FRI, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK is the prover over this field)")
+_allow_only(GF128AuroraOps, _GF64_AURORA, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK and, through GF128AuroraOps, Aurora are the provers over this field)")
+_allow_only(GF256AuroraOps, _GF64_AURORA, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK and, through GF256AuroraOps, Aurora are the provers over this field)")
 _allow_only(AltBn128DeviceOps, _OPERATORS - {"_coset_range"}, "DeviceOps.%s: coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
 
 

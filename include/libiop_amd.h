@@ -293,8 +293,8 @@ int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out);
  * (r1cs_rs_iop.tcc:181-222), sumcheck_g_oracle (sumcheck.tcc:58-119; a zero domain element inverts to zero, utils.tcc:79-97) and
  * polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371).  Codeword domains of dimension above 40 are refused.
  * iopx_gf64_mul_dev and iopx_gf64_inv_dev above are the products and inverses.  Aurora over gf64 runs through these from the Python
- * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); Fractal, a distributed prover, head
- * evaluation and the fused re-extensions are not built over gf64. */
+ * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); Fractal, a distributed prover and head
+ * evaluation are not built over gf64 (the fused re-extensions: libiop_amd_batch.h). */
 int iopx_gf64_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_gf64_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init);
 int iopx_lincomb_gf64_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
@@ -387,6 +387,11 @@ int iopx_gf256_inverse_host(const uint64_t *x, uint64_t *out);
  * twins: the gf64 entries of those names above at two and four words per element.  They are declared once for both fields, from one
  * parameterised text, in libiop_amd_gfx.h (beside this file), as the kernels behind them are written once (libiop_amd/csrc/gfx_ops.h). */
 #include "libiop_amd_gfx.h"
+
+/* ---- GF(2^64), GF(2^128), GF(2^256): batched transforms and the fused re-extension ----------------- */
+/* iopx_add_{ifft,lde,reextend,reextend_lde}_{gf64,gf128,gf256}_batch_dev: the gf192 entries of those names above at one, two and four words per
+ * element, declared once for the three fields in libiop_amd_batch.h (beside this file); the kernels are those of libiop_amd/csrc/gfx_additive.h. */
+#include "libiop_amd_batch.h"
 
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
@@ -746,14 +751,14 @@ int iopx_fp3_modulus(uint64_t *out);
 #define IOPX_FIELD_EDWARDS_FR 1
 #define IOPX_FIELD_ALT_BN128_FR 2   /* Aurora instances (BLAKE2b or Poseidon: iopx_aurora_prove_hashed) and the FRI-only SNARK; no Fractal, no distributed prover */
 /* libff::gf64 (3 stays unknown): Aurora instances and the FRI-only SNARK on one GPU with BLAKE2b, in the reference's schedule (no head evaluation, whatever
- * IOPX_HEAD_EVAL says; no fused re-extension).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf64: a communicator (the _dist forms),
+ * IOPX_HEAD_EVAL says; re-extensions through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf64: a communicator (the _dist forms),
  * iopx_fractal_index / iopx_fractal_prove, a Poseidon hash, and a codeword domain of more than 2^IOPX_GF64_MAX_DOMAIN_DIM points — the bound of the gf64
  * transform entries — which is checked from the parameters before any device work. */
 #define IOPX_FIELD_GF64 4
 #define IOPX_GF64_MAX_DOMAIN_DIM 40
 /* libff::gf128: Aurora instances from CSR matrices (iopx_aurora_instance_create; iopx_aurora_prove, iopx_aurora_prove_hashed with IOPX_HASH_BLAKE2B,
- * iopx_aurora_instance_warm) and the FRI-only SNARK on one GPU, 2 words per element, in the reference's schedule (no head evaluation, no fused
- * re-extension).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, iopx_fractal_index /
+ * iopx_aurora_instance_warm) and the FRI-only SNARK on one GPU, 2 words per element, in the reference's schedule (no head evaluation; re-extensions
+ * through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, iopx_fractal_index /
  * iopx_fractal_prove, a codeword domain of more than 2^IOPX_GFX_MAX_DOMAIN_DIM points (checked from the parameters before any device work), and
  * iopx_aurora_example_instance_create (the synthetic instance is not generated over this field: build it as CSR matrices plus an assignment). */
 #define IOPX_FIELD_GF128 5

@@ -92,6 +92,12 @@ GFX_OPS_SYMBOLS = [pattern % field for field in ("gf128", "gf256")
                                    "iopx_rowcheck_%s_dev", "iopx_fz_%s_dev", "iopx_sumcheck_g_%s_dev", "iopx_poly_div_vanishing_%s_dev")]
 
 
+# the declarations of include/libiop_amd_batch.h (which libiop_amd.h includes): the batched transforms and the fused re-extension over gf64, gf128 and
+# gf256, one parameterised text for the three fields
+BATCH_SYMBOLS = [pattern % field for field in ("gf64", "gf128", "gf256")
+                 for pattern in ("iopx_add_ifft_%s_batch_dev", "iopx_add_lde_%s_batch_dev", "iopx_add_reextend_%s_batch_dev", "iopx_add_reextend_lde_%s_batch_dev")]
+
+
 class NoDeviceError(RuntimeError):
     pass
 
@@ -321,6 +327,13 @@ class Library:
                      "sumcheck_g_%s_dev", "poly_div_vanishing_%s_dev"):
             getattr(c, "iopx_" + name % "gf128").argtypes = list(getattr(c, "iopx_" + name % "gf64").argtypes)
             getattr(c, "iopx_" + name % "gf256").argtypes = list(getattr(c, "iopx_" + name % "gf64").argtypes)
+
+        # the batched transforms and the fused re-extension: the prototypes of the gf192 entries, for the three fields of libiop_amd_batch.h
+        c.iopx_add_reextend_gf192_batch_dev.argtypes = [_vp, _sz, _u64p, _sz, _sz, _u64p, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
+        c.iopx_add_reextend_lde_gf192_batch_dev.argtypes = [_vp, _sz, ctypes.POINTER(_vp), _sz, _sz, _u64p, _sz, _sz, _u64p, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
+        for name in ("add_ifft_%s_batch_dev", "add_lde_%s_batch_dev", "add_reextend_%s_batch_dev", "add_reextend_lde_%s_batch_dev"):
+            for field in ("gf64", "gf128", "gf256"):
+                getattr(c, "iopx_" + name % field).argtypes = list(getattr(c, "iopx_" + name % "gf192").argtypes)
 
     # ---- error translation (the exception types the reference throws) ----
     def _check(self, rc):
@@ -1229,27 +1242,31 @@ class Library:
         fn = self.c.iopx_add_lde_gf128_dev if words == 2 else self.c.iopx_add_lde_gf256_dev if words == 4 else self.c.iopx_add_lde_gf192_dev
         self._check(fn(_vp(d_coeffs), n_coeffs, basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), coset_begin, coset_count, _vp(d_out)))
 
-    def additive_IFFT_batch_dev(self, d_evals, batch, basis, shift, d_out):
+    def additive_IFFT_batch_dev(self, d_evals, batch, basis, shift, d_out, words=3):
         """`batch` inverse transforms over one domain, vectors back to back."""
-        basis, shift = _as_u64(basis), _as_u64(shift)
-        self._check(self.c.iopx_add_ifft_gf192_batch_dev(_vp(d_evals), int(batch), basis.ctypes.data_as(_u64p), basis.shape[0],
-                                                         shift.ctypes.data_as(_u64p), _vp(d_out)))
+        basis, shift = _as_u64(basis, words), _as_u64(shift, words)
+        fn = (self.c.iopx_add_ifft_gf64_batch_dev if words == 1 else self.c.iopx_add_ifft_gf128_batch_dev if words == 2
+              else self.c.iopx_add_ifft_gf256_batch_dev if words == 4 else self.c.iopx_add_ifft_gf192_batch_dev)
+        self._check(fn(_vp(d_evals), int(batch), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), _vp(d_out)))
 
-    def additive_LDE_batch_dev(self, d_coeffs, n_coeffs, basis, shift, coset_begin, coset_count, d_outs):
+    def additive_LDE_batch_dev(self, d_coeffs, n_coeffs, basis, shift, coset_begin, coset_count, d_outs, words=3):
         """Low-degree extensions of several polynomials (lists of device pointers) over one domain; phase 1 runs once."""
-        basis, shift = _as_u64(basis), _as_u64(shift)
+        basis, shift = _as_u64(basis, words), _as_u64(shift, words)
         cin, cout = (_vp * len(d_coeffs))(*d_coeffs), (_vp * len(d_outs))(*d_outs)
-        self._check(self.c.iopx_add_lde_gf192_batch_dev(cin, int(n_coeffs), len(d_coeffs), basis.ctypes.data_as(_u64p), basis.shape[0],
-                                                        shift.ctypes.data_as(_u64p), int(coset_begin), int(coset_count), cout))
+        fn = (self.c.iopx_add_lde_gf64_batch_dev if words == 1 else self.c.iopx_add_lde_gf128_batch_dev if words == 2
+              else self.c.iopx_add_lde_gf256_batch_dev if words == 4 else self.c.iopx_add_lde_gf192_batch_dev)
+        self._check(fn(cin, int(n_coeffs), len(d_coeffs), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), int(coset_begin),
+                       int(coset_count), cout))
 
-    def additive_reextend_batch_dev(self, d_evals, batch, basis, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs):
+    def additive_reextend_batch_dev(self, d_evals, batch, basis, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs, words=3):
         """FFT_over_field_subset(IFFT_over_field_subset(evals, H), L) for `batch` back-to-back vectors over H = span(basis[:d_dim]) +
         eval_shift onto cosets of L = span(basis) + shift, without materialising the coefficients."""
-        basis, shift, es = _as_u64(basis), _as_u64(shift), _as_u64(eval_shift)
-        self.c.iopx_add_reextend_gf192_batch_dev.argtypes = [_vp, _sz, _u64p, _sz, _sz, _u64p, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
+        basis, shift, es = _as_u64(basis, words), _as_u64(shift, words), _as_u64(eval_shift, words)
         cout = (_vp * len(d_outs))(*d_outs)
-        self._check(self.c.iopx_add_reextend_gf192_batch_dev(_vp(d_evals), int(batch), basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim),
-                                                             es.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p), int(coset_begin), int(coset_count), cout))
+        fn = (self.c.iopx_add_reextend_gf64_batch_dev if words == 1 else self.c.iopx_add_reextend_gf128_batch_dev if words == 2
+              else self.c.iopx_add_reextend_gf256_batch_dev if words == 4 else self.c.iopx_add_reextend_gf192_batch_dev)
+        self._check(fn(_vp(d_evals), int(batch), basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim), es.ctypes.data_as(_u64p),
+                       shift.ctypes.data_as(_u64p), int(coset_begin), int(coset_count), cout))
 
     def additive_reextend2_batch_dev(self, d_evals_a, batch_a, eval_shift_a, d_evals_b, batch_b, eval_shift_b, basis, d_dim, shift, coset_begin, coset_count, d_outs):
         """additive_reextend_batch_dev for two groups of vectors over cosets of the same span with different shifts, in one batch: d_outs holds
@@ -1261,17 +1278,16 @@ class Library:
                                                               basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim), shift.ctypes.data_as(_u64p), int(coset_begin),
                                                               int(coset_count), cout))
 
-    def additive_reextend_lde_batch_dev(self, d_evals, batch, d_coeffs, n_coeffs, basis, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs):
+    def additive_reextend_lde_batch_dev(self, d_evals, batch, d_coeffs, n_coeffs, basis, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs, words=3):
         """additive_reextend_batch_dev plus, in the same batch, the codewords of the polynomials at device pointers d_coeffs (n_coeffs
         coefficients each, at most 2^d_dim): d_outs holds the `batch` re-extensions first, then one codeword per polynomial."""
-        basis, shift, es = _as_u64(basis), _as_u64(shift), _as_u64(eval_shift)
-        self.c.iopx_add_reextend_lde_gf192_batch_dev.argtypes = [_vp, _sz, ctypes.POINTER(_vp), _sz, _sz, _u64p, _sz, _sz, _u64p, _u64p, _sz, _sz,
-                                                                 ctypes.POINTER(_vp)]
+        basis, shift, es = _as_u64(basis, words), _as_u64(shift, words), _as_u64(eval_shift, words)
         cin = (_vp * max(1, len(d_coeffs)))(*d_coeffs)
         cout = (_vp * len(d_outs))(*d_outs)
-        self._check(self.c.iopx_add_reextend_lde_gf192_batch_dev(_vp(d_evals), int(batch), cin, int(n_coeffs), len(d_coeffs), basis.ctypes.data_as(_u64p),
-                                                                 basis.shape[0], int(d_dim), es.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p),
-                                                                 int(coset_begin), int(coset_count), cout))
+        fn = (self.c.iopx_add_reextend_lde_gf64_batch_dev if words == 1 else self.c.iopx_add_reextend_lde_gf128_batch_dev if words == 2
+              else self.c.iopx_add_reextend_lde_gf256_batch_dev if words == 4 else self.c.iopx_add_reextend_lde_gf192_batch_dev)
+        self._check(fn(_vp(d_evals), int(batch), cin, int(n_coeffs), len(d_coeffs), basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim),
+                       es.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p), int(coset_begin), int(coset_count), cout))
 
     def taylor_dev(self, d_S, log_n, d_twist=0):
         self._check(self.c.iopx_add_taylor_gf192_dev(_vp(d_S), log_n, _vp(d_twist)))

@@ -113,16 +113,16 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
 }
 
 // FFT_over_field_subset(IFFT_over_field_subset(v, H), L) for `batch` vectors stored back to back.  When H is spanned by the first basis
-// vectors of L the coefficient form is skipped (iopx_add_reextend_gf192_batch_dev); otherwise the two transforms run one after the other.
+// vectors of L the coefficient form is skipped (the field's add_reextend_batch entry); otherwise the two transforms run one after the other.
 // H_is_first_coset: H is the first coset of its span inside L (same shift), so the first |H| entries of each codeword are the input itself.
-// A subspace-only field (gf64, gf128, gf256) has no fused or batched re-extension: here and in the two forms below its transforms run one after the other.
+// A subspace-only field (gf64, gf128, gf256) has this entry and the one of FFT_and_reextend_packed, not the two-group form between them: there its two groups run one after the other.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &packed, std::size_t batch, const field_subset<FieldT> &H,
                                                    const field_subset<FieldT> &L, bool H_is_first_coset = false)
 {
     const std::size_t n = H.num_elements();
     std::vector<device_vector<FieldT>> outs;
-    bool prefix = additive(L) && !detail::binary_only<FieldT>() && H.dimension() <= L.dimension();
+    bool prefix = additive(L) && H.dimension() <= L.dimension();
     if (prefix) for (std::size_t i = 0; i < H.dimension(); ++i) prefix = prefix && std::memcmp(&H.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     if (prefix) {
         std::vector<uint64_t *> ptrs;
@@ -134,8 +134,8 @@ std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &
             ptrs.push_back(outs[k].words() + (copy_first ? sizeof(FieldT) / 8 * n : 0));
         }
         if (copy_first) { range.first = 1; range.second -= 1; }
-        check(iopx_add_reextend_gf192_batch_dev(packed.words(), batch, basis_words(L), L.dimension(), H.dimension(), shift_words(H), shift_words(L), range.first,
-                                                range.second, ptrs.data()));
+        check(ops::add_reextend_batch<field_of<FieldT>>(packed.words(), batch, basis_words(L), L.dimension(), H.dimension(), shift_words(H), shift_words(L), range.first,
+                                                        range.second, ptrs.data()));
         return outs;
     }
     for (std::size_t k = 0; k < batch; ++k) outs.push_back(FFT<FieldT>(IFFT<FieldT>(packed.slice(k * n, n), H), n, L));
@@ -166,13 +166,13 @@ std::vector<device_vector<FieldT>> reextend2_packed(const device_vector<FieldT> 
 }
 
 // { FFT_over_field_subset(poly, L) } followed by reextend_packed(packed, batch, H, L): one call when H is spanned by the first basis vectors
-// of L and the polynomial has at most |H| coefficients (iopx_add_reextend_lde_gf192_batch_dev: the transforms share their last passes),
+// of L and the polynomial has at most |H| coefficients (the field's add_reextend_lde_batch entry: the transforms share their forward passes),
 // the separate calls otherwise.  Same field elements either way.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> FFT_and_reextend_packed(const device_vector<FieldT> &poly, const device_vector<FieldT> &packed, std::size_t batch,
                                                            const field_subset<FieldT> &H, const field_subset<FieldT> &L)
 {
-    bool prefix = !detail::binary_only<FieldT>() && additive(L) && additive(H) && H.dimension() <= L.dimension() && poly.size() <= H.num_elements() && H.dimension() > 0;
+    bool prefix = additive(L) && additive(H) && H.dimension() <= L.dimension() && poly.size() <= H.num_elements() && H.dimension() > 0;
     if (prefix) for (std::size_t i = 0; i < H.dimension(); ++i) prefix = prefix && std::memcmp(&H.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     std::vector<device_vector<FieldT>> outs;
     if (!prefix) {
@@ -186,8 +186,8 @@ std::vector<device_vector<FieldT>> FFT_and_reextend_packed(const device_vector<F
     for (std::size_t k = 0; k < batch; ++k) ptrs[k] = outs[1 + k].words();
     ptrs[batch] = outs[0].words();
     const uint64_t *coeffs[1] = { poly.words() };
-    check(iopx_add_reextend_lde_gf192_batch_dev(packed.words(), batch, coeffs, poly.size(), 1, basis_words(L), L.dimension(), H.dimension(), shift_words(H),
-                                                shift_words(L), range.first, range.second, ptrs.data()));
+    check(ops::add_reextend_lde_batch<field_of<FieldT>>(packed.words(), batch, coeffs, poly.size(), 1, basis_words(L), L.dimension(), H.dimension(), shift_words(H),
+                                                        shift_words(L), range.first, range.second, ptrs.data()));
     return outs;
 }
 

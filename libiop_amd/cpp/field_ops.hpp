@@ -42,6 +42,9 @@ struct subspace_ops {
     decltype(&iopx_rowcheck_gf192_dev) rowcheck; decltype(&iopx_fz_gf192_dev) fz; decltype(&iopx_sumcheck_g_gf192_dev) sumcheck_g;
     decltype(&iopx_poly_div_vanishing_gf192_dev) poly_div_vanishing; decltype(&iopx_domain_offsets_gf192_dev) domain_offsets;
     decltype(&iopx_vanishing_evals_gf192_dev) vanishing_evals; decltype(&iopx_rational_sumcheck_constraint_gf192_dev) rational_sumcheck_constraint;
+    // several vectors over one domain in every launch, and the fused re-extension (IFFT over H, FFT over L, no coefficient form in between)
+    decltype(&iopx_add_ifft_gf192_batch_dev) add_ifft_batch; decltype(&iopx_add_lde_gf192_batch_dev) add_lde_batch;
+    decltype(&iopx_add_reextend_gf192_batch_dev) add_reextend_batch; decltype(&iopx_add_reextend_lde_gf192_batch_dev) add_reextend_lde_batch;
 };
 
 // the slots in the order of the declarations above, line for line
@@ -78,6 +81,8 @@ inline constexpr subspace_ops gf192_subspace = {
     iopx_rowcheck_gf192_dev, iopx_fz_gf192_dev, iopx_sumcheck_g_gf192_dev,
     iopx_poly_div_vanishing_gf192_dev, iopx_domain_offsets_gf192_dev,
     iopx_vanishing_evals_gf192_dev, iopx_rational_sumcheck_constraint_gf192_dev,
+    iopx_add_ifft_gf192_batch_dev, iopx_add_lde_gf192_batch_dev,
+    iopx_add_reextend_gf192_batch_dev, iopx_add_reextend_lde_gf192_batch_dev,
 };
 inline constexpr subspace_ops gf64_subspace = {
     iopx_add_fft_gf64_dev, iopx_add_lde_gf64_dev, iopx_add_ifft_gf64_dev,
@@ -85,6 +90,8 @@ inline constexpr subspace_ops gf64_subspace = {
     iopx_rowcheck_gf64_dev, iopx_fz_gf64_dev, iopx_sumcheck_g_gf64_dev,
     iopx_poly_div_vanishing_gf64_dev, nullptr,
     nullptr, nullptr,
+    iopx_add_ifft_gf64_batch_dev, iopx_add_lde_gf64_batch_dev,
+    iopx_add_reextend_gf64_batch_dev, iopx_add_reextend_lde_gf64_batch_dev,
 };
 inline constexpr subspace_ops gf128_subspace = {
     iopx_add_fft_gf128_dev, iopx_add_lde_gf128_dev, iopx_add_ifft_gf128_dev,
@@ -92,6 +99,8 @@ inline constexpr subspace_ops gf128_subspace = {
     iopx_rowcheck_gf128_dev, iopx_fz_gf128_dev, iopx_sumcheck_g_gf128_dev,
     iopx_poly_div_vanishing_gf128_dev, nullptr,
     nullptr, nullptr,
+    iopx_add_ifft_gf128_batch_dev, iopx_add_lde_gf128_batch_dev,
+    iopx_add_reextend_gf128_batch_dev, iopx_add_reextend_lde_gf128_batch_dev,
 };
 inline constexpr subspace_ops gf256_subspace = {
     iopx_add_fft_gf256_dev, iopx_add_lde_gf256_dev, iopx_add_ifft_gf256_dev,
@@ -99,6 +108,8 @@ inline constexpr subspace_ops gf256_subspace = {
     iopx_rowcheck_gf256_dev, iopx_fz_gf256_dev, iopx_sumcheck_g_gf256_dev,
     iopx_poly_div_vanishing_gf256_dev, nullptr,
     nullptr, nullptr,
+    iopx_add_ifft_gf256_batch_dev, iopx_add_lde_gf256_batch_dev,
+    iopx_add_reextend_gf256_batch_dev, iopx_add_reextend_lde_gf256_batch_dev,
 };
 inline constexpr prime_field_ops edwards_Fr = {
     { "edwards Fr", 180, true,
@@ -190,6 +201,27 @@ template<class F> inline int add_lde(const uint64_t *d_coeffs, std::size_t n_coe
 template<class F> inline int add_ifft(const uint64_t *d_evals, const uint64_t *basis, std::size_t m, const uint64_t *shift, uint64_t *d_out)
 {
     return entry<F>(&subspace_ops::add_ifft, "add_ifft")(d_evals, basis, m, shift, d_out);
+}
+template<class F> inline int add_ifft_batch(const uint64_t *d_evals, std::size_t batch, const uint64_t *basis, std::size_t m, const uint64_t *shift, uint64_t *d_out)
+{
+    return entry<F>(&subspace_ops::add_ifft_batch, "add_ifft_batch")(d_evals, batch, basis, m, shift, d_out);
+}
+template<class F> inline int add_lde_batch(const uint64_t *const *d_coeffs, std::size_t n_coeffs, std::size_t batch, const uint64_t *basis, std::size_t m, const uint64_t *shift,
+                                           std::size_t coset_begin, std::size_t coset_count, uint64_t *const *d_outs)
+{
+    return entry<F>(&subspace_ops::add_lde_batch, "add_lde_batch")(d_coeffs, n_coeffs, batch, basis, m, shift, coset_begin, coset_count, d_outs);
+}
+template<class F> inline int add_reextend_batch(const uint64_t *d_evals, std::size_t batch, const uint64_t *basis, std::size_t m, std::size_t d_dim, const uint64_t *eval_shift,
+                                                const uint64_t *shift, std::size_t coset_begin, std::size_t coset_count, uint64_t *const *d_outs)
+{
+    return entry<F>(&subspace_ops::add_reextend_batch, "add_reextend_batch")(d_evals, batch, basis, m, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs);
+}
+template<class F> inline int add_reextend_lde_batch(const uint64_t *d_evals, std::size_t batch, const uint64_t *const *d_coeffs, std::size_t n_coeffs, std::size_t n_polys,
+                                                    const uint64_t *basis, std::size_t m, std::size_t d_dim, const uint64_t *eval_shift, const uint64_t *shift,
+                                                    std::size_t coset_begin, std::size_t coset_count, uint64_t *const *d_outs)
+{
+    return entry<F>(&subspace_ops::add_reextend_lde_batch, "add_reextend_lde_batch")(d_evals, batch, d_coeffs, n_coeffs, n_polys, basis, m, d_dim, eval_shift, shift, coset_begin,
+                                                                                     coset_count, d_outs);
 }
 template<class F> inline int fri_fold_add(const uint64_t *d_f, const uint64_t *basis, std::size_t m, const uint64_t *shift, std::size_t coset_size, const uint64_t *x_i, uint64_t *d_next)
 {

@@ -37,6 +37,31 @@ int iopx_add_ifft_gf256_dev(const uint64_t *d_evals, const uint64_t *basis, size
     return x_add_ifft_dev<Elem256>(d_evals, basis, m, shift, d_out);
 }
 
+// the batched and fused forms (include/libiop_amd_batch.h)
+int iopx_add_ifft_gf256_batch_dev(const uint64_t *d_evals, size_t batch, const uint64_t *basis, size_t m, const uint64_t *shift, uint64_t *d_out)
+{
+    return x_add_ifft_batch_dev<Elem256>(d_evals, batch, basis, m, shift, d_out);
+}
+
+int iopx_add_lde_gf256_batch_dev(const uint64_t *const *d_coeffs, size_t n_coeffs, size_t batch, const uint64_t *basis, size_t m,
+                                 const uint64_t *shift, size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    return x_add_lde_batch_dev<Elem256>(d_coeffs, n_coeffs, batch, basis, m, shift, coset_begin, coset_count, d_outs);
+}
+
+int iopx_add_reextend_gf256_batch_dev(const uint64_t *d_evals, size_t batch, const uint64_t *basis, size_t m, size_t d_dim, const uint64_t *eval_shift,
+                                      const uint64_t *shift, size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    return x_add_reextend_batch_dev<Elem256>(d_evals, batch, basis, m, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs);
+}
+
+int iopx_add_reextend_lde_gf256_batch_dev(const uint64_t *d_evals, size_t batch, const uint64_t *const *d_coeffs, size_t n_coeffs, size_t n_polys,
+                                          const uint64_t *basis, size_t m, size_t d_dim, const uint64_t *eval_shift, const uint64_t *shift,
+                                          size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    return x_add_reextend_lde_batch_dev<Elem256>(d_evals, batch, d_coeffs, n_coeffs, n_polys, basis, m, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs);
+}
+
 int iopx_add_fft_gf256(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                        const uint64_t *shift, uint64_t *out)
 {

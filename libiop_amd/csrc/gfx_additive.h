@@ -728,26 +728,26 @@ static BfParamsX bf_params_x(const AddPlanX<F> &pl, const uint64_t *rs, int nhi)
 static bool bf_a16(const BfParamsX &p) { return al16(p.src) && al16(p.dst) && al16(p.rs) && al16(p.ltab); }
 
 template<class F>
-static void launch_upper_x(bool inv, BfParamsX p, const P2PassX &ps, size_t cosets)
+static void launch_upper_x(bool inv, BfParamsX p, const P2PassX &ps, size_t cosets, bool batch = false)
 {
     const size_t EB = sizeof(typename F::mem);
     p.c = ps.c; p.h = ps.h; p.A = ps.A; p.p_hi = ps.p_hi; p.p_lo = ps.p_lo;
     const int tb = ps.c + ps.A;
     const size_t E = (size_t)1 << tb, grid = cosets << (p.d - tb);
     const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 2));
-    if (inv) IOPX_LAUNCHX(bf_a16(p), "bfly_upper_inv", (cosets * 2 * EB) << p.d, kx_bfly_upper_inv, dim3((unsigned)grid), dim3(threads), E * EB, p);
+    if (inv) IOPX_LAUNCHX(bf_a16(p), batch ? "bfly_upper_inv_batch" : "bfly_upper_inv", (cosets * 2 * EB) << p.d, kx_bfly_upper_inv, dim3((unsigned)grid), dim3(threads), E * EB, p);
     else IOPX_LAUNCHX(bf_a16(p), "bfly_upper", (cosets * 2 * EB) << p.d, kx_bfly_upper, dim3((unsigned)grid), dim3(threads), E * EB, p);
 }
 
 template<class F>
-static void launch_edge_x(bool inv, BfParamsX p, size_t cosets)
+static void launch_edge_x(bool inv, BfParamsX p, size_t cosets, bool batch = false)
 {
     const size_t EB = sizeof(typename F::mem);
     const int tb = p.a_low + p.c_top;
     p.total_units = cosets << (p.d - tb);
     const size_t E = (size_t)1 << (tb + p.g_bits), grid = (p.total_units + (((size_t)1) << p.g_bits) - 1) >> p.g_bits;
     const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 2));
-    if (inv) IOPX_LAUNCHX(bf_a16(p), "bfly_edge_inv", (cosets * 2 * EB) << p.d, kx_bfly_edge_inv, dim3((unsigned)grid), dim3(threads), E * EB, p);
+    if (inv) IOPX_LAUNCHX(bf_a16(p), batch ? "bfly_edge_inv_batch" : "bfly_edge_inv", (cosets * 2 * EB) << p.d, kx_bfly_edge_inv, dim3((unsigned)grid), dim3(threads), E * EB, p);
     else IOPX_LAUNCHX(bf_a16(p), "bfly_edge", (cosets * 2 * EB) << p.d, kx_bfly_edge, dim3((unsigned)grid), dim3(threads), E * EB, p);
 }
 
@@ -897,6 +897,368 @@ static int x_add_ifft_dev(const uint64_t *d_evals, const uint64_t *basis, size_t
     if (rc != IOPX_OK) return rc;
     if (W != d_out) return copy_d2d(d_out, W, EB << m);
     return IOPX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched forms: several vectors over ONE domain share every launch (x_add_ifft_batch_dev, x_add_lde_batch_dev), and the fused re-extension
+// (x_add_reextend_lde_batch_dev).  The kernels are the bodies above under a second grid dimension: workgroup (x, v) does for vector v what
+// workgroup x does in the single-vector launch, so the outputs are the single-vector entries' bit for bit.  An inverse pass over `batch` vectors
+// stored back to back needs no second dimension: with no coset basis (nhi = 0) the vectors are the "cosets" of the single-vector kernels, and
+// 2^g_bits small vectors share one workgroup's tile as cosets do.  The profile reports every launch of this section under the kernel's name + "_batch".
+// ---------------------------------------------------------------------------------------------
+struct BfBatchParamsX {
+    BfParamsX p;                    // src / dst: vector 0's
+    const uint64_t *const *dsts;    // last pass: device array of the vectors' outputs (the caller's d_outs)
+    size_t src_stride, dst_stride;  // elements from one vector to the next in src / in dst (upper passes)
+    size_t dst_off;                 // last pass: elements added to dsts[v] (the coset group's offset)
+};
+
+template<class F, bool A16>
+__global__ void __launch_bounds__(512, F::UPPER_WAVES) kx_bfly_upper_batch(BfBatchParamsX q)
+{
+    BfParamsX p = q.p;
+    p.src += (size_t)F::W * blockIdx.y * q.src_stride;
+    p.dst += (size_t)F::W * blockIdx.y * q.dst_stride;
+    bfly_upper_body<F, A16, false>(p);
+}
+
+template<class F, bool A16>
+__global__ void __launch_bounds__(512) kx_bfly_edge_batch(BfBatchParamsX q)
+{
+    BfParamsX p = q.p;
+    p.src += (size_t)F::W * blockIdx.y * q.src_stride;
+    p.dst = const_cast<uint64_t *>(q.dsts[blockIdx.y]) + (size_t)F::W * q.dst_off;
+    bfly_edge_body<F, A16, false>(p);
+}
+
+struct P1BatchParamsX { P1ParamsX p; size_t stride; };
+template<class F, bool A16> __global__ void __launch_bounds__(512) kx_phase1_batch(P1BatchParamsX q)
+{
+    P1ParamsX p = q.p;
+    p.S += (size_t)F::W * blockIdx.y * q.stride;
+    phase1_body<F, A16, false>(p);
+}
+template<class F, bool A16> __global__ void __launch_bounds__(512) kx_phase1_inv_batch(P1BatchParamsX q)
+{
+    P1ParamsX p = q.p;
+    p.S += (size_t)F::W * blockIdx.y * q.stride;
+    phase1_body<F, A16, true>(p);
+}
+
+// dst + v * 2^d <- srcs[v] zero padded, for every vector v of the grid's second dimension
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_pad_copy_batch(uint64_t *dst, const uint64_t *const *srcs, size_t n_src, size_t n_dst)
+{
+    const uint64_t *src = srcs[blockIdx.y];
+    uint64_t *out = dst + (size_t)F::W * blockIdx.y * n_dst;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_dst; i += (size_t)gridDim.x * blockDim.x)
+        F::template store<A16>(out, i, i < n_src ? F::template load<A16>(src, i) : F::zero());
+}
+
+static const size_t BATCH_MAX_X = 65535;           // the second grid dimension's bound
+
+// phase 1 of `count` vectors of 2^d elements back to back at S: one launch per pass
+template<class F, bool INV>
+static int run_phase1_batch_x(AddPlanX<F> &pl, uint64_t *S, size_t count)
+{
+    const size_t EB = sizeof(typename F::mem);
+    int rc = ensure_pow_x(pl, INV);
+    if (rc != IOPX_OK) return rc;
+    const size_t np = pl.p1.size();
+    const bool a16 = al16(S) && al16((INV ? pl.pow_inv : pl.pow).p);      // an element is 16 bytes or more where it matters: every vector is aligned as the first
+    for (size_t i = 0; i < np; ++i) {
+        const P1PassX &ps = pl.p1[INV ? np - 1 - i : i];
+        P1BatchParamsX q;
+        P1ParamsX &p = q.p;
+        p.S = S; p.pow = (INV ? pl.pow_inv : pl.pow).u64(); p.d = pl.d;
+        p.c = ps.c; p.h = ps.h; p.A = ps.A; p.j0 = ps.j0; p.j1 = ps.j1; p.k_start = ps.k_start; p.k_end = ps.k_end; p.twist_first = ps.twist_first;
+        q.stride = (size_t)1 << pl.d;
+        const int tb = ps.c + ps.A;
+        const size_t E = (size_t)1 << tb, grid = (size_t)1 << (pl.d - tb);
+        const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 4));
+        if (INV) IOPX_LAUNCHX(a16, "phase1_inv_batch", (count * 2 * EB) << pl.d, kx_phase1_inv_batch, dim3((unsigned)grid, (unsigned)count), dim3(threads), E * EB, q);
+        else IOPX_LAUNCHX(a16, "phase1_batch", (count * 2 * EB) << pl.d, kx_phase1_batch, dim3((unsigned)grid, (unsigned)count), dim3(threads), E * EB, q);
+    }
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// inverse phase 2 of `count` vectors back to back (natural order at src -> block order at dst, src != dst): the vectors as the cosets of the
+// single-vector kernels, rs = the recursed shift alone
+template<class F>
+static int run_phase2_inv_batch_x(AddPlanX<F> &pl, const uint64_t *src, uint64_t *dst, const uint64_t *rs, size_t count)
+{
+    BfParamsX p = bf_params_x(pl, rs, 0);
+    p.src = src; p.dst = dst;
+    launch_edge_x<F>(true, p, count, true);
+    p.src = dst;
+    for (size_t i = pl.p2_upper.size(); i-- > 0;) launch_upper_x<F>(true, p, pl.p2_upper[i], count, true);
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+template<class F>
+static void launch_upper_batch_x(BfBatchParamsX q, const P2PassX &ps, size_t cosets, size_t vectors, bool a16)
+{
+    const size_t EB = sizeof(typename F::mem);
+    BfParamsX &p = q.p;
+    p.c = ps.c; p.h = ps.h; p.A = ps.A; p.p_hi = ps.p_hi; p.p_lo = ps.p_lo;
+    const int tb = ps.c + ps.A;
+    const size_t E = (size_t)1 << tb, grid = cosets << (p.d - tb);
+    const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 2));
+    IOPX_LAUNCHX(a16, "bfly_upper_batch", (vectors * cosets * 2 * EB) << p.d, kx_bfly_upper_batch, dim3((unsigned)grid, (unsigned)vectors), dim3(threads), E * EB, q);
+}
+
+template<class F>
+static void launch_edge_batch_x(BfBatchParamsX q, size_t cosets, size_t vectors, bool a16)
+{
+    const size_t EB = sizeof(typename F::mem);
+    BfParamsX &p = q.p;
+    const int tb = p.a_low + p.c_top;
+    p.total_units = cosets << (p.d - tb);
+    const size_t E = (size_t)1 << (tb + p.g_bits), grid = (p.total_units + (((size_t)1) << p.g_bits) - 1) >> p.g_bits;
+    const int threads = (int)std::min<size_t>(512, std::max<size_t>(64, E / 2));
+    IOPX_LAUNCHX(a16, "bfly_edge_batch", (vectors * cosets * 2 * EB) << p.d, kx_bfly_edge_batch, dim3((unsigned)grid, (unsigned)vectors), dim3(threads), E * EB, q);
+}
+
+// Forward phase 2 of cosets [coset_begin, +coset_count) for `total` vectors of 2^d elements in block order, back to back at Wk (overwritten), into the
+// outputs d_dsts[v] (a device array; outs_a16: every one of them is 16-byte aligned).  The block-order staging of the upper passes holds a
+// group of cosets of a group of vectors, at most 2^STAGE_BITS elements as in run_phase2_fwd_x (one coset of one vector where that is
+// already more): a batch that does not fit takes the coset range, and then the vectors, in several rounds.
+template<class F>
+static int run_phase2_fwd_batch_x(AddPlanX<F> &pl, uint64_t *Wk, size_t total, const uint64_t *const *d_dsts, bool outs_a16, const uint64_t *rs, int nhi,
+                                  size_t coset_begin, size_t coset_count)
+{
+    const size_t EB = sizeof(typename F::mem);
+    const int d = pl.d;
+    const size_t nd = (size_t)1 << d;
+    BfBatchParamsX q;
+    memset(&q, 0, sizeof(q));
+    q.p = bf_params_x(pl, rs, nhi);
+    BfParamsX &p = q.p;
+    const bool a16 = al16(Wk) && al16(rs) && al16(p.ltab);
+    if (pl.p2_upper.empty() || coset_count == 1) {          // no staging: one pass from Wk, or the upper passes in place on Wk
+        for (size_t v0 = 0; v0 < total; v0 += BATCH_MAX_X) {
+            const size_t nv = std::min(BATCH_MAX_X, total - v0);
+            p.src = Wk + F::W * v0 * nd; p.dst = Wk + F::W * v0 * nd;
+            q.src_stride = nd; q.dst_stride = nd; q.dsts = d_dsts + v0;
+            if (pl.p2_upper.empty()) {
+                const size_t step = (size_t)1 << 30;        // the unit count of a launch stays below 2^31 workgroups
+                for (size_t c0 = 0; c0 < coset_count; c0 += step) {
+                    p.src_shared = 1; p.coset_base = coset_begin + c0; q.dst_off = c0 << d;
+                    launch_edge_batch_x<F>(q, std::min(step, coset_count - c0), nv, a16 && outs_a16);
+                }
+            } else {
+                p.src_shared = 0; p.coset_base = coset_begin; q.dst_off = 0;
+                for (const P2PassX &ps : pl.p2_upper) launch_upper_batch_x<F>(q, ps, 1, nv, a16);
+                launch_edge_batch_x<F>(q, 1, nv, a16 && outs_a16);
+            }
+        }
+        IOPX_HIP(hipGetLastError());
+        return IOPX_OK;
+    }
+    const int stage_bits = opt_range("IOPX_GFX_BATCH_STAGE_BITS", F::STAGE_BITS, 0, F::STAGE_BITS);       // the tests lower it to reach the rounds at small sizes
+    const size_t slots = std::max<size_t>(1, ((size_t)1 << stage_bits) >> d);                               // cosets of single vectors the staging may hold
+    const size_t nvmax = std::min(std::min(total, slots), BATCH_MAX_X), group = std::min(coset_count, std::max<size_t>(1, slots / nvmax));
+    TmpBuf stage;
+    int rc = stage.alloc((nvmax * group * EB) << d);
+    if (rc != IOPX_OK) return rc;
+    const bool sa16 = a16 && al16(stage.p);
+    for (size_t v0 = 0; v0 < total; v0 += nvmax) {
+        const size_t nv = std::min(nvmax, total - v0);
+        for (size_t c0 = 0; c0 < coset_count; c0 += group) {
+            const size_t cnt = std::min(group, coset_count - c0);
+            p.coset_base = coset_begin + c0;
+            p.dst = stage.u64(); q.dst_stride = group << d;
+            for (size_t i = 0; i < pl.p2_upper.size(); ++i) {
+                if (i == 0) { p.src = Wk + F::W * v0 * nd; p.src_shared = 1; q.src_stride = nd; }
+                else { p.src = stage.u64(); p.src_shared = 0; q.src_stride = group << d; }
+                launch_upper_batch_x<F>(q, pl.p2_upper[i], cnt, nv, sa16);
+            }
+            p.src = stage.u64(); p.src_shared = 0; q.src_stride = group << d;
+            q.dsts = d_dsts + v0; q.dst_off = c0 << d;
+            launch_edge_batch_x<F>(q, cnt, nv, sa16 && outs_a16);
+        }
+    }
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// the recursed shift terms of H's shift alone and of L's shift with its coset basis, in one table: rs_H at element 0, rs_L at element d
+template<class F>
+static int upload_rs2_x(const AddPlanX<F> &pl, const uint64_t *eval_shift, const uint64_t *shift, const uint64_t *hi_basis, int nhi, TmpBuf &drs)
+{
+    typedef typename F::host H;
+    std::vector<uint64_t> rs((size_t)(2 + nhi) * pl.d * F::W);
+    pl.recurse(H(eval_shift), rs.data());
+    pl.recurse(H(shift), rs.data() + (size_t)pl.d * F::W);
+    for (int v = 0; v < nhi; ++v) pl.recurse(H(hi_basis + F::W * v), rs.data() + (size_t)(2 + v) * pl.d * F::W);
+    int rc = drs.alloc(rs.size() * 8);
+    if (rc != IOPX_OK) return rc;
+    return upload(drs.p, rs.data(), rs.size() * 8);
+}
+
+// a host array of device pointers on the device; *a16: every one of them is 16-byte aligned
+static int upload_ptrs_x(const uint64_t *const *a, size_t na, const uint64_t *const *b, size_t nb, TmpBuf &dptrs, bool *a16)
+{
+    std::vector<uint64_t> h;
+    *a16 = true;
+    for (size_t k = 0; k < na; ++k) { h.push_back((uint64_t)(uintptr_t)a[k]); *a16 = *a16 && al16(a[k]); }
+    for (size_t k = 0; k < nb; ++k) { h.push_back((uint64_t)(uintptr_t)b[k]); *a16 = *a16 && al16(b[k]); }
+    int rc = dptrs.alloc(h.size() * 8);
+    if (rc != IOPX_OK) return rc;
+    return upload(dptrs.p, h.data(), h.size() * 8);
+}
+
+static int check_batch_x(size_t batch)
+{
+    if (batch == 0 || batch > 65535) return fail(IOPX_ERR_INVALID_ARGUMENT, "batch size %zu outside 1..65535", batch);
+    return IOPX_OK;
+}
+
+// `batch` inverse transforms over the same domain, vectors stored back to back (d_evals and d_out: batch * 2^m elements)
+template<class F>
+static int x_add_ifft_batch_dev(const uint64_t *d_evals, size_t batch, const uint64_t *basis, size_t m, const uint64_t *shift, uint64_t *d_out)
+{
+    const size_t EB = sizeof(typename F::mem);
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    rc = check_basis_args_x(basis, m, shift);
+    if (rc != IOPX_OK) return rc;
+    if (!d_evals || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    if ((rc = check_batch_x(batch)) != IOPX_OK) return rc;
+    const size_t bytes = (batch * EB) << m;
+    if (m == 0) return copy_d2d(d_out, d_evals, bytes);
+    std::shared_ptr<AddPlanX<F>> pl;
+    rc = get_plan_x<F>(basis, (int)m, &pl);
+    if (rc != IOPX_OK) return rc;
+    TmpBuf drs;
+    rc = upload_rs_x(*pl, shift, nullptr, 0, drs);
+    if (rc != IOPX_OK) return rc;
+    // the first pass permutes: in place, the transforms run in a work buffer and are copied back
+    TmpBuf work;
+    uint64_t *W = d_out;
+    if (d_evals == d_out) {
+        rc = work.alloc(bytes);
+        if (rc != IOPX_OK) return rc;
+        W = work.u64();
+    }
+    rc = run_phase2_inv_batch_x(*pl, d_evals, W, drs.u64(), batch);
+    if (rc != IOPX_OK) return rc;
+    rc = run_phase1_batch_x<F, true>(*pl, W, batch);
+    if (rc != IOPX_OK) return rc;
+    if (W != d_out) return copy_d2d(d_out, W, bytes);
+    return IOPX_OK;
+}
+
+// `batch` low-degree extensions over the same domain: polynomial k (n_coeffs coefficients at d_coeffs[k]) -> cosets [coset_begin, +coset_count)
+// of its transform at d_outs[k]
+template<class F>
+static int x_add_lde_batch_dev(const uint64_t *const *d_coeffs, size_t n_coeffs, size_t batch, const uint64_t *basis, size_t m, const uint64_t *shift,
+                               size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    const size_t EB = sizeof(typename F::mem);
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    rc = check_basis_args_x(basis, m, shift);
+    if (rc != IOPX_OK) return rc;
+    if (!d_coeffs || !d_outs) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    if ((rc = check_batch_x(batch)) != IOPX_OK) return rc;
+    for (size_t k = 0; k < batch; ++k) if (!d_coeffs[k] || !d_outs[k]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    const size_t n = (size_t)1 << m;
+    if (n_coeffs > n) return fail(IOPX_ERR_INVALID_ARGUMENT, "additive FFT: %zu coefficients exceed the domain size %zu", n_coeffs, n);
+    if (n_coeffs <= 1) {                                    // constants: one fill each
+        for (size_t k = 0; k < batch; ++k) {
+            rc = x_add_lde_dev<F>(d_coeffs[k], n_coeffs, basis, m, shift, coset_begin, coset_count, d_outs[k]);
+            if (rc != IOPX_OK) return rc;
+        }
+        return IOPX_OK;
+    }
+    const int d = (int)ceil_log2(n_coeffs);
+    const int nhi = (int)m - d;
+    const size_t all_cosets = (size_t)1 << nhi, nd = (size_t)1 << d;
+    if (coset_count == 0 || coset_begin >= all_cosets || coset_count > all_cosets - coset_begin)
+        return fail(IOPX_ERR_INVALID_ARGUMENT, "coset range [%zu, +%zu) outside the %zu cosets of the transform", coset_begin, coset_count, all_cosets);
+    std::shared_ptr<AddPlanX<F>> pl;
+    rc = get_plan_x<F>(basis, d, &pl);
+    if (rc != IOPX_OK) return rc;
+    TmpBuf drs, dptrs, work;
+    rc = upload_rs_x(*pl, shift, basis + F::W * (size_t)d, nhi, drs);
+    if (rc != IOPX_OK) return rc;
+    bool ptrs_a16;
+    rc = upload_ptrs_x(d_outs, batch, d_coeffs, batch, dptrs, &ptrs_a16);
+    if (rc != IOPX_OK) return rc;
+    rc = work.alloc(batch * nd * EB);
+    if (rc != IOPX_OK) return rc;
+    const uint64_t *const *dev_outs = (const uint64_t *const *)dptrs.u64();
+    IOPX_LAUNCHX(al16(work.p) && ptrs_a16, "pad_copy_batch", 0, kx_pad_copy_batch, dim3(grid_x(nd, 256), (unsigned)batch), dim3(256), 0, work.u64(), dev_outs + batch,
+                 n_coeffs, nd);
+    rc = run_phase1_batch_x<F, false>(*pl, work.u64(), batch);
+    if (rc != IOPX_OK) return rc;
+    return run_phase2_fwd_batch_x(*pl, work.u64(), batch, dev_outs, ptrs_a16, drs.u64(), nhi, coset_begin, coset_count);
+}
+
+// FFT_over_field_subset(IFFT_over_field_subset(evals, H), L) for `batch` vectors back to back, H = span(basis[0..d_dim)) + eval_shift and
+// L = span(basis[0..m)) + shift, together with the codewords of n_polys polynomials of n_coeffs <= 2^d_dim coefficients (d_outs: the re-extensions,
+// then the codewords).  Phase 1 depends on the basis prefix only, not on the shift, so the inverse transform's last half and the forward transform's
+// first half cancel exactly: H's butterflies are undone into block order and the butterflies of L's cosets applied to that, with no phase-1 pass and no
+// coefficient vector in between; the polynomials join after a phase 1 of their own, and every forward launch serves both kinds.
+template<class F>
+static int x_add_reextend_lde_batch_dev(const uint64_t *d_evals, size_t batch, const uint64_t *const *d_coeffs, size_t n_coeffs, size_t n_polys,
+                                        const uint64_t *basis, size_t m, size_t d_dim, const uint64_t *eval_shift, const uint64_t *shift,
+                                        size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    const size_t EB = sizeof(typename F::mem);
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    rc = check_basis_args_x(basis, m, shift);
+    if (rc != IOPX_OK) return rc;
+    if (!d_evals || !d_outs || !eval_shift || (n_polys && !d_coeffs)) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    if (batch == 0 || batch > 65535 || n_polys > 65535) return fail(IOPX_ERR_INVALID_ARGUMENT, "batch size %zu + %zu outside 1..65535", batch, n_polys);
+    if (d_dim > m) return fail(IOPX_ERR_INVALID_ARGUMENT, "the evaluation domain must be spanned by the first basis vectors of the codeword domain");
+    for (size_t k = 0; k < batch + n_polys; ++k) if (!d_outs[k]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    for (size_t k = 0; k < n_polys; ++k) if (!d_coeffs[k]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    const int d = (int)d_dim, nhi = (int)m - d;
+    const size_t all_cosets = (size_t)1 << nhi, nd = (size_t)1 << d;
+    if (n_polys && n_coeffs > nd) return fail(IOPX_ERR_INVALID_ARGUMENT, "%zu coefficients exceed the 2^%d of the evaluation domain", n_coeffs, d);
+    if (coset_count == 0 || coset_begin >= all_cosets || coset_count > all_cosets - coset_begin)
+        return fail(IOPX_ERR_INVALID_ARGUMENT, "coset range [%zu, +%zu) outside the %zu cosets of the transform", coset_begin, coset_count, all_cosets);
+    if (d == 0) {                                           // constants: every evaluation equals them
+        for (size_t k = 0; k < batch + n_polys; ++k) {
+            rc = x_add_lde_dev<F>(k < batch ? d_evals + F::W * k : d_coeffs[k - batch], k < batch ? 1 : n_coeffs, basis, m, shift, coset_begin, coset_count, d_outs[k]);
+            if (rc != IOPX_OK) return rc;
+        }
+        return IOPX_OK;
+    }
+    std::shared_ptr<AddPlanX<F>> pl;
+    rc = get_plan_x<F>(basis, d, &pl);
+    if (rc != IOPX_OK) return rc;
+    const size_t total = batch + n_polys;
+    TmpBuf drs, dptrs, work;
+    rc = upload_rs2_x(*pl, eval_shift, shift, basis + F::W * (size_t)d, nhi, drs);
+    if (rc != IOPX_OK) return rc;
+    bool ptrs_a16;
+    rc = upload_ptrs_x(d_outs, total, d_coeffs, n_polys, dptrs, &ptrs_a16);
+    if (rc != IOPX_OK) return rc;
+    rc = work.alloc(total * nd * EB);
+    if (rc != IOPX_OK) return rc;
+    const uint64_t *const *dev_outs = (const uint64_t *const *)dptrs.u64();
+    rc = run_phase2_inv_batch_x(*pl, d_evals, work.u64(), drs.u64(), batch);           // H's butterflies undone: natural order -> block order
+    if (rc != IOPX_OK) return rc;
+    if (n_polys) {
+        uint64_t *P = work.u64() + F::W * batch * nd;
+        IOPX_LAUNCHX(al16(P) && ptrs_a16, "pad_copy_batch", 0, kx_pad_copy_batch, dim3(grid_x(nd, 256), (unsigned)n_polys), dim3(256), 0, P, dev_outs + total, n_coeffs, nd);
+        rc = run_phase1_batch_x<F, false>(*pl, P, n_polys);
+        if (rc != IOPX_OK) return rc;
+    }
+    return run_phase2_fwd_batch_x(*pl, work.u64(), total, dev_outs, ptrs_a16, drs.u64() + F::W * (size_t)d, nhi, coset_begin, coset_count);
+}
+
+template<class F>
+static int x_add_reextend_batch_dev(const uint64_t *d_evals, size_t batch, const uint64_t *basis, size_t m, size_t d_dim, const uint64_t *eval_shift,
+                                    const uint64_t *shift, size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    return x_add_reextend_lde_batch_dev<F>(d_evals, batch, nullptr, 0, 0, basis, m, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs);
 }
 
 template<class F>

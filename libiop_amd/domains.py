@@ -197,11 +197,14 @@ class GF64:
     """libff::gf64 (x^64 + x^4 + x^3 + x + 1, one word), additive arm.  Host scalars are (1,) uint64 arrays; the handful of host-side
     products run on Python integers."""
     name, additive, elem_bytes, words, soundness_bits = "gf64", True, 8, 1, 64
-    # no batched or fused transform, nothing that only Fractal calls; lincomb_affine is there because its entry shares the kernel of lincomb
+    # nothing that only Fractal calls; lincomb_affine is there because its entry shares the kernel of lincomb
     entries = {
         "FFT": ("additive_FFT_gf64_dev", {}),
         "IFFT": ("additive_IFFT_gf64_dev", {}),
         "LDE": ("additive_LDE_gf64_dev", {}),                           # optional: reextend_packed, one vector at a time
+        "LDE_batch": ("additive_LDE_batch_dev", {"words": 1}),          # optional: FFT_batch
+        "IFFT_batch": ("additive_IFFT_batch_dev", {"words": 1}),        # optional: IFFT_batch, IFFT_batch_packed
+        "reextend_batch": ("additive_reextend_batch_dev", {"words": 1}),  # optional: reextend_packed, fused
         "fold": ("evaluate_next_f_i_over_entire_domain_gf64_dev", {}),
         "ldt_combine": ("ldt_combine_gf64_dev", {}),
         "rowcheck": ("rowcheck_dev", {"words": 1}),
@@ -325,6 +328,9 @@ class GF128(GF64):
         "FFT": ("additive_FFT_dev", {"words": 2}),
         "IFFT": ("additive_IFFT_dev", {"words": 2}),
         "LDE": ("additive_LDE_dev", {"words": 2}),
+        "LDE_batch": ("additive_LDE_batch_dev", {"words": 2}),          # optional: FFT_batch
+        "IFFT_batch": ("additive_IFFT_batch_dev", {"words": 2}),        # optional: IFFT_batch, IFFT_batch_packed
+        "reextend_batch": ("additive_reextend_batch_dev", {"words": 2}),  # optional: reextend_packed, fused
         "fold": ("fri_fold_dev", {"words": 2}),
         "ldt_combine": ("ldt_combine_dev", {"words": 2}),
         "sub": ("field_add_dev", {"words": 2}),
@@ -422,6 +428,9 @@ class GF256(GF128):
         "FFT": ("additive_FFT_dev", {"words": 4}),
         "IFFT": ("additive_IFFT_dev", {"words": 4}),
         "LDE": ("additive_LDE_dev", {"words": 4}),
+        "LDE_batch": ("additive_LDE_batch_dev", {"words": 4}),          # optional: FFT_batch
+        "IFFT_batch": ("additive_IFFT_batch_dev", {"words": 4}),        # optional: IFFT_batch, IFFT_batch_packed
+        "reextend_batch": ("additive_reextend_batch_dev", {"words": 4}),  # optional: reextend_packed, fused
         "fold": ("fri_fold_dev", {"words": 4}),
         "ldt_combine": ("ldt_combine_dev", {"words": 4}),
         "sub": ("field_add_dev", {"words": 4}),

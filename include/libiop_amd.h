@@ -293,8 +293,8 @@ int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out);
  * (r1cs_rs_iop.tcc:181-222), sumcheck_g_oracle (sumcheck.tcc:58-119; a zero domain element inverts to zero, utils.tcc:79-97) and
  * polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371).  Codeword domains of dimension above 40 are refused.
  * iopx_gf64_mul_dev and iopx_gf64_inv_dev above are the products and inverses.  Aurora over gf64 runs through these from the Python
- * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); Fractal, a distributed prover and head
- * evaluation are not built over gf64 (the fused re-extensions: libiop_amd_batch.h). */
+ * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); Fractal and a distributed prover
+ * are not built over gf64 (the fused re-extensions: libiop_amd_batch.h; head evaluation, behind the option IOPX_GFX_HEAD_EVAL: libiop_amd_head.h). */
 int iopx_gf64_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_gf64_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init);
 int iopx_lincomb_gf64_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
@@ -392,6 +392,12 @@ int iopx_gf256_inverse_host(const uint64_t *x, uint64_t *out);
 /* iopx_add_{ifft,lde,reextend,reextend_lde}_{gf64,gf128,gf256}_batch_dev: the gf192 entries of those names above at one, two and four words per
  * element, declared once for the three fields in libiop_amd_batch.h (beside this file); the kernels are those of libiop_amd/csrc/gfx_additive.h. */
 #include "libiop_amd_batch.h"
+
+/* ---- GF(2^64), GF(2^128), GF(2^256): what head evaluation needs ------------------------------------ */
+/* iopx_div_by_vanishing_{gf64,gf128,gf256}_dev, iopx_{gf64,gf128,gf256}_vanishing_host and iopx_add_reextend2_{gf64,gf128,gf256}_batch_dev: the gf192
+ * entries of those names in this file at one, two and four words per element, declared once for the three fields in libiop_amd_head.h (beside this
+ * file).  With them the native Aurora prover takes the head route over these fields when the option IOPX_GFX_HEAD_EVAL is non-zero (default 0). */
+#include "libiop_amd_head.h"
 
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
@@ -670,7 +676,7 @@ int iopx_pow_solve_poseidon_bn128(const iopx_poseidon_params *params, const uint
  * algorithmic_bytes = elements swept x 24 x (read + write) summed over the launches, 0 for kernels that do not report it). */
 /* Options: named integers that select a prover schedule or a tile geometry (the names are listed in DESIGN.md).  A name's value is what
  * iopx_set_option gave it, else the environment variable of that name (read once per process, at the name's first lookup), else the built-in
- * default.  Schedule options (IOPX_HEAD_EVAL, IOPX_MERKLE_STREAM, IOPX_DEFER_ROOTS) are looked up per proof; tile geometries are latched by
+ * default.  Schedule options (IOPX_HEAD_EVAL, IOPX_GFX_HEAD_EVAL, IOPX_MERKLE_STREAM, IOPX_DEFER_ROOTS) are looked up per proof; tile geometries are latched by
  * their component at its first use. */
 int iopx_set_option(const char *name, int value);
 int iopx_clear_option(const char *name);
@@ -750,15 +756,15 @@ int iopx_fp3_modulus(uint64_t *out);
 #define IOPX_FIELD_GF192 0
 #define IOPX_FIELD_EDWARDS_FR 1
 #define IOPX_FIELD_ALT_BN128_FR 2   /* Aurora instances (BLAKE2b or Poseidon: iopx_aurora_prove_hashed) and the FRI-only SNARK; no Fractal, no distributed prover */
-/* libff::gf64 (3 stays unknown): Aurora instances and the FRI-only SNARK on one GPU with BLAKE2b, in the reference's schedule (no head evaluation, whatever
- * IOPX_HEAD_EVAL says; re-extensions through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf64: a communicator (the _dist forms),
+/* libff::gf64 (3 stays unknown): Aurora instances and the FRI-only SNARK on one GPU with BLAKE2b, in the reference's schedule unless the option IOPX_GFX_HEAD_EVAL is non-zero (default 0:
+ * no head evaluation, whatever IOPX_HEAD_EVAL says; non-zero: the head route where IOPX_HEAD_EVAL allows it, same bytes; libiop_amd_head.h.  Re-extensions through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf64: a communicator (the _dist forms),
  * iopx_fractal_index / iopx_fractal_prove, a Poseidon hash, and a codeword domain of more than 2^IOPX_GF64_MAX_DOMAIN_DIM points — the bound of the gf64
  * transform entries — which is checked from the parameters before any device work. */
 #define IOPX_FIELD_GF64 4
 #define IOPX_GF64_MAX_DOMAIN_DIM 40
 /* libff::gf128: Aurora instances from CSR matrices (iopx_aurora_instance_create; iopx_aurora_prove, iopx_aurora_prove_hashed with IOPX_HASH_BLAKE2B,
- * iopx_aurora_instance_warm) and the FRI-only SNARK on one GPU, 2 words per element, in the reference's schedule (no head evaluation; re-extensions
- * through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, iopx_fractal_index /
+ * iopx_aurora_instance_warm) and the FRI-only SNARK on one GPU, 2 words per element, in the reference's schedule (head evaluation only under the option
+ * IOPX_GFX_HEAD_EVAL, default 0: libiop_amd_head.h; re-extensions through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, iopx_fractal_index /
  * iopx_fractal_prove, a codeword domain of more than 2^IOPX_GFX_MAX_DOMAIN_DIM points (checked from the parameters before any device work), and
  * iopx_aurora_example_instance_create (the synthetic instance is not generated over this field: build it as CSR matrices plus an assignment). */
 #define IOPX_FIELD_GF128 5

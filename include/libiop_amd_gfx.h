@@ -18,7 +18,7 @@
  * other launch in 64-bit words (the profile reports the latter under the kernel's name + "_w64").  Codeword domains of dimension above 40 are
  * refused.  iopx_FIELD_add_dev, iopx_FIELD_mul_dev and iopx_FIELD_inv_dev of libiop_amd.h are the sums, products and inverses.  Aurora over these
  * fields runs through these entries from the Python prover (libiop_amd.domains.GF128AuroraOps, GF256AuroraOps) and from the native one
- * (IOPX_FIELD_GF128, IOPX_FIELD_GF256); Fractal, a distributed prover and head evaluation are not built (the fused re-extensions: libiop_amd_batch.h).
+ * (IOPX_FIELD_GF128, IOPX_FIELD_GF256); Fractal and a distributed prover are not built (the fused re-extensions: libiop_amd_batch.h; head evaluation, behind an option: libiop_amd_head.h).
  *
  * The Python binding lists these names in libiop_amd.GFX_OPS_SYMBOLS, beside EXPORTED_SYMBOLS for the declarations of libiop_amd.h. */
 #ifndef LIBIOP_AMD_GFX_H

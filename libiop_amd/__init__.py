@@ -97,6 +97,11 @@ GFX_OPS_SYMBOLS = [pattern % field for field in ("gf128", "gf256")
 BATCH_SYMBOLS = [pattern % field for field in ("gf64", "gf128", "gf256")
                  for pattern in ("iopx_add_ifft_%s_batch_dev", "iopx_add_lde_%s_batch_dev", "iopx_add_reextend_%s_batch_dev", "iopx_add_reextend_lde_%s_batch_dev")]
 
+# the declarations of include/libiop_amd_head.h (which libiop_amd.h includes): what head evaluation needs over gf64, gf128 and gf256 (the pointwise
+# division by Z_S, the host's Z_S(x), the two-group fused re-extension), one parameterised text for the three fields
+HEAD_SYMBOLS = [pattern % field for field in ("gf64", "gf128", "gf256")
+                for pattern in ("iopx_div_by_vanishing_%s_dev", "iopx_%s_vanishing_host", "iopx_add_reextend2_%s_batch_dev")]
+
 
 class NoDeviceError(RuntimeError):
     pass
@@ -332,6 +337,12 @@ class Library:
         c.iopx_add_reextend_gf192_batch_dev.argtypes = [_vp, _sz, _u64p, _sz, _sz, _u64p, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
         c.iopx_add_reextend_lde_gf192_batch_dev.argtypes = [_vp, _sz, ctypes.POINTER(_vp), _sz, _sz, _u64p, _sz, _sz, _u64p, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
         for name in ("add_ifft_%s_batch_dev", "add_lde_%s_batch_dev", "add_reextend_%s_batch_dev", "add_reextend_lde_%s_batch_dev"):
+            for field in ("gf64", "gf128", "gf256"):
+                getattr(c, "iopx_" + name % field).argtypes = list(getattr(c, "iopx_" + name % "gf192").argtypes)
+        # what head evaluation needs: the prototypes of the gf192 entries, for the three fields of libiop_amd_head.h
+        c.iopx_div_by_vanishing_gf192_dev.argtypes = [_vp, _u64p, _sz, _u64p, _sz, _u64p, _vp]
+        c.iopx_add_reextend2_gf192_batch_dev.argtypes = [_vp, _sz, _u64p, _vp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
+        for name in ("div_by_vanishing_%s_dev", "%s_vanishing_host", "add_reextend2_%s_batch_dev"):
             for field in ("gf64", "gf128", "gf256"):
                 getattr(c, "iopx_" + name % field).argtypes = list(getattr(c, "iopx_" + name % "gf192").argtypes)
 
@@ -1268,15 +1279,24 @@ class Library:
         self._check(fn(_vp(d_evals), int(batch), basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim), es.ctypes.data_as(_u64p),
                        shift.ctypes.data_as(_u64p), int(coset_begin), int(coset_count), cout))
 
-    def additive_reextend2_batch_dev(self, d_evals_a, batch_a, eval_shift_a, d_evals_b, batch_b, eval_shift_b, basis, d_dim, shift, coset_begin, coset_count, d_outs):
+    def additive_reextend2_batch_dev(self, d_evals_a, batch_a, eval_shift_a, d_evals_b, batch_b, eval_shift_b, basis, d_dim, shift, coset_begin, coset_count, d_outs, words=3):
         """additive_reextend_batch_dev for two groups of vectors over cosets of the same span with different shifts, in one batch: d_outs holds
         group a's codewords first, then group b's."""
-        basis, shift, ea, eb = _as_u64(basis), _as_u64(shift), _as_u64(eval_shift_a), _as_u64(eval_shift_b)
-        self.c.iopx_add_reextend2_gf192_batch_dev.argtypes = [_vp, _sz, _u64p, _vp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
+        basis, shift, ea, eb = _as_u64(basis, words), _as_u64(shift, words), _as_u64(eval_shift_a, words), _as_u64(eval_shift_b, words)
         cout = (_vp * len(d_outs))(*d_outs)
-        self._check(self.c.iopx_add_reextend2_gf192_batch_dev(_vp(d_evals_a), int(batch_a), ea.ctypes.data_as(_u64p), _vp(d_evals_b), int(batch_b), eb.ctypes.data_as(_u64p),
-                                                              basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim), shift.ctypes.data_as(_u64p), int(coset_begin),
-                                                              int(coset_count), cout))
+        fn = (self.c.iopx_add_reextend2_gf64_batch_dev if words == 1 else self.c.iopx_add_reextend2_gf128_batch_dev if words == 2
+              else self.c.iopx_add_reextend2_gf256_batch_dev if words == 4 else self.c.iopx_add_reextend2_gf192_batch_dev)
+        self._check(fn(_vp(d_evals_a), int(batch_a), ea.ctypes.data_as(_u64p), _vp(d_evals_b), int(batch_b), eb.ctypes.data_as(_u64p),
+                       basis.ctypes.data_as(_u64p), basis.shape[0], int(d_dim), shift.ctypes.data_as(_u64p), int(coset_begin), int(coset_count), cout))
+
+    def div_by_vanishing(self, d_in, basis, shift, sub_dim, sub_shift, d_out, words=3):
+        """d_out[j] = d_in[j] / Z_S(x_j) over span(basis) + shift, S = span(basis[:sub_dim]) + sub_shift (d_in, d_out: device pointers; d_out may be
+        d_in): one product per element.  (Not named *_dev: tests/memory_contract_cases.py keeps one list of rows for the methods of that suffix and is
+        closed; this entry's memory-contract rows are tests/test_gfx_head_memory.py's.)"""
+        basis, shift, ss = _as_u64(basis, words), _as_u64(shift, words), _as_u64(sub_shift, words)
+        fn = (self.c.iopx_div_by_vanishing_gf64_dev if words == 1 else self.c.iopx_div_by_vanishing_gf128_dev if words == 2
+              else self.c.iopx_div_by_vanishing_gf256_dev if words == 4 else self.c.iopx_div_by_vanishing_gf192_dev)
+        self._check(fn(_vp(d_in), basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), int(sub_dim), ss.ctypes.data_as(_u64p), _vp(d_out)))
 
     def additive_reextend_lde_batch_dev(self, d_evals, batch, d_coeffs, n_coeffs, basis, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs, words=3):
         """additive_reextend_batch_dev plus, in the same batch, the codewords of the polynomials at device pointers d_coeffs (n_coeffs
@@ -1427,6 +1447,17 @@ class Library:
         value, lin = np.zeros(3, dtype=np.uint64), np.zeros(3, dtype=np.uint64)
         self._check(self.c.iopx_gf192_vanishing_host(basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), x.ctypes.data_as(_u64p),
                                                      value.ctypes.data_as(_u64p), lin.ctypes.data_as(_u64p)))
+        return value, lin
+
+    def vanishing_host(self, basis, shift, x, words=3, want_value=True, want_linear_coefficient=True):
+        """(Z_S(x), Z_S's linear coefficient) for S = span(basis) + shift, on the host; an output that is not wanted is passed as NULL and returned as None."""
+        basis, shift, x = _as_u64(basis, words), _as_u64(shift, words), _as_u64(x, words)
+        value = np.zeros(words, dtype=np.uint64) if want_value else None
+        lin = np.zeros(words, dtype=np.uint64) if want_linear_coefficient else None
+        fn = (self.c.iopx_gf64_vanishing_host if words == 1 else self.c.iopx_gf128_vanishing_host if words == 2
+              else self.c.iopx_gf256_vanishing_host if words == 4 else self.c.iopx_gf192_vanishing_host)
+        self._check(fn(basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), x.ctypes.data_as(_u64p),
+                       value.ctypes.data_as(_u64p) if want_value else None, lin.ctypes.data_as(_u64p) if want_linear_coefficient else None))
         return value, lin
 
     def gf192_inverse_host(self, x):

@@ -115,7 +115,6 @@ device_vector<FieldT> IFFT(const device_vector<FieldT> &evals, const field_subse
 // FFT_over_field_subset(IFFT_over_field_subset(v, H), L) for `batch` vectors stored back to back.  When H is spanned by the first basis
 // vectors of L the coefficient form is skipped (the field's add_reextend_batch entry); otherwise the two transforms run one after the other.
 // H_is_first_coset: H is the first coset of its span inside L (same shift), so the first |H| entries of each codeword are the input itself.
-// A subspace-only field (gf64, gf128, gf256) has this entry and the one of FFT_and_reextend_packed, not the two-group form between them: there its two groups run one after the other.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &packed, std::size_t batch, const field_subset<FieldT> &H,
                                                    const field_subset<FieldT> &L, bool H_is_first_coset = false)
@@ -143,13 +142,13 @@ std::vector<device_vector<FieldT>> reextend_packed(const device_vector<FieldT> &
 }
 
 // reextend_packed(a, batch_a, Ha, L) followed by reextend_packed(b, batch_b, Hb, L) in one call, when Ha and Hb are cosets of the same span of L's first
-// basis vectors (iopx_add_reextend2_gf192_batch_dev: the forward passes and the shared last pass run over all the vectors); the separate calls otherwise.
+// basis vectors (the field's add_reextend2_batch entry: the forward passes and the shared last pass run over all the vectors); the separate calls otherwise.
 template<typename FieldT>
 std::vector<device_vector<FieldT>> reextend2_packed(const device_vector<FieldT> &a, std::size_t batch_a, const field_subset<FieldT> &Ha, const device_vector<FieldT> &b,
                                                     std::size_t batch_b, const field_subset<FieldT> &Hb, const field_subset<FieldT> &L)
 {
     std::vector<device_vector<FieldT>> outs;
-    bool together = !detail::binary_only<FieldT>() && additive(L) && additive(Ha) && additive(Hb) && Ha.dimension() == Hb.dimension() && Ha.dimension() > 0 && Ha.dimension() <= L.dimension();
+    bool together = additive(L) && additive(Ha) && additive(Hb) && Ha.dimension() == Hb.dimension() && Ha.dimension() > 0 && Ha.dimension() <= L.dimension();
     for (std::size_t i = 0; together && i < Ha.dimension(); ++i)
         together = std::memcmp(&Ha.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0 && std::memcmp(&Hb.basis()[i], &L.basis()[i], sizeof(FieldT)) == 0;
     if (!together) {
@@ -160,8 +159,8 @@ std::vector<device_vector<FieldT>> reextend2_packed(const device_vector<FieldT> 
     const auto range = dist::coset_range(L, Ha.dimension());
     std::vector<uint64_t *> ptrs;
     for (std::size_t k = 0; k < batch_a + batch_b; ++k) { outs.emplace_back(range.second << Ha.dimension()); ptrs.push_back(outs.back().words()); }
-    check(iopx_add_reextend2_gf192_batch_dev(a.words(), batch_a, shift_words(Ha), b.words(), batch_b, shift_words(Hb), basis_words(L), L.dimension(), Ha.dimension(),
-                                             shift_words(L), range.first, range.second, ptrs.data()));
+    check(ops::add_reextend2_batch<field_of<FieldT>>(a.words(), batch_a, shift_words(Ha), b.words(), batch_b, shift_words(Hb), basis_words(L), L.dimension(), Ha.dimension(),
+                                                     shift_words(L), range.first, range.second, ptrs.data()));
     return outs;
 }
 
@@ -248,6 +247,17 @@ device_vector<FieldT> IFFT_of_known_degree(const device_vector<FieldT> &evals, s
     return out;
 }
 
+// f_(i+1) = fold(f_i, x_i) over a whole domain, into `out` (|D| / coset_size elements, possibly a slice of a packed batch)
+template<typename FieldT>
+void fold_into(const device_vector<FieldT> &f, const field_subset<FieldT> &D, std::size_t coset_size, const FieldT &x_i, const device_vector<FieldT> &out)   // fri_aux.tcc:5-34
+{
+    require_whole(D);
+    if (D.distributed()) throw std::logic_error("fold_into: a distributed domain");
+    if (out.size() != D.num_elements() / coset_size) throw std::invalid_argument("fold_into: output size");
+    if (additive(D)) check(ops::fri_fold_add<field_of<FieldT>>(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    else check(field_entry<FieldT>(&P::fri_fold_mul, "fold")(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+}
+
 // Over a distributed domain the rank's cosets are whole (dist.hpp), so its part folds as the local sub-domain with the same x_i and is the
 // rank's part of f_(i+1); when the next domain is kept whole the parts are gathered.
 template<typename FieldT>
@@ -257,11 +267,9 @@ device_vector<FieldT> fold(const device_vector<FieldT> &f, const field_subset<Fi
         const device_vector<FieldT> part = fold<FieldT>(f, dist::local_domain(D_in), coset_size, x_i);
         return next_distributed ? part : dist::gather_layout<FieldT>(part, D_in.type());
     }
-    const field_subset<FieldT> &D = D_in;
-    require_whole(D);
-    device_vector<FieldT> out(D.num_elements() / coset_size);
-    if (additive(D)) check(ops::fri_fold_add<field_of<FieldT>>(f.words(), basis_words(D), D.dimension(), shift_words(D), coset_size, detail::words(&x_i), out.words()));
-    else check(field_entry<FieldT>(&P::fri_fold_mul, "fold")(f.words(), D.dimension(), gen_words(D), shift_words(D), coset_size, detail::words(&x_i), out.words()));
+    require_whole(D_in);
+    device_vector<FieldT> out(D_in.num_elements() / coset_size);
+    fold_into<FieldT>(f, D_in, coset_size, x_i, out);
     return out;
 }
 
@@ -324,12 +332,13 @@ inline bool head_evaluation_enabled()
 {
     return iopx_get_option("IOPX_HEAD_EVAL", 1) != 0;   // looked up per proof (iopx_set_option): tests and bench.py prove the same instance both ways
 }
-// ... for FieldT: a subspace-only field (gf64, gf128, gf256) always runs the reference's schedule, whatever the option says — its re-extensions have no fused form and its
-// pointwise division by Z_I no entry, so nothing of the head route is built over it
+// ... for FieldT: a subspace-only field (gf64, gf128, gf256) takes the head route only when IOPX_GFX_HEAD_EVAL is set as well (default 0, looked up per proof
+// like IOPX_HEAD_EVAL): the route is built over it (include/libiop_amd_head.h), its default schedule stays the reference's
 template<typename FieldT>
 bool head_evaluation()
 {
-    return !detail::binary_only<FieldT>() && head_evaluation_enabled();
+    if (detail::binary_only<FieldT>()) return head_evaluation_enabled() && iopx_get_option("IOPX_GFX_HEAD_EVAL", 0) != 0;
+    return head_evaluation_enabled();
 }
 template<typename FieldT>
 bool use_head(const field_subset<FieldT> &D, std::size_t count)
@@ -838,8 +847,7 @@ public:
             const field_subset<FieldT> V0 = dist::window_domain(whole, dist::window{ 0, 1, V_.num_elements() });
             const device_vector<FieldT> fw_prime_V0 = dev::reextend_packed<FieldT>(fw_prime_evals, 1, V_, V0)[0];
             const device_vector<FieldT> fw_V0(V0.num_elements());                            // Z_I is constant on the cosets of I: one product per element
-            check(iopx_div_by_vanishing_gf192_dev(fw_prime_V0.words(), dev::basis_words(V0), V0.dimension(), dev::shift_words(V0), I_.dimension(), dev::shift_words(I_),
-                                                  fw_V0.words()));
+            check(ops::div_by_vanishing<field_of<FieldT>>(dev::domain_words<FieldT>(V0), fw_prime_V0.words(), I_.dimension(), dev::shift_words(I_), fw_V0.words()));
             if (V0.dimension() == C_.dimension()) {
                 // one batch of four: at the pair bits where three polynomials leave a wavefront a quarter empty, four fill it
                 const std::vector<device_vector<FieldT>> four = dev::reextend2_packed<FieldT>(Mz, 3, C_, fw_V0, 1, V0, L_);
@@ -936,21 +944,35 @@ class FRI_protocol {                                                            
         for (std::size_t l = 0; l < poly_handles_.size(); ++l) {
             device_vector<FieldT> f0;
             if (!split || me == 0) { const dist::one_rank_section alone; f0 = IOP_.get_oracle_evaluations_over_window(poly_handles_[l], h0); }
+            // f_1 over the head of L^(1), one per interaction, back to back: ONE batched re-extension per LDT instance (at one interaction, the single call)
+            const std::size_t n1 = head / cs0;
+            device_vector<FieldT> f1_heads(interactive_repetitions_ * n1);
             for (std::size_t j = 0; j < interactive_repetitions_; ++j) {
                 const FieldT x_0 = IOP_.obtain_verifier_random_message(verifier_challenge_handles_[0][j])[0];
-                device_vector<FieldT> f1_head(head / cs0);                                         // f_1 over the head of L^(1)
-                if (!split || me == 0) { const dist::one_rank_section alone; f1_head = dev::fold<FieldT>(f0, D_h0, cs0, x_0); }
+                device_vector<FieldT> f1_head = f1_heads.slice(j * n1, n1);
+                if (!split || me == 0) { const dist::one_rank_section alone; dev::fold_into<FieldT>(f0, D_h0, cs0, x_0, f1_head); }
                 if (split) dist::broadcast<FieldT>(f1_head, 0);
-                by_interaction[j][l] = dev::reextend_packed<FieldT>(f1_head, 1, D_h1, L1)[0];     // subspaces: no coefficient form in between
+            }
+            {
+                std::vector<device_vector<FieldT>> extended = dev::reextend_packed<FieldT>(f1_heads, interactive_repetitions_, D_h1, L1);   // subspaces: no coefficient form in between
+                for (std::size_t j = 0; j < interactive_repetitions_; ++j) by_interaction[j][l] = extended[j];
             }
             if (!split || me == checker) {
                 const dist::one_rank_section alone;
                 const device_vector<FieldT> f0c = IOP_.get_oracle_evaluations_over_window(poly_handles_[l], c0);
+                // every interaction's fold of the window beside its extension's values, packed: ONE comparison per LDT instance
+                const std::size_t nc = D_c0.num_elements() / cs0;
+                const device_vector<FieldT> folded(interactive_repetitions_ * nc);
+                device_vector<FieldT> extended;
+                if (interactive_repetitions_ > 1) extended = device_vector<FieldT>(interactive_repetitions_ * nc);
                 for (std::size_t j = 0; j < interactive_repetitions_; ++j) {
                     const FieldT x_0 = IOP_.obtain_verifier_random_message(verifier_challenge_handles_[0][j])[0];
-                    const device_vector<FieldT> folded = dev::fold<FieldT>(f0c, D_c0, cs0, x_0), extended = dist::window_of<FieldT>(by_interaction[j][l], L1, c1);
-                    check(iopx_count_mismatch_dev(folded.data(), extended.data(), folded.size() * sizeof(FieldT), d_differ.data()));
+                    dev::fold_into<FieldT>(f0c, D_c0, cs0, x_0, folded.slice(j * nc, nc));
+                    const device_vector<FieldT> window = dist::window_of<FieldT>(by_interaction[j][l], L1, c1);
+                    if (interactive_repetitions_ > 1) extended.slice(j * nc, nc).copy_from(window);
+                    else extended = window;
                 }
+                check(iopx_count_mismatch_dev(folded.data(), extended.data(), folded.size() * sizeof(FieldT), d_differ.data()));
             }
         }
         if (split) check(iopx_comm_all_reduce_u64_dev(dist::ctx().comm, d_differ.data(), 1, IOPX_COMM_SUM));

@@ -13,7 +13,7 @@ namespace libiop_amd {
 
 // ---- host scalars of FieldT (per-proof constants only) --------------------------------------------------------------------------
 // One body for every field, written against the table of field_ops.hpp: gf192 keeps its branches (xor, the subspace forms of Z_S),
-// everything else is the field's entry.  A size / kind the table does not have fails to compile.
+// everything else is the field's entry (Z_S on the host included).  A size / kind the table does not have fails to compile.
 template<typename FieldT>
 struct field_host {
     typedef ops::field<sizeof(FieldT), field_kind<FieldT>::type == affine_subspace_type> table;
@@ -51,15 +51,18 @@ struct field_host {
     }
     static FieldT neg(const FieldT &a) { return sub(zero(), a); }
     static FieldT inverse(const FieldT &a) { uint64_t w[WORDS]; check(entry(&P::host_inverse, "inverse")(detail::words(&a), w)); return from_words(w); }
+    // Over gf64, gf128 and gf256 only the head route asks for Z_S on the host, and that route sits behind IOPX_GFX_HEAD_EVAL: with the option unset the two
+    // subspace forms below are refused as before the route existed (nothing observable changes); with it set they go through the field's vanishing_host slot
+    static bool subspace_host_forms() { return WORDS == 3 || iopx_get_option("IOPX_GFX_HEAD_EVAL", 0) != 0; }
     // Z_S(x) for the domain S (vanishing_polynomial::evaluation_at_point): the linearized polynomial of the subspace through the
     // library's host helper / x^|S| - shift^|S| (vanishing_polynomial.tcc:14-25)
     static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
-            if (WORDS != 3) ops::missing("vanishing_eval", table::vec->name);               // gf64, gf128, gf256: no host form of Z_S (only the head route and Fractal ask)
+            if (!subspace_host_forms()) ops::missing("vanishing_eval", table::vec->name);
             uint64_t w[WORDS];
             const FieldT shift = S.shift();
-            check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), w, nullptr));
+            check(entry(&ops::subspace_ops::vanishing_host, "vanishing_eval")(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), w, nullptr));
             return from_words(w);
         }
         return sub(pow(x, S.num_elements()), pow(S.shift(), S.num_elements()));
@@ -68,10 +71,10 @@ struct field_host {
     static FieldT vanishing_derivative(const field_subset<FieldT> &S, const FieldT &x)
     {
         if (S.type() == affine_subspace_type) {
-            if (WORDS != 3) ops::missing("vanishing_derivative", table::vec->name);
+            if (!subspace_host_forms()) ops::missing("vanishing_derivative", table::vec->name);
             uint64_t w[WORDS];
             const FieldT shift = S.shift();
-            check(iopx_gf192_vanishing_host(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), nullptr, w));
+            check(entry(&ops::subspace_ops::vanishing_host, "vanishing_derivative")(detail::words(S.basis().data()), S.dimension(), detail::words(&shift), detail::words(&x), nullptr, w));
             return from_words(w);
         }
         return mul(from_uint(S.num_elements()), pow(x, S.num_elements() - 1));

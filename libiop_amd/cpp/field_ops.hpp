@@ -45,6 +45,9 @@ struct subspace_ops {
     // several vectors over one domain in every launch, and the fused re-extension (IFFT over H, FFT over L, no coefficient form in between)
     decltype(&iopx_add_ifft_gf192_batch_dev) add_ifft_batch; decltype(&iopx_add_lde_gf192_batch_dev) add_lde_batch;
     decltype(&iopx_add_reextend_gf192_batch_dev) add_reextend_batch; decltype(&iopx_add_reextend_lde_gf192_batch_dev) add_reextend_lde_batch;
+    // what head evaluation needs: the pointwise division by Z_S, the two-group fused re-extension, Z_S(x) on the host
+    decltype(&iopx_div_by_vanishing_gf192_dev) div_by_vanishing; decltype(&iopx_add_reextend2_gf192_batch_dev) add_reextend2_batch;
+    decltype(&iopx_gf192_vanishing_host) vanishing_host;
 };
 
 // the slots in the order of the declarations above, line for line
@@ -83,6 +86,8 @@ inline constexpr subspace_ops gf192_subspace = {
     iopx_vanishing_evals_gf192_dev, iopx_rational_sumcheck_constraint_gf192_dev,
     iopx_add_ifft_gf192_batch_dev, iopx_add_lde_gf192_batch_dev,
     iopx_add_reextend_gf192_batch_dev, iopx_add_reextend_lde_gf192_batch_dev,
+    iopx_div_by_vanishing_gf192_dev, iopx_add_reextend2_gf192_batch_dev,
+    iopx_gf192_vanishing_host,
 };
 inline constexpr subspace_ops gf64_subspace = {
     iopx_add_fft_gf64_dev, iopx_add_lde_gf64_dev, iopx_add_ifft_gf64_dev,
@@ -92,6 +97,8 @@ inline constexpr subspace_ops gf64_subspace = {
     nullptr, nullptr,
     iopx_add_ifft_gf64_batch_dev, iopx_add_lde_gf64_batch_dev,
     iopx_add_reextend_gf64_batch_dev, iopx_add_reextend_lde_gf64_batch_dev,
+    iopx_div_by_vanishing_gf64_dev, iopx_add_reextend2_gf64_batch_dev,
+    iopx_gf64_vanishing_host,
 };
 inline constexpr subspace_ops gf128_subspace = {
     iopx_add_fft_gf128_dev, iopx_add_lde_gf128_dev, iopx_add_ifft_gf128_dev,
@@ -101,6 +108,8 @@ inline constexpr subspace_ops gf128_subspace = {
     nullptr, nullptr,
     iopx_add_ifft_gf128_batch_dev, iopx_add_lde_gf128_batch_dev,
     iopx_add_reextend_gf128_batch_dev, iopx_add_reextend_lde_gf128_batch_dev,
+    iopx_div_by_vanishing_gf128_dev, iopx_add_reextend2_gf128_batch_dev,
+    iopx_gf128_vanishing_host,
 };
 inline constexpr subspace_ops gf256_subspace = {
     iopx_add_fft_gf256_dev, iopx_add_lde_gf256_dev, iopx_add_ifft_gf256_dev,
@@ -110,6 +119,8 @@ inline constexpr subspace_ops gf256_subspace = {
     nullptr, nullptr,
     iopx_add_ifft_gf256_batch_dev, iopx_add_lde_gf256_batch_dev,
     iopx_add_reextend_gf256_batch_dev, iopx_add_reextend_lde_gf256_batch_dev,
+    iopx_div_by_vanishing_gf256_dev, iopx_add_reextend2_gf256_batch_dev,
+    iopx_gf256_vanishing_host,
 };
 inline constexpr prime_field_ops edwards_Fr = {
     { "edwards Fr", 180, true,
@@ -222,6 +233,25 @@ template<class F> inline int add_reextend_lde_batch(const uint64_t *d_evals, std
 {
     return entry<F>(&subspace_ops::add_reextend_lde_batch, "add_reextend_lde_batch")(d_evals, batch, d_coeffs, n_coeffs, n_polys, basis, m, d_dim, eval_shift, shift, coset_begin,
                                                                                      coset_count, d_outs);
+}
+template<class F> inline int add_reextend2_batch(const uint64_t *d_evals_a, std::size_t batch_a, const uint64_t *eval_shift_a, const uint64_t *d_evals_b, std::size_t batch_b,
+                                                 const uint64_t *eval_shift_b, const uint64_t *basis, std::size_t m, std::size_t d_dim, const uint64_t *shift,
+                                                 std::size_t coset_begin, std::size_t coset_count, uint64_t *const *d_outs)
+{
+    return entry<F>(&subspace_ops::add_reextend2_batch, "add_reextend2_batch")(d_evals_a, batch_a, eval_shift_a, d_evals_b, batch_b, eval_shift_b, basis, m, d_dim, shift,
+                                                                               coset_begin, coset_count, d_outs);
+}
+// d_out[j] = d_in[j] / Z_S(x_j) over D, S = span(D.basis[0..sub_dim)) + sub_shift
+template<class F> inline int div_by_vanishing(const domain &D, const uint64_t *d_in, std::size_t sub_dim, const uint64_t *sub_shift, uint64_t *d_out)
+{
+    if (!subspace<F>(D, "div_by_vanishing")) missing("div_by_vanishing (multiplicative coset)", F::vec->name);
+    return entry<F>(&subspace_ops::div_by_vanishing, "div_by_vanishing")(d_in, D.basis, D.dim, D.shift, sub_dim, sub_shift, d_out);
+}
+// Z_S(x) and Z_S's linear coefficient on the host (either output may be null)
+template<class F> inline int vanishing_host(const domain &S, const uint64_t *x, uint64_t *value_out, uint64_t *linear_coefficient_out)
+{
+    if (!subspace<F>(S, "vanishing_host")) missing("vanishing_host (multiplicative coset)", F::vec->name);
+    return entry<F>(&subspace_ops::vanishing_host, "vanishing_host")(S.basis, S.dim, S.shift, x, value_out, linear_coefficient_out);
 }
 template<class F> inline int fri_fold_add(const uint64_t *d_f, const uint64_t *basis, std::size_t m, const uint64_t *shift, std::size_t coset_size, const uint64_t *x_i, uint64_t *d_next)
 {

@@ -107,6 +107,14 @@ int iopx_add_reextend_lde_gf64_batch_dev(const uint64_t *d_evals, size_t batch, 
     return x_add_reextend_lde_batch_dev<Elem64>(d_evals, batch, d_coeffs, n_coeffs, n_polys, basis, m, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs);
 }
 
+// the two-group fused re-extension (include/libiop_amd_head.h)
+int iopx_add_reextend2_gf64_batch_dev(const uint64_t *d_evals_a, size_t batch_a, const uint64_t *eval_shift_a, const uint64_t *d_evals_b, size_t batch_b,
+                                     const uint64_t *eval_shift_b, const uint64_t *basis, size_t m, size_t d_dim, const uint64_t *shift,
+                                     size_t coset_begin, size_t coset_count, uint64_t *const *d_outs)
+{
+    return x_add_reextend2_batch_dev<Elem64>(d_evals_a, batch_a, eval_shift_a, d_evals_b, batch_b, eval_shift_b, basis, m, d_dim, shift, coset_begin, coset_count, d_outs);
+}
+
 int iopx_add_fft_gf64(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                       const uint64_t *shift, uint64_t *out)
 {

@@ -9,6 +9,8 @@
 //   iopx_fz_gf64_dev                               fz_virtual_oracle::evaluated_contents (r1cs_rs_iop.tcc:181-222)
 //   iopx_sumcheck_g_gf64_dev                       sumcheck_g_oracle::evaluated_contents (sumcheck.tcc:58-119)
 //   iopx_poly_div_vanishing_gf64_dev               polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371)
+//   iopx_div_by_vanishing_gf64_dev,                the head route's pointwise division by Z_S and the host's Z_S(x) (include/libiop_amd_head.h)
+//   iopx_gf64_vanishing_host
 //
 // An element is 8 bytes and a product ~0.13k VALU ops (gf64_dev.h): every kernel here is bound by its HBM passes, so each one reads every
 // input once and writes the output once, in a grid-stride loop.  Where the position of an element does not enter the addressing beyond
@@ -33,6 +35,14 @@ static int ops64_grid(size_t work)
     size_t g = (work + 255) / 256;
     if (g > 16384) g = 16384;
     return (int)(g ? g : 1);
+}
+
+// ... under the option IOPX_GF64_OPS_MAX_BLOCKS (default: the cap above; looked up per launch; a test helper as gfx_ops.h's IOPX_GFX_OPS_MAX_BLOCKS:
+// a small cap sends a grid-stride loop round again at a few thousand elements)
+static int ops64_grid_capped(size_t work)
+{
+    const int g = ops64_grid(work), cap = opt_range("IOPX_GF64_OPS_MAX_BLOCKS", 16384, 1, 16384);
+    return g < cap ? g : cap;
 }
 
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
@@ -207,6 +217,21 @@ __global__ void __launch_bounds__(256) k64_rowcheck(uint64_t *out, const uint64_
     }
 }
 
+// out[x] = in[x] / Z_S(x): Z_S is constant on the cosets of S, the blocks position >> s of the domain; one product per element, out may be in
+template<int V>
+__global__ void __launch_bounds__(256) k64_div_by_vanishing(uint64_t *out, const uint64_t *in, const uint64_t *zinv, int s, size_t n)
+{
+    OPS64_LOOP(V, j, n) {
+        uint64_t a[V];
+        ld64<V>(a, in, j, n);
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            if (j + e < n) a[e] = mul64(a[e], zinv[(j + e) >> s]);
+        }
+        st64<V>(out, j, n, a);
+    }
+}
+
 // result[x] = fw(x) Z_I(x) + f_1v(x)
 template<int V>
 __global__ void __launch_bounds__(256) k64_fz(uint64_t *out, const uint64_t *fw, const uint64_t *f1v, const uint64_t *tab, int m, size_t n)
@@ -310,11 +335,13 @@ static std::vector<uint64_t> table_key64(const uint64_t *basis, size_t m, const 
 }
 
 // 1 / Z_H on each coset of H = span(basis[0..h)) + constraint_shift inside span(basis[0..m)) + shift (virtual_oracles.hip): evaluated on the
-// host, inverted with Montgomery's trick (one field inversion), kept on the device per pair of domains
-static int vanishing_inverse_table64(const uint64_t *basis, size_t m, const uint64_t *shift, size_t h, const uint64_t *constraint_shift, TmpBuf &dz)
+// host, inverted with Montgomery's trick (one field inversion), kept on the device per pair of domains and caller (`tag`; `meets`: the caller's
+// refusal of a domain on which Z_H has a zero)
+static int vanishing_inverse_table64(const uint64_t *basis, size_t m, const uint64_t *shift, size_t h, const uint64_t *constraint_shift, TmpBuf &dz,
+                                     uint64_t tag = 0x3634726f77 /* "64row" */, const char *meets = "the codeword domain intersects the constraint domain")
 {
     const size_t cosets = (size_t)1 << (m - h);
-    return cached_domain_table(table_key64(basis, m, shift, nullptr, h, constraint_shift, 0x3634726f77), [&](std::vector<uint64_t> &zinv) -> int {   // "64row"
+    return cached_domain_table(table_key64(basis, m, shift, nullptr, h, constraint_shift, tag), [&](std::vector<uint64_t> &zinv) -> int {
         const std::vector<hgf64> b = host_elems64(basis, m);
         const SubspacePoly64 lin(b.data(), h);
         const hgf64 z_shift = lin.eval(hgf64(constraint_shift[0]));
@@ -324,7 +351,7 @@ static int vanishing_inverse_table64(const uint64_t *basis, size_t m, const uint
             hgf64 x(shift[0]);                                  // first element of the coset: index c << h (utils.tcc:8-30)
             for (size_t k = h; k < m; ++k) if ((c >> (k - h)) & 1) x += b[k];
             z[c] = lin.eval(x) + z_shift;
-            if (z[c].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "the codeword domain intersects the constraint domain");
+            if (z[c].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "%s", meets);
             acc = acc * z[c];
             prefix[c] = acc;
         }
@@ -623,6 +650,41 @@ int iopx_poly_div_vanishing_gf64_dev(const uint64_t *d_poly, size_t n_coeffs, co
         return t;
     };
     return run_division64(d_poly + N, M, min_off, d_quotient, terms_of_pass);
+}
+
+// d_out[j] = d_in[j] / Z_S(x_j) over span(basis[0..m)) + shift, S = span(basis[0..sub_dim)) + sub_shift (d_out may be d_in).  The profile reports the
+// one-element form (a vector that is not 16-byte aligned) as k64_div_by_vanishing_w64.
+int iopx_div_by_vanishing_gf64_dev(const uint64_t *d_in, const uint64_t *basis, size_t m, const uint64_t *shift, size_t sub_dim, const uint64_t *sub_shift,
+                                   uint64_t *d_out)
+{
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!d_in || !d_out || (m > 0 && !basis) || !shift || !sub_shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (sub_dim > m || m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "the vanishing set must be spanned by a prefix of the domain's basis");
+    TmpBuf dz;
+    if ((rc = vanishing_inverse_table64(basis, m, shift, sub_dim, sub_shift, dz, 0x3634646976 /* "64div" */, "the domain intersects the vanishing set")) != IOPX_OK) return rc;
+    const size_t n = (size_t)1 << m;
+    if (aligned16(d_in) && aligned16(d_out)) {
+        ProfScope ps_("k64_div_by_vanishing", 2 * n * 8);
+        hipLaunchKernelGGL(k64_div_by_vanishing<2>, dim3(ops64_grid_capped((n + 1) / 2)), dim3(256), 0, stream(), d_out, d_in, (const uint64_t *)dz.u64(), (int)sub_dim, n);
+    } else {
+        ProfScope ps_("k64_div_by_vanishing_w64", 2 * n * 8);
+        hipLaunchKernelGGL(k64_div_by_vanishing<1>, dim3(ops64_grid_capped(n)), dim3(256), 0, stream(), d_out, d_in, (const uint64_t *)dz.u64(), (int)sub_dim, n);
+    }
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// Z_S(x) and Z_S's linear coefficient (its formal derivative, vanishing_polynomial.tcc:55-74) for S = span(basis) + shift: host only
+int iopx_gf64_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *shift, const uint64_t *x, uint64_t *value_out, uint64_t *linear_coefficient_out)
+{
+    if ((dim > 0 && !basis) || !shift || !x) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (dim > 63) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
+    const std::vector<hgf64> b = host_elems64(basis, dim);
+    const SubspacePoly64 lin(b.data(), dim);
+    if (value_out) value_out[0] = (lin.eval(hgf64(x[0])) + lin.eval(hgf64(shift[0]))).v;
+    if (linear_coefficient_out) linear_coefficient_out[0] = lin.coeff[0].v;
+    return IOPX_OK;
 }
 
 } // extern "C"

@@ -1261,6 +1261,57 @@ static int x_add_reextend_batch_dev(const uint64_t *d_evals, size_t batch, const
     return x_add_reextend_lde_batch_dev<F>(d_evals, batch, nullptr, 0, 0, basis, m, d_dim, eval_shift, shift, coset_begin, coset_count, d_outs);
 }
 
+// Two groups of evaluation vectors over cosets of the same span with different shifts (f_Az, f_Bz, f_Cz over H and f_w over the first coset of V inside
+// L), re-extended in ONE batch: each group's butterflies are undone with its own recursed shift, every forward launch runs over all batch_a + batch_b
+// vectors; no phase-1 launch in either direction.  d_outs: group a's codewords, then group b's; bit for bit the two one-group calls'.  The three
+// recursed shifts travel in one table, each section starting at an even word: rs_a, rs_b, then rs_L with L's coset basis behind it.
+template<class F>
+static int x_add_reextend2_batch_dev(const uint64_t *d_evals_a, size_t batch_a, const uint64_t *eval_shift_a, const uint64_t *d_evals_b, size_t batch_b,
+                                     const uint64_t *eval_shift_b, const uint64_t *basis, size_t m, size_t d_dim, const uint64_t *shift, size_t coset_begin,
+                                     size_t coset_count, uint64_t *const *d_outs)
+{
+    typedef typename F::host H;
+    const size_t EB = sizeof(typename F::mem);
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    rc = check_basis_args_x(basis, m, shift);
+    if (rc != IOPX_OK) return rc;
+    if (!d_evals_a || !d_evals_b || !d_outs || !eval_shift_a || !eval_shift_b) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    if (batch_a == 0 || batch_b == 0 || batch_a > 65535 || batch_b > 65535 || batch_a + batch_b > 65535)
+        return fail(IOPX_ERR_INVALID_ARGUMENT, "batch sizes %zu + %zu outside 1..65535", batch_a, batch_b);
+    if (d_dim == 0 || d_dim > m) return fail(IOPX_ERR_INVALID_ARGUMENT, "the evaluation domains must be spanned by the first basis vectors of the codeword domain");
+    const size_t total = batch_a + batch_b;
+    for (size_t k = 0; k < total; ++k) if (!d_outs[k]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null buffer");
+    const int d = (int)d_dim, nhi = (int)m - d;
+    const size_t all_cosets = (size_t)1 << nhi, nd = (size_t)1 << d;
+    if (coset_count == 0 || coset_begin >= all_cosets || coset_count > all_cosets - coset_begin)
+        return fail(IOPX_ERR_INVALID_ARGUMENT, "coset range [%zu, +%zu) outside the %zu cosets of the transform", coset_begin, coset_count, all_cosets);
+    std::shared_ptr<AddPlanX<F>> pl;
+    rc = get_plan_x<F>(basis, d, &pl);
+    if (rc != IOPX_OK) return rc;
+    TmpBuf drs, dptrs, work;
+    const size_t section = ((size_t)d * F::W + 1) & ~(size_t)1;
+    {
+        std::vector<uint64_t> rs(2 * section + (size_t)(1 + nhi) * d * F::W, 0);
+        pl->recurse(H(eval_shift_a), rs.data());
+        pl->recurse(H(eval_shift_b), rs.data() + section);
+        pl->recurse(H(shift), rs.data() + 2 * section);
+        for (int v = 0; v < nhi; ++v) pl->recurse(H(basis + F::W * (size_t)(d + v)), rs.data() + 2 * section + (size_t)(1 + v) * d * F::W);
+        if ((rc = drs.alloc(rs.size() * 8)) != IOPX_OK) return rc;
+        if ((rc = upload(drs.p, rs.data(), rs.size() * 8)) != IOPX_OK) return rc;
+    }
+    bool ptrs_a16;
+    rc = upload_ptrs_x(d_outs, total, nullptr, 0, dptrs, &ptrs_a16);
+    if (rc != IOPX_OK) return rc;
+    rc = work.alloc(total * nd * EB);
+    if (rc != IOPX_OK) return rc;
+    rc = run_phase2_inv_batch_x(*pl, d_evals_a, work.u64(), drs.u64(), batch_a);                                       // each group's butterflies undone: natural -> block order
+    if (rc != IOPX_OK) return rc;
+    rc = run_phase2_inv_batch_x(*pl, d_evals_b, work.u64() + F::W * batch_a * nd, drs.u64() + section, batch_b);
+    if (rc != IOPX_OK) return rc;
+    return run_phase2_fwd_batch_x(*pl, work.u64(), total, (const uint64_t *const *)dptrs.u64(), ptrs_a16, drs.u64() + 2 * section, nhi, coset_begin, coset_count);
+}
+
 template<class F>
 static int x_add_fft_host(const uint64_t *coeffs, size_t n_coeffs, const uint64_t *basis, size_t m,
                           const uint64_t *shift, uint64_t *out)

@@ -11,6 +11,7 @@
 //   x_fz_dev                                       fz_virtual_oracle::evaluated_contents (r1cs_rs_iop.tcc:181-222)
 //   x_sumcheck_g_dev                               sumcheck_g_oracle::evaluated_contents (sumcheck.tcc:58-119)
 //   x_poly_div_vanishing_dev                       polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371)
+//   x_div_by_vanishing_dev, x_vanishing_host       the head route's pointwise division by Z_S and the host's Z_S(x) (include/libiop_amd_head.h)
 //
 // One element per lane, in a grid-stride loop: every kernel reads each input once and writes the output once.  An element travels as F::mem
 // through F::load<A16> / F::store<A16>: the A16 instantiation (128-bit accesses) runs when every device pointer of the launch, the cached
@@ -169,6 +170,15 @@ __global__ void __launch_bounds__(256) kx_rowcheck(uint64_t *out, const uint64_t
     }
 }
 
+// out[x] = in[x] / Z_S(x): Z_S is constant on the cosets of S, the blocks position >> s of the domain; one product per element, out may be in
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_div_by_vanishing(uint64_t *out, const uint64_t *in, const uint64_t *zinv, int s, size_t n)
+{
+    OPSX_LOOP(j, n) {
+        F::template store<A16>(out, j, F::mul(F::template load<A16>(in, j), F::template load<A16>(zinv, j >> s)));
+    }
+}
+
 // result[x] = fw(x) Z_I(x) + f_1v(x)
 template<class F, bool A16>
 __global__ void __launch_bounds__(256) kx_fz(uint64_t *out, const uint64_t *fw, const uint64_t *f1v, const uint64_t *tab, int m, size_t n)
@@ -272,13 +282,15 @@ static std::vector<uint64_t> table_key_x(const uint64_t *basis, size_t m, const 
 }
 
 // 1 / Z_H on each coset of H = span(basis[0..h)) + constraint_shift inside span(basis[0..m)) + shift (virtual_oracles.hip): evaluated on the
-// host, inverted with Montgomery's trick (one field inversion), kept on the device per pair of domains
+// host, inverted with Montgomery's trick (one field inversion), kept on the device per pair of domains and caller (`kind`; `meets`: the caller's
+// refusal of a domain on which Z_H has a zero)
 template<class F>
-static int vanishing_inverse_table_x(const uint64_t *basis, size_t m, const uint64_t *shift, size_t h, const uint64_t *constraint_shift, TmpBuf &dz)
+static int vanishing_inverse_table_x(const uint64_t *basis, size_t m, const uint64_t *shift, size_t h, const uint64_t *constraint_shift, TmpBuf &dz,
+                                     uint64_t kind = 1, const char *meets = "the codeword domain intersects the constraint domain")
 {
     typedef typename F::host H;
     const size_t cosets = (size_t)1 << (m - h);
-    return cached_domain_table(table_key_x<F>(basis, m, shift, nullptr, h, constraint_shift, 1), [&](std::vector<uint64_t> &zinv) -> int {
+    return cached_domain_table(table_key_x<F>(basis, m, shift, nullptr, h, constraint_shift, kind), [&](std::vector<uint64_t> &zinv) -> int {
         const std::vector<H> b = host_elems_x<F>(basis, m);
         const SubspacePolyX<H> lin(b.data(), h);
         const H z_shift = lin.eval(H(constraint_shift));
@@ -288,7 +300,7 @@ static int vanishing_inverse_table_x(const uint64_t *basis, size_t m, const uint
             H x(shift);                                         // first element of the coset: index c << h (utils.tcc:8-30)
             for (size_t k = h; k < m; ++k) if ((c >> (k - h)) & 1) x += b[k];
             z[c] = lin.eval(x) + z_shift;
-            if (z[c].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "the codeword domain intersects the constraint domain");
+            if (z[c].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "%s", meets);
             acc = acc * z[c];
             prefix[c] = acc;
         }
@@ -567,6 +579,38 @@ static int x_poly_div_vanishing_dev(const uint64_t *d_poly, size_t n_coeffs, con
     return run_division_x<F>(d_poly + F::W * N, M, min_off, d_quotient, terms_of_pass);
 }
 
+// d_out[j] = d_in[j] / Z_S(x_j) over span(basis[0..m)) + shift, S = span(basis[0..sub_dim)) + sub_shift (d_out may be d_in)
+template<class F>
+static int x_div_by_vanishing_dev(const uint64_t *d_in, const uint64_t *basis, size_t m, const uint64_t *shift, size_t sub_dim, const uint64_t *sub_shift,
+                                  uint64_t *d_out)
+{
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!d_in || !d_out || (m > 0 && !basis) || !shift || !sub_shift) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (sub_dim > m || m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "the vanishing set must be spanned by a prefix of the domain's basis");
+    TmpBuf dz;
+    if ((rc = vanishing_inverse_table_x<F>(basis, m, shift, sub_dim, sub_shift, dz, 4, "the domain intersects the vanishing set")) != IOPX_OK) return rc;
+    const size_t n = (size_t)1 << m;
+    IOPX_OPS_LAUNCH(ops_al16(d_in) && ops_al16(d_out) && ops_al16(dz.p), "div_by_vanishing", 2 * n * 8 * F::W, kx_div_by_vanishing, n,
+                    d_out, d_in, (const uint64_t *)dz.u64(), (int)sub_dim, n);
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// Z_S(x) and Z_S's linear coefficient (its formal derivative, vanishing_polynomial.tcc:55-74) for S = span(basis) + shift: host only
+template<class F>
+static int x_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *shift, const uint64_t *x, uint64_t *value_out, uint64_t *linear_coefficient_out)
+{
+    typedef typename F::host H;
+    if ((dim > 0 && !basis) || !shift || !x) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (dim > 63) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
+    const std::vector<H> b = host_elems_x<F>(basis, dim);
+    const SubspacePolyX<H> lin(b.data(), dim);
+    if (value_out) (lin.eval(H(x)) + lin.eval(H(shift))).store(value_out);
+    if (linear_coefficient_out) lin.coeff[0].store(linear_coefficient_out);
+    return IOPX_OK;
+}
+
 } // namespace iopx
 
 // the C entries of one field: iopx_*_<field>_dev over the bodies above
@@ -615,5 +659,15 @@ static int x_poly_div_vanishing_dev(const uint64_t *d_poly, size_t n_coeffs, con
                                               uint64_t *d_quotient)                                                                                             \
     {                                                                                                                                                           \
         return iopx::x_poly_div_vanishing_dev<F>(d_poly, n_coeffs, basis, dim, shift, d_quotient);                                                              \
+    }                                                                                                                                                           \
+    int iopx_div_by_vanishing_##FIELD##_dev(const uint64_t *d_in, const uint64_t *basis, size_t m, const uint64_t *shift, size_t sub_dim,                      \
+                                            const uint64_t *sub_shift, uint64_t *d_out)                                                                         \
+    {                                                                                                                                                           \
+        return iopx::x_div_by_vanishing_dev<F>(d_in, basis, m, shift, sub_dim, sub_shift, d_out);                                                               \
+    }                                                                                                                                                           \
+    int iopx_##FIELD##_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *shift, const uint64_t *x, uint64_t *value_out,                         \
+                                      uint64_t *linear_coefficient_out)                                                                                         \
+    {                                                                                                                                                           \
+        return iopx::x_vanishing_host<F>(basis, dim, shift, x, value_out, linear_coefficient_out);                                                              \
     }                                                                                                                                                           \
     }

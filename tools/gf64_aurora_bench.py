@@ -7,7 +7,10 @@ ends in a device synchronise), the two fields alternating proof by proof so that
 the spread (max - min over the median) are reported.  The profile is taken in a proof of its own, after the timed ones: per kernel the
 launches, the milliseconds, the bytes its launches declared and the rate those give.  A run without a GPU fails.
 
-    python tools/gf64_aurora_bench.py [--log-n 16 20] [--reps 7] [--out FILE]"""
+    python tools/gf64_aurora_bench.py [--log-n 16 20] [--reps 7] [--head-eval {0,1}] [--out FILE]
+
+--head-eval sets the option IOPX_GFX_HEAD_EVAL through iopx_set_option before the first proof (1: head evaluation over the subspace-only fields; left
+unset without the flag: the library's default, 0).  gf192's schedule does not read it."""
 import argparse
 import hashlib
 import json
@@ -28,12 +31,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log-n", type=int, nargs="+", default=[16, 20])
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--head-eval", type=int, choices=(0, 1), default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("gf64_aurora_bench: no GPU (timings are taken on the device only)")
     lib = libiop_amd.lib()
     lib.init(0)
+    if a.head_eval is not None:
+        lib.set_option("IOPX_GFX_HEAD_EVAL", a.head_eval)
     lib.set_stream(torch.cuda.current_stream().cuda_stream)
     results = []
     for log_n in a.log_n:
@@ -56,7 +62,7 @@ def main():
             lib.profile_begin()
             lib.aurora_prove(insts["gf64"])
             prof = lib.profile_report()
-            entry = {"log_n": log_n}
+            entry = {"log_n": log_n, "head_eval": a.head_eval}
             for name, _ in FIELDS:
                 ms = sorted(times[name])
                 med = statistics.median(ms)

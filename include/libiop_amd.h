@@ -284,7 +284,7 @@ int iopx_gf64_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out,
 int iopx_gf64_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count);
 int iopx_gf64_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out);
-/* The protocol-layer steps of the encoded Aurora prover over gf64 (libiop_amd/csrc/gf64_ops.hip).  Each entry takes the argument list of
+/* The protocol-layer steps of the encoded Aurora prover over gf64 (libiop_amd/csrc/gfx_ops.h, instantiated by gf64_ops.hip).  Each entry takes the argument list of
  * its _gf192 twin further down with one word per element, makes the same argument checks with the same messages and cites the same
  * reference lines: the synthetic-instance helpers and f_w' = z - f_1v (r1cs_examples.tcc:40-64), the powers of alpha
  * (basic_lincheck_aux.tcc:37-45), random_linear_combination_oracle (random_linear_combination.tcc:27-57; at most 16 oracles) and its affine

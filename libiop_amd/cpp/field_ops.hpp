@@ -57,7 +57,7 @@ inline constexpr vector_ops gf192 = {
     iopx_gf192_add_dev, iopx_gf192_mul_dev, iopx_gf192_inv_dev, iopx_gf192_div_dev, iopx_gf192_pow_table_dev,
     iopx_lincomb_gf192_dev, iopx_lincomb_affine_gf192_dev, iopx_lincheck_gf192_dev, iopx_spmv_gf192_dev, iopx_rational_combine_gf192_dev,
 };
-// libff::gf64: the Aurora prover's entries (csrc/gf64_ops.hip); no batch division and no rational combination (Fractal is not built over it)
+// libff::gf64: the Aurora prover's entries (csrc/gfx_ops.h through gf64_ops.hip); no batch division and no rational combination (Fractal is not built over it)
 inline constexpr vector_ops gf64 = {
     "gf64", 64, false,
     iopx_gf64_host_mul, iopx_gf64_inverse_host,

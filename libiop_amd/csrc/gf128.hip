@@ -108,7 +108,6 @@ int iopx_ldt_combine_gf128_dev(const void *const *d_oracles, size_t num_oracles,
 
 int iopx_gf128_mul_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return x_mul_dev<Elem128>(d_a, d_b, d_out, count); }
 int iopx_gf128_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count) { return x_inv_dev<Elem128>(d_a, d_out, count); }
-int iopx_gf128_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count) { return x_add_dev<Elem128>(d_a, d_b, d_out, count); }
 int iopx_gf128_host_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) { return x_host_mul<Elem128>(a, b, out); }
 int iopx_gf128_inverse_host(const uint64_t *x, uint64_t *out) { return x_inverse_host<Elem128>(x, out); }
 

@@ -495,13 +495,6 @@ __global__ void __launch_bounds__(256) kx_inv(const uint64_t *a, uint64_t *out, 
         F::template store<A16>(out, i, F::inv(F::template load<A16>(a, i)));
 }
 
-template<class F, bool A16>
-__global__ void __launch_bounds__(256) kx_add(const uint64_t *a, const uint64_t *b, uint64_t *out, size_t count)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x)
-        F::template store<A16>(out, i, F::add(F::template load<A16>(a, i), F::template load<A16>(b, i)));
-}
-
 // ---------------------------------------------------------------------------------------------
 // host: field helpers
 // ---------------------------------------------------------------------------------------------
@@ -1573,18 +1566,6 @@ static int x_inv_dev(const uint64_t *d_a, uint64_t *d_out, size_t count)
     if (count == 0) return IOPX_OK;
     if (!d_a || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
     IOPX_LAUNCHX(al16(d_a) && al16(d_out), "inv", 0, kx_inv, dim3(grid_x(count, 256)), dim3(256), 0, d_a, d_out, count);
-    IOPX_HIP(hipGetLastError());
-    return IOPX_OK;
-}
-
-template<class F>
-static int x_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count)
-{
-    int rc = ensure_device();
-    if (rc != IOPX_OK) return rc;
-    if (count == 0) return IOPX_OK;
-    if (!d_a || !d_b || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
-    IOPX_LAUNCHX(al16(d_a) && al16(d_b) && al16(d_out), "add", 0, kx_add, dim3(grid_x(count, 256)), dim3(256), 0, d_a, d_b, d_out, count);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }

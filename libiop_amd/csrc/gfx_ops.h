@@ -1,8 +1,9 @@
-// The protocol-layer steps of the encoded Aurora prover over a binary field wider than one word, written once: the twins of gf64_ops.hip
-// for GF(2^128) and GF(2^256).  gf128_ops.hip and gf256_ops.hip include this text and instantiate it for their element trait (gf128_elem.h,
-// gf256_elem.h; gfx_additive.h lists what a trait gives, and this text reads OPS_TAG besides: the tag of its cached domain tables).
+// The protocol-layer steps of the encoded Aurora prover over a binary field, written once: the twins of encoded_ops.hip / virtual_oracles.hip
+// for GF(2^64), GF(2^128) and GF(2^256).  gf64_ops.hip, gf128_ops.hip and gf256_ops.hip include this text and instantiate it for their element
+// trait (gf64_elem.h, gf128_elem.h, gf256_elem.h; gfx_additive.h lists what a trait gives, and this text reads OPS_TAG besides: the tag of its
+// cached domain tables).
 //
-//   x_pow_table_dev                                the powers of alpha (basic_lincheck_aux.tcc:37-45)
+//   x_add_dev, x_pow_table_dev                     the vector add, the powers of alpha (basic_lincheck_aux.tcc:37-45)
 //   x_lincomb_dev                                  random_linear_combination_oracle::evaluated_contents (random_linear_combination.tcc:27-57),
 //                                                  single_matrix_denominator::evaluated_contents (holographic_lincheck_aux.tcc:117-143)
 //   x_spmv_dev                                     create_Az_Bz_Cz_from_variable_assignment (r1cs.tcc:236-268), p_alpha_ABC (basic_lincheck_aux.tcc:64-88)
@@ -13,13 +14,16 @@
 //   x_poly_div_vanishing_dev                       polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371)
 //   x_div_by_vanishing_dev, x_vanishing_host       the head route's pointwise division by Z_S and the host's Z_S(x) (include/libiop_amd_head.h)
 //
-// One element per lane, in a grid-stride loop: every kernel reads each input once and writes the output once.  An element travels as F::mem
-// through F::load<A16> / F::store<A16>: the A16 instantiation (128-bit accesses) runs when every device pointer of the launch, the cached
-// tables included, is 16-byte aligned, the other one (64-bit words, "_w64" in the profile) otherwise.  Constants of a launch (coefficients,
-// the squares of a base, the terms of a division pass) travel in the kernel's argument block: no upload.  The domain-shaped values Z_I(x_j),
-// Z_H(x_j), x_j, x_j^|H| are subset sums of an (m + 1)-entry table over the bits of j (linearized_polynomial.tcc:83-108).  No LDS.
-// The grid is capped by the option IOPX_GFX_OPS_MAX_BLOCKS (default 16384, looked up per launch; a test helper: a small cap sends every
-// grid-stride loop round again at a few thousand elements).
+// Every kernel reads each input once and writes the output once, in a grid-stride loop.  An element travels as F::mem through F::load<A16> /
+// F::store<A16>: the A16 instantiation (16-byte accesses) runs when every device pointer that it reads or writes 16 bytes at a time is 16-byte
+// aligned, the other one (64-bit words, "_w64" in the profile) otherwise.  A lane takes one element; in the 16-byte form over a one-word
+// element it takes the two consecutive elements of one access (ops_lane) where the position of an element does not enter the addressing
+// beyond "j and j + 1": everywhere but the powers of a base, the CSR gather and the division passes (odd offsets), which have one form over
+// such an element and the plain name.  Constants of a launch (coefficients, the squares of a base, the terms of a division pass) travel in
+// the kernel's argument block: no upload.  The domain-shaped values Z_I(x_j), Z_H(x_j), x_j, x_j^|H| are subset sums of an (m + 1)-entry
+// table over the bits of j (linearized_polynomial.tcc:83-108); position j + 1 of a pair differs from position j by the table's entry for
+// bit 0.  No LDS.  The grid is capped by the option IOPX_GFX_OPS_MAX_BLOCKS (default 16384, looked up per launch; a test helper: a small cap
+// sends every grid-stride loop round again at a few thousand elements).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -39,20 +43,37 @@ static int ops_grid_x(size_t work)
 }
 
 static bool ops_al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+// a cached table is read one element at a time: a one-word element asks no alignment of it
+template<class F> static bool ops_table_al16(const void *p) { return F::W == 1 || ops_al16(p); }
 
-// launch the A16 instantiation when `a16`, the 64-bit-word one otherwise, under the matching profile name: the field's stem + the kernel's name
-// (+ "_w64"), built once per launch site and field
-#define IOPX_OPS_LAUNCH(a16, name, bytes, K, work, ...)                                                                \
+// elements per lane in the 16-byte form: two one-word elements fill one access.  The kernels written over a lane's elements (LaneX below)
+// take ops_lane<F, A16>: one for every wider element and in the 64-bit-word form.
+template<class F, bool A16> constexpr int ops_lane = A16 && F::W == 1 ? 2 : 1;
+
+// Launch K over `work` elements: K<F, true> (`lane` elements per lane: ops_lane<F, true> for a kernel written over a lane's elements, 1 for
+// the others) when `a16`, K<F, false> otherwise, under the matching profile name: the field's stem + the kernel's name (+ "_w64"), built once
+// per launch site and field.  Where the two would be the same code (a one-word element, one element per lane) there is one instantiation
+// and one name, without "_w64".
+#define IOPX_OPS_LAUNCH(a16, name, bytes, K, lane, work, ...)                                                          \
     do {                                                                                                               \
-        const bool a16_ = (a16);                                                                                       \
+        constexpr size_t lane_ = (lane);                                                                               \
+        constexpr bool forms_ = F::W > 1 || lane_ > 1;                                                                 \
+        const bool a16_ = forms_ && (a16);                                                                             \
         static const std::string names_[2] = { std::string(F::stem()) + name, std::string(F::stem()) + name + "_w64" }; \
-        ProfScope ps_(names_[a16_ ? 0 : 1].c_str(), bytes);                                                            \
-        const dim3 grid_(ops_grid_x(work));                                                                            \
-        if (a16_) hipLaunchKernelGGL((K<F, true>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                        \
-        else hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                            \
+        ProfScope ps_(names_[forms_ && !a16_ ? 1 : 0].c_str(), bytes);                                                 \
+        const dim3 grid_(ops_grid_x(a16_ ? ((work) + lane_ - 1) / lane_ : (work)));                                    \
+        if constexpr (forms_) {                                                                                        \
+            if (a16_) hipLaunchKernelGGL((K<F, true>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                    \
+            else hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                        \
+        } else {                                                                                                       \
+            hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                             \
+        }                                                                                                              \
     } while (0)
 
-#define OPSX_LOOP(j, n) for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < (n); j += (size_t)gridDim.x * blockDim.x)
+// a grid-stride loop of V elements per lane: j is a multiple of V
+#define OPSX_LOOP_V(V, j, n) \
+    for (size_t j = (size_t)(V) * ((size_t)blockIdx.x * blockDim.x + threadIdx.x); j < (n); j += (size_t)(V) * gridDim.x * blockDim.x)
+#define OPSX_LOOP(j, n) OPSX_LOOP_V(1, j, n)
 
 // t[0] + sum_{bit k of j} t[1 + k], j < 2^m
 template<class F, bool A16>
@@ -61,6 +82,106 @@ __device__ __forceinline__ typename F::mem subset_sum_x(const uint64_t *t, int m
     typename F::mem v = F::template load<A16>(t, 0);
     for (int k = 0; k < m; ++k) if ((j >> k) & 1) v = F::add(v, F::template load<A16>(t, 1 + k));
     return v;
+}
+
+// The elements [j, j + V) of one lane as a value (val) and the field's operations on it: what a kernel over a lane's elements is written in.
+// An operand of the arithmetic may be named ahead of it (fetch) and read where it is used (get), for the sake of the pair form below.
+//
+// One element per lane: val is the element, every operation is the field's own, and an operand is fetched where it is used.  The kernels
+// then are the text they were before the pair form, and the code of the wider fields is the code it was.
+template<class F, bool A16, int V = ops_lane<F, A16>>
+struct LaneX : F {
+    static_assert(V == 1, "one element per lane, or the pair form below");
+    typedef typename F::mem mem;
+    typedef mem val;
+    typedef const uint64_t *operand;
+    static __device__ __forceinline__ val load(const uint64_t *p, size_t j, size_t) { return F::template load<A16>(p, j); }
+    static __device__ __forceinline__ void store(uint64_t *p, size_t j, size_t, const val &x) { F::template store<A16>(p, j, x); }
+    static __device__ __forceinline__ operand fetch(const uint64_t *p, size_t, size_t) { return p; }
+    static __device__ __forceinline__ val get(operand p, size_t j, size_t) { return F::template load<A16>(p, j); }
+    static __device__ __forceinline__ const mem &splat(const mem &c) { return c; }
+    // zinv[j >> s], the entry of the position's coset: named (coset) and read where it is used (entry), as an operand
+    struct cosets { const uint64_t *zinv; size_t j; int s; };
+    static __device__ __forceinline__ cosets coset(const uint64_t *zinv, size_t j, int s, size_t) { cosets z; z.zinv = zinv; z.j = j; z.s = s; return z; }
+    static __device__ __forceinline__ val entry(const cosets &z) { return F::template load<A16>(z.zinv, z.j >> z.s); }
+    static __device__ __forceinline__ val sums(const uint64_t *t, int m, size_t j) { return subset_sum_x<F, A16>(t, m, j); }
+    // add, mul and inv are F's functions themselves (hence the base class), not wrappers of them: behind a wrapper's extra level of inlining
+    // the compiler swapped the operands of a few commutative instructions in the products of the wider fields
+    using F::add;
+    using F::mul;
+    using F::inv;
+};
+
+// Two one-word elements per lane, j even.  Position j + 1 is absent at the end of an odd n: it reads as zero and is not written.  A pair is
+// fetched where it is named: its accesses sit in branches of their own (the absent position), which the compiler does not move, so fetched at
+// their uses they would wait behind the arithmetic in front of them.
+struct alignas(16) OpsPair { uint64_t a, b; };
+
+template<class F, bool A16>
+struct LaneX<F, A16, 2> {
+    static constexpr int V = 2;
+    typedef typename F::mem mem;
+    struct val { mem e[V]; };
+    typedef val operand;
+
+    static __device__ __forceinline__ val load(const uint64_t *p, size_t j, size_t n)
+    {
+        val r;
+        if (j + 1 < n) { const OpsPair t = *reinterpret_cast<const OpsPair *>(p + j); r.e[0] = t.a; r.e[1] = t.b; }
+        else { r.e[0] = p[j]; r.e[1] = 0; }
+        return r;
+    }
+    static __device__ __forceinline__ void store(uint64_t *p, size_t j, size_t n, const val &x)
+    {
+        if (j + 1 < n) { OpsPair t; t.a = x.e[0]; t.b = x.e[1]; *reinterpret_cast<OpsPair *>(p + j) = t; }
+        else p[j] = x.e[0];
+    }
+    static __device__ __forceinline__ operand fetch(const uint64_t *p, size_t j, size_t n) { return load(p, j, n); }
+    static __device__ __forceinline__ const val &get(const operand &x, size_t, size_t) { return x; }
+    // one value of the launch in both positions
+    static __device__ __forceinline__ val splat(const mem &c) { val r; r.e[0] = c; r.e[1] = c; return r; }
+    // zinv[(j + e) >> s], the entry of each position's coset, fetched where it is named.  The absent position has none, and a product with
+    // the entries leaves that position as it is (a branch per element: the two products one after the other take 54 registers in rowcheck,
+    // side by side 69)
+    struct cosets { mem e[V]; size_t j, n; };
+    static __device__ __forceinline__ cosets coset(const uint64_t *zinv, size_t j, int s, size_t n)
+    {
+        cosets z;
+        z.j = j; z.n = n;
+#pragma unroll
+        for (int e = 0; e < V; ++e) z.e[e] = j + e < n ? F::template load<A16>(zinv, (j + e) >> s) : F::zero();
+        return z;
+    }
+    static __device__ __forceinline__ const cosets &entry(const cosets &z) { return z; }
+    static __device__ __forceinline__ val mul(const val &a, const cosets &z)
+    {
+        val r = a;
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            if (z.j + e < z.n) r.e[e] = F::mul(a.e[e], z.e[e]);
+        }
+        return r;
+    }
+    // the subset sums at positions j and j + 1: the second is the first plus the entry for bit 0, which the table of a domain of one element
+    // does not have (there position j + 1 is absent)
+    static __device__ __forceinline__ val sums(const uint64_t *t, int m, size_t j)
+    {
+        val r;
+        r.e[0] = subset_sum_x<F, A16>(t, m, j);
+        r.e[1] = m > 0 ? F::add(r.e[0], F::template load<A16>(t, 1)) : F::zero();
+        return r;
+    }
+    static __device__ __forceinline__ val add(const val &a, const val &b) { val r; r.e[0] = F::add(a.e[0], b.e[0]); r.e[1] = F::add(a.e[1], b.e[1]); return r; }
+    static __device__ __forceinline__ val mul(const val &a, const val &b) { val r; r.e[0] = F::mul(a.e[0], b.e[0]); r.e[1] = F::mul(a.e[1], b.e[1]); return r; }
+    static __device__ __forceinline__ val inv(const val &a) { val r; r.e[0] = F::inv(a.e[0]); r.e[1] = F::inv(a.e[1]); return r; }
+};
+
+// ---- elementwise -----------------------------------------------------------------------------------------------------------
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_add(uint64_t *out, const uint64_t *a, const uint64_t *b, size_t n)
+{
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, n) L::store(out, j, n, L::add(L::load(a, j, n), L::load(b, j, n)));
 }
 
 // ---- the powers of a base -------------------------------------------------------------------------------------------------
@@ -100,10 +221,11 @@ struct LincombParamsX {
 template<class F, bool A16>
 __global__ void __launch_bounds__(256) kx_lincomb(LincombParamsX<F> p)
 {
-    OPSX_LOOP(j, p.n) {
-        typename F::mem acc = p.constant;
-        for (int i = 0; i < p.num; ++i) acc = F::add(acc, F::mul(F::template load<A16>(p.o[i], j), p.c[i]));
-        F::template store<A16>(p.out, j, acc);
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, p.n) {
+        typename L::val acc = L::splat(p.constant);
+        for (int i = 0; i < p.num; ++i) acc = L::add(acc, L::mul(L::load(p.o[i], j, p.n), L::splat(p.c[i])));
+        L::store(p.out, j, p.n, acc);
     }
 }
 
@@ -163,10 +285,13 @@ template<class F, bool A16>
 __global__ void __launch_bounds__(256) kx_rowcheck(uint64_t *out, const uint64_t *az, const uint64_t *bz, const uint64_t *cz, const uint64_t *zinv, int h,
                                                    size_t n)
 {
-    OPSX_LOOP(j, n) {
-        const typename F::mem ab = F::mul(F::template load<A16>(az, j), F::template load<A16>(bz, j));
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, n) {
+        const typename L::operand a = L::fetch(az, j, n), b = L::fetch(bz, j, n), c = L::fetch(cz, j, n);
+        const typename L::cosets z = L::coset(zinv, j, h, n);
+        const typename L::val ab = L::mul(L::get(a, j, n), L::get(b, j, n));
         // characteristic 2: a b - c = a b + c
-        F::template store<A16>(out, j, F::mul(F::add(ab, F::template load<A16>(cz, j)), F::template load<A16>(zinv, j >> h)));
+        L::store(out, j, n, L::mul(L::add(ab, L::get(c, j, n)), L::entry(z)));
     }
 }
 
@@ -174,18 +299,19 @@ __global__ void __launch_bounds__(256) kx_rowcheck(uint64_t *out, const uint64_t
 template<class F, bool A16>
 __global__ void __launch_bounds__(256) kx_div_by_vanishing(uint64_t *out, const uint64_t *in, const uint64_t *zinv, int s, size_t n)
 {
-    OPSX_LOOP(j, n) {
-        F::template store<A16>(out, j, F::mul(F::template load<A16>(in, j), F::template load<A16>(zinv, j >> s)));
-    }
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, n) L::store(out, j, n, L::mul(L::load(in, j, n), L::entry(L::coset(zinv, j, s, n))));
 }
 
 // result[x] = fw(x) Z_I(x) + f_1v(x)
 template<class F, bool A16>
 __global__ void __launch_bounds__(256) kx_fz(uint64_t *out, const uint64_t *fw, const uint64_t *f1v, const uint64_t *tab, int m, size_t n)
 {
-    OPSX_LOOP(j, n) {
-        const typename F::mem z = subset_sum_x<F, A16>(tab, m, j);
-        F::template store<A16>(out, j, F::add(F::mul(F::template load<A16>(fw, j), z), F::template load<A16>(f1v, j)));
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, n) {
+        const typename L::operand w = L::fetch(fw, j, n), f = L::fetch(f1v, j, n);
+        const typename L::val z = L::sums(tab, m, j);
+        L::store(out, j, n, L::add(L::mul(L::get(w, j, n), z), L::get(f, j, n)));
     }
 }
 
@@ -205,14 +331,16 @@ struct SumcheckParamsX {
 template<class F, bool A16, bool NONZERO>
 __device__ __forceinline__ void sumcheck_g_body(const SumcheckParamsX<F> &p)
 {
-    OPSX_LOOP(j, p.n) {
-        typename F::mem f = F::template load<A16>(p.f, j);
-        f = F::add(f, F::mul(subset_sum_x<F, A16>(p.ztab, p.m, j), F::template load<A16>(p.h, j)));
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, p.n) {
+        const typename L::operand h = L::fetch(p.h, j, p.n);
+        typename L::val f = L::load(p.f, j, p.n);
+        f = L::add(f, L::mul(L::sums(p.ztab, p.m, j), L::get(h, j, p.n)));
         if constexpr (NONZERO) {
-            const typename F::mem xinv_c = F::mul(F::inv(subset_sum_x<F, A16>(p.xtab, p.m, j)), p.c);
-            f = F::add(f, F::mul(subset_sum_x<F, A16>(p.htab, p.m, j), xinv_c));
+            const typename L::val xinv_c = L::mul(L::inv(L::sums(p.xtab, p.m, j)), L::splat(p.c));
+            f = L::add(f, L::mul(L::sums(p.htab, p.m, j), xinv_c));
         }
-        F::template store<A16>(p.out, j, f);
+        L::store(p.out, j, p.n, f);
     }
 }
 template<class F, bool A16> __global__ void __launch_bounds__(256) kx_sumcheck_g_zero_sum(SumcheckParamsX<F> p) { sumcheck_g_body<F, A16, false>(p); }
@@ -233,12 +361,13 @@ struct LincheckParamsX {
 template<class F, bool A16>
 __global__ void __launch_bounds__(256) kx_lincheck(LincheckParamsX<F> p)
 {
-    OPSX_LOOP(j, p.n) {
-        typename F::mem comb = F::zero();
-        for (int m = 0; m < p.num_matrices; ++m) comb = F::add(comb, F::mul(F::template load<A16>(p.mz[m], j), p.r[m]));
-        comb = F::mul(comb, F::template load<A16>(p.p1, j));
-        comb = F::add(comb, F::mul(F::template load<A16>(p.fz, j), F::template load<A16>(p.p2, j)));
-        F::template store<A16>(p.out, j, comb);
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, p.n) {
+        typename L::val comb = L::splat(F::zero());
+        for (int m = 0; m < p.num_matrices; ++m) comb = L::add(comb, L::mul(L::load(p.mz[m], j, p.n), L::splat(p.r[m])));
+        comb = L::mul(comb, L::load(p.p1, j, p.n));
+        comb = L::add(comb, L::mul(L::load(p.fz, j, p.n), L::load(p.p2, j, p.n)));
+        L::store(p.out, j, p.n, comb);
     }
 }
 
@@ -255,7 +384,7 @@ template<class F>
 static typename F::mem mem_of_x(const typename F::host &x)
 {
     typename F::mem r;
-    x.store(r.w);
+    x.store(reinterpret_cast<uint64_t *>(&r));       // F::mem is F::W words
     return r;
 }
 
@@ -347,10 +476,22 @@ static int run_division_x(const uint64_t *d_high, size_t M, size_t min_offset, u
             continue;
         }
         p.src = src; p.dst = dst; p.M = M;
-        IOPX_OPS_LAUNCH(ops_al16(src) && ops_al16(dst), "polydiv_pass", 2 * M * EB, kx_polydiv_pass, M, p);
+        IOPX_OPS_LAUNCH(ops_al16(src) && ops_al16(dst), "polydiv_pass", 2 * M * EB, kx_polydiv_pass, 1, M, p);
         IOPX_HIP(hipGetLastError());
         src = dst;
     }
+    return IOPX_OK;
+}
+
+template<class F>
+static int x_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count)
+{
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (count == 0) return IOPX_OK;
+    if (!d_a || !d_b || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    IOPX_OPS_LAUNCH(ops_al16(d_a) && ops_al16(d_b) && ops_al16(d_out), "add", 3 * count * 8 * F::W, kx_add, (ops_lane<F, true>), count, d_out, d_a, d_b, count);
+    IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
 
@@ -367,13 +508,13 @@ static int x_lincomb_dev(const void *const *d_oracles, size_t num, const uint64_
     for (size_t i = 0; i < num; ++i) {
         if (!d_oracles[i]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null oracle");
         p.o[i] = (const uint64_t *)d_oracles[i];
-        memcpy(p.c[i].w, coeffs + F::W * i, 8 * F::W);
+        memcpy(&p.c[i], coeffs + F::W * i, 8 * F::W);
         a16 = a16 && ops_al16(d_oracles[i]);
     }
-    if (constant) memcpy(p.constant.w, constant, 8 * F::W);
+    if (constant) memcpy(&p.constant, constant, 8 * F::W);
     p.out = d_out; p.num = (int)num; p.n = n;
     if (n == 0) return IOPX_OK;
-    IOPX_OPS_LAUNCH(a16, "lincomb", (num + 1) * n * 8 * F::W, kx_lincomb, n, p);
+    IOPX_OPS_LAUNCH(a16, "lincomb", (num + 1) * n * 8 * F::W, kx_lincomb, (ops_lane<F, true>), n, p);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -400,8 +541,8 @@ static int x_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, 
     if (p.nbits > POWX_MAX_BITS) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
     H x(base);
     for (int k = 0; k < p.nbits; ++k) { p.sq[k] = mem_of_x<F>(x); x = x.squared(); }
-    memcpy(p.init.w, init, 8 * F::W);
-    IOPX_OPS_LAUNCH(ops_al16(d_out), "pow_table", count * 8 * F::W, kx_pow_table, count, d_out, count, p);
+    memcpy(&p.init, init, 8 * F::W);
+    IOPX_OPS_LAUNCH(ops_al16(d_out), "pow_table", count * 8 * F::W, kx_pow_table, 1, count, d_out, count, p);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -418,9 +559,9 @@ static int x_spmv_dev(const uint64_t *d_row_ptr, const uint32_t *d_col, const ui
     memset(&p, 0, sizeof(p));
     p.row_ptr = d_row_ptr; p.col = d_col; p.coeff = d_coeff; p.vec = d_vec; p.out = d_out; p.rows = rows; p.accumulate = accumulate;
     p.has_scale = scale ? 1 : 0;
-    if (scale) memcpy(p.scale.w, scale, 8 * F::W);
+    if (scale) memcpy(&p.scale, scale, 8 * F::W);
     // the entries are counted on the device only: the rows' output is what the host can declare
-    IOPX_OPS_LAUNCH(ops_al16(d_coeff) && ops_al16(d_vec) && ops_al16(d_out), "spmv", (size_t)(accumulate ? 2 : 1) * rows * 8 * F::W, kx_spmv, rows, p);
+    IOPX_OPS_LAUNCH(ops_al16(d_coeff) && ops_al16(d_vec) && ops_al16(d_out), "spmv", (size_t)(accumulate ? 2 : 1) * rows * 8 * F::W, kx_spmv, 1, rows, p);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -441,12 +582,12 @@ static int x_lincheck_dev(const uint64_t *d_fz, const void *const *d_Mz, size_t 
     for (size_t m = 0; m < num_matrices; ++m) {
         if (!d_Mz[m]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
         p.mz[m] = (const uint64_t *)d_Mz[m];
-        memcpy(p.r[m].w, r_Mz + F::W * m, 8 * F::W);
+        memcpy(&p.r[m], r_Mz + F::W * m, 8 * F::W);
         a16 = a16 && ops_al16(d_Mz[m]);
     }
     p.num_matrices = (int)num_matrices; p.n = n;
     if (n == 0) return IOPX_OK;
-    IOPX_OPS_LAUNCH(a16, "lincheck", (num_matrices + 4) * n * 8 * F::W, kx_lincheck, n, p);
+    IOPX_OPS_LAUNCH(a16, "lincheck", (num_matrices + 4) * n * 8 * F::W, kx_lincheck, (ops_lane<F, true>), n, p);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -463,8 +604,8 @@ static int x_rowcheck_dev(const uint64_t *d_Az, const uint64_t *d_Bz, const uint
     TmpBuf dz;
     if ((rc = vanishing_inverse_table_x<F>(basis, m, shift, h, constraint_shift, dz)) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << m;
-    IOPX_OPS_LAUNCH(ops_al16(d_Az) && ops_al16(d_Bz) && ops_al16(d_Cz) && ops_al16(d_out) && ops_al16(dz.p), "rowcheck", 4 * n * 8 * F::W, kx_rowcheck, n,
-                    d_out, d_Az, d_Bz, d_Cz, (const uint64_t *)dz.u64(), (int)h, n);
+    IOPX_OPS_LAUNCH(ops_al16(d_Az) && ops_al16(d_Bz) && ops_al16(d_Cz) && ops_al16(d_out) && ops_table_al16<F>(dz.p), "rowcheck", 4 * n * 8 * F::W,
+                    kx_rowcheck, (ops_lane<F, true>), n, d_out, d_Az, d_Bz, d_Cz, (const uint64_t *)dz.u64(), (int)h, n);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -490,7 +631,7 @@ static int x_fz_dev(const uint64_t *d_fw, const uint64_t *d_f1v, const uint64_t 
     }, dt);
     if (rc != IOPX_OK) return rc;
     const size_t n = (size_t)1 << m;
-    IOPX_OPS_LAUNCH(ops_al16(d_fw) && ops_al16(d_f1v) && ops_al16(d_out) && ops_al16(dt.p), "fz", 3 * n * 8 * F::W, kx_fz, n,
+    IOPX_OPS_LAUNCH(ops_al16(d_fw) && ops_al16(d_f1v) && ops_al16(d_out) && ops_table_al16<F>(dt.p), "fz", 3 * n * 8 * F::W, kx_fz, (ops_lane<F, true>), n,
                     d_out, d_fw, d_f1v, (const uint64_t *)dt.u64(), (int)m, n);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
@@ -532,10 +673,10 @@ static int x_sumcheck_g_dev(const uint64_t *d_f, const uint64_t *d_h, const uint
     p.f = d_f; p.h = d_h; p.out = d_out;
     p.xtab = dtabs.u64(); p.htab = dtabs.u64() + table_words; p.ztab = dtabs.u64() + 2 * table_words;
     p.c = mem_of_x<F>(c); p.m = (int)m; p.n = (size_t)1 << m;
-    // the three tables are whole elements apart: aligned together with the block
-    const bool a16 = ops_al16(d_f) && ops_al16(d_h) && ops_al16(d_out) && ops_al16(p.xtab) && ops_al16(p.htab) && ops_al16(p.ztab);
-    if (c.is_zero()) IOPX_OPS_LAUNCH(a16, "sumcheck_g_zero_sum", 3 * p.n * 8 * F::W, kx_sumcheck_g_zero_sum, p.n, p);
-    else IOPX_OPS_LAUNCH(a16, "sumcheck_g", 3 * p.n * 8 * F::W, kx_sumcheck_g, p.n, p);
+    // the three tables are whole elements apart: where an element is 16 bytes or more they are aligned together with the block
+    const bool a16 = ops_al16(d_f) && ops_al16(d_h) && ops_al16(d_out) && ops_table_al16<F>(p.xtab) && ops_table_al16<F>(p.htab) && ops_table_al16<F>(p.ztab);
+    if (c.is_zero()) IOPX_OPS_LAUNCH(a16, "sumcheck_g_zero_sum", 3 * p.n * 8 * F::W, kx_sumcheck_g_zero_sum, (ops_lane<F, true>), p.n, p);
+    else IOPX_OPS_LAUNCH(a16, "sumcheck_g", 3 * p.n * 8 * F::W, kx_sumcheck_g, (ops_lane<F, true>), p.n, p);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -591,8 +732,8 @@ static int x_div_by_vanishing_dev(const uint64_t *d_in, const uint64_t *basis, s
     TmpBuf dz;
     if ((rc = vanishing_inverse_table_x<F>(basis, m, shift, sub_dim, sub_shift, dz, 4, "the domain intersects the vanishing set")) != IOPX_OK) return rc;
     const size_t n = (size_t)1 << m;
-    IOPX_OPS_LAUNCH(ops_al16(d_in) && ops_al16(d_out) && ops_al16(dz.p), "div_by_vanishing", 2 * n * 8 * F::W, kx_div_by_vanishing, n,
-                    d_out, d_in, (const uint64_t *)dz.u64(), (int)sub_dim, n);
+    IOPX_OPS_LAUNCH(ops_al16(d_in) && ops_al16(d_out) && ops_table_al16<F>(dz.p), "div_by_vanishing", 2 * n * 8 * F::W, kx_div_by_vanishing,
+                    (ops_lane<F, true>), n, d_out, d_in, (const uint64_t *)dz.u64(), (int)sub_dim, n);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }
@@ -616,6 +757,10 @@ static int x_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *s
 // the C entries of one field: iopx_*_<field>_dev over the bodies above
 #define IOPX_GFX_OPS_ENTRIES(FIELD, F)                                                                                                                          \
     extern "C" {                                                                                                                                                \
+    int iopx_##FIELD##_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count)                                                         \
+    {                                                                                                                                                           \
+        return iopx::x_add_dev<F>(d_a, d_b, d_out, count);                                                                                                      \
+    }                                                                                                                                                           \
     int iopx_##FIELD##_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init)                                                 \
     {                                                                                                                                                           \
         return iopx::x_pow_table_dev<F>(d_out, count, base, init);                                                                                              \

@@ -1006,7 +1006,7 @@ class GF256DeviceOps(DeviceOps):
 
 class GF64AuroraOps(GF64DeviceOps):
     """GF64DeviceOps plus what the Aurora prover (libiop_amd/aurora.py, libiop_amd/bcs.py) calls: the iopx_*_gf64_dev entries of
-    libiop_amd/csrc/gf64_ops.hip.  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  The operators only Fractal
+    libiop_amd/csrc/gfx_ops.h (gf64_ops.hip).  Constructed by name — DeviceOps(...) over GF64 keeps returning GF64DeviceOps.  The operators only Fractal
     calls (div, domain_offsets, domain_elements, vanishing_evals, lagrange_evals, rational_*) keep raising."""
 
 

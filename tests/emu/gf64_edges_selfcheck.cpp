@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY: the pair-form entries of libiop_amd/csrc/gf64_ops.hip in a stand-alone program over the CPU build, for
+// TEST INFRASTRUCTURE ONLY: the pair-form entries of libiop_amd/csrc/gfx_ops.h over gf64 (gf64_ops.hip) in a stand-alone program over the CPU build, for
 // AddressSanitizer and UBSan (make gf64_edges_selfcheck_san && ./gf64_edges_selfcheck_san; nothing is loaded into Python, nothing preloaded).
 // Two things no comparison of outputs sees, because the values involved are never stored: a 16-byte access at an address that is only 8-byte
 // aligned (an entry that takes the two-element form although one of its vectors is off the boundary), and the read of a subset-sum table's

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY: the nine entries of include/libiop_amd_head.h (gf64_ops.hip, gfx_ops.h, gfx_additive.h) in a stand-alone program over the
+// TEST INFRASTRUCTURE ONLY: the nine entries of include/libiop_amd_head.h (gfx_ops.h, gfx_additive.h) in a stand-alone program over the
 // CPU build, for AddressSanitizer and UBSan (make -f gfx_head_selfcheck.mk gfx_head_selfcheck_san && ./gfx_head_selfcheck_san; nothing is loaded
 // into Python, nothing preloaded).  What no comparison of outputs sees, because the values involved are never stored: a 16-byte access at an address
 // that is only 8-byte aligned (an entry that takes the 128-bit or the pair form although one of its vectors is off the boundary), and a read past

@@ -1,4 +1,4 @@
-// TEST INFRASTRUCTURE ONLY: the protocol-layer entries of libiop_amd/csrc/gfx_ops.h (gf128_ops.hip, gf256_ops.hip) in a stand-alone program over
+// TEST INFRASTRUCTURE ONLY: the protocol-layer entries of libiop_amd/csrc/gfx_ops.h over the wider fields (gf128_ops.hip, gf256_ops.hip) in a stand-alone program over
 // the CPU build, for AddressSanitizer and UBSan (make -f gfx_ops_edges_selfcheck.mk gfx_ops_edges_selfcheck_san && ./gfx_ops_edges_selfcheck_san; nothing is loaded into Python,
 // nothing preloaded).  Two things no comparison of outputs sees, because the values involved are never stored: a 16-byte access at an address that
 // is only 8-byte aligned (an entry that takes the 128-bit form although one of its vectors is off the boundary), and a read past a subset-sum

@@ -1,4 +1,4 @@
-# TEST INFRASTRUCTURE ONLY: the entries of gfx_ops.h (gf128_ops.hip, gf256_ops.hip) with each vector in turn off the 16-byte boundary, and the
+# TEST INFRASTRUCTURE ONLY: the entries of gfx_ops.h over the wider fields (gf128_ops.hip, gf256_ops.hip; gf64_edges_selfcheck has gf64's) with each vector in turn off the 16-byte boundary, and the
 # domain-shaped ones on a domain of one element, under AddressSanitizer and UBSan in a stand-alone program (gfx_ops_edges_selfcheck.cpp), over the
 # sanitizer objects and flags of the Makefile beside this file.
 #   make -f gfx_ops_edges_selfcheck.mk gfx_ops_edges_selfcheck_san && ./gfx_ops_edges_selfcheck_san

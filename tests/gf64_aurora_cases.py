@@ -1,13 +1,13 @@
-"""Cases for Aurora over GF(2^64): the protocol-layer entries of libiop_amd/csrc/gf64_ops.hip against the function-level oracle, and the
+"""Cases for Aurora over GF(2^64): the protocol-layer entries (libiop_amd/csrc/gfx_ops.h, instantiated by gf64_ops.hip) against the function-level oracle, and the
 Python prover (libiop_amd/aurora.py over domains.GF64AuroraOps) and the native one (field code 4 of the C ABI) against the oracle's prover
 and verifier.  Shared by
 tests/test_gf64_aurora_emu.py (CPU emulation) and tests/test_gpu_gf64_aurora.py (MI355X): every function takes the Library under test.
 
 Every comparison is byte equality.  Elements are (n, 1) uint64 arrays.  Each kernel case runs with its vectors at a 16-byte boundary and 8
-bytes past one: the entries take two elements per lane in the first placement and one in the second.  The edge cases (check_small_domains,
-check_short_vectors, check_mixed_placements, check_aliased_outputs, check_domain_table_turnover) add the smallest domains and vectors, one
-argument alone off the boundary, outputs over inputs and the turnover of the library's domain tables; tests/gf64_large_cases.py has the
-same entries past their launch caps."""
+bytes past one: the entries take two elements per lane in the first placement (the profile's k64_<name>) and one in the second
+(k64_<name>_w64).  The edge cases (check_small_domains, check_short_vectors, check_mixed_placements, check_aliased_outputs, check_small_grid,
+check_domain_table_turnover) add the smallest domains and vectors, one argument alone off the boundary, outputs over inputs, a grid of two
+or three blocks and the turnover of the library's domain tables; tests/gf64_large_cases.py has the same entries past their launch caps."""
 import ctypes
 import hashlib
 import json
@@ -372,10 +372,9 @@ def run_placed(lib, inputs, out_count, call, offsets, alias=None):
         return dev.get(out, out_count), prof
 
 
-def pair_form_entries(lib):
-    """(profile label, inputs, output length, call) of every entry that has a two-elements-per-lane form, at a length that ends in half a pair
-    (513) or on a domain of 2^9"""
-    n, m = 513, 9
+def pair_form_entries(lib, n=513, m=9):
+    """(profile label, inputs, output length, call) of every entry of the protocol layer that has a two-elements-per-lane form, at a length that
+    ends in half a pair (513) or on a domain of 2^9"""
     basis, shift = codeword_domain(m)
     mu = G.elem(int(G.seeded("sumcheck mu", 1)[0, 0]) | BIT63)
     coef, constant, r = G.seeded("placed lincomb coef", 3), G.elem(int(G.seeded("lincomb constant", 1)[0, 0])), G.seeded("placed lincheck r", 2)
@@ -394,35 +393,100 @@ def pair_form_entries(lib):
     ]
 
 
+def one_form_entries(lib, n):
+    """the same of the entries that take one element per lane wherever their vectors lie (one kernel, one profile label): the powers of a base, the
+    CSR product and one division pass exactly (|H| / 2 < n <= |H|: the passes of a longer division alternate with a temporary of the library's)"""
+    base, init = G.elem(int(G.seeded("pow base", 1)[0, 0]) | BIT63), G.elem(int(G.seeded("pow init", 1)[0, 0]))
+    rng = np.random.default_rng(n)
+    lengths = rng.integers(0, 4, size=n)
+    row_ptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+    col = rng.integers(0, 64, size=int(row_ptr[-1])).astype(np.uint32)
+    dbasis, dshift = G.std_basis(max(n - 1, 0).bit_length()), G.elem(BIT63 | 0x80)
+    dN = 1 << dbasis.shape[0]
+
+    def spmv(p, o):
+        with Device(lib) as dev:            # the CSR offsets and columns are not element vectors: they sit in buffers of their own, aligned
+            lib.spmv_dev(dev.put(row_ptr), dev.put(col), p[0], n, p[1], o, words=1)
+            lib.synchronize()
+    return [
+        ("k64_pow_table", [], n, lambda p, o: lib.pow_table_dev(o, n, base, init, words=1)),
+        ("k64_spmv", [G.seeded("placed spmv coef", col.shape[0]), G.seeded("placed spmv vec", 64)], n, spmv),
+        ("k64_polydiv_pass", [G.seeded("placed polydiv", n + dN)], n, lambda p, o: lib.poly_div_vanishing_dev(p[0], n + dN, dbasis, dshift, o, words=1)),
+    ]
+
+
+def launches(prof, label):
+    """(launches of the 16-byte form, launches of the 64-bit-word form) of one kernel in a profile"""
+    return prof.get(label, (0,))[0], prof.get(label + "_w64", (0,))[0]
+
+
 def _for_each_entry(lib, body):
     for label, inputs, out_count, call in pair_form_entries(lib):
         aligned, prof = run_placed(lib, inputs, out_count, call, [0] * (len(inputs) + 1))
-        assert prof.get(label, (0,))[0] == 1, label
+        assert launches(prof, label) == (1, 0), (label, "all aligned: one launch of the two-element form", launches(prof, label))
         body(label, inputs, out_count, call, aligned)
 
 
 def check_mixed_placements(lib):
     """exactly one vector, each argument in turn and the output last, 8 bytes past a 16-byte boundary: the entry takes one element per lane
-    (the same profile label), launches once and returns the all-aligned result"""
+    (the profile's label + "_w64", and no launch under the plain label), launches once and returns the all-aligned result"""
     def body(label, inputs, out_count, call, aligned):
         for which in range(len(inputs) + 1):
             offsets = [8 if i == which else 0 for i in range(len(inputs) + 1)]
             got, prof = run_placed(lib, inputs, out_count, call, offsets)
-            assert prof.get(label, (0,))[0] == 1, (label, which)
+            assert launches(prof, label) == (0, 1), (label, which, launches(prof, label))
             assert np.array_equal(got, aligned), (label, which)
     _for_each_entry(lib, body)
 
 
 def check_aliased_outputs(lib):
     """the output over each input in turn, at both placements: every entry here is elementwise (position j of the output depends on position j
-    of the inputs), and the provers call them that way"""
+    of the inputs), and the provers call them that way.  One launch in all, under the name of the placement's form."""
     def body(label, inputs, out_count, call, aligned):
         for off in OFFSETS:
             for which in range(len(inputs)):
                 got, prof = run_placed(lib, inputs, out_count, call, [off] * (len(inputs) + 1), alias=which)
-                assert prof.get(label, (0,))[0] == 1, (label, off, which)
+                assert launches(prof, label) == ((1, 0) if off == 0 else (0, 1)), (label, off, which, launches(prof, label))
                 assert np.array_equal(got, aligned), (label, off, which)
     _for_each_entry(lib, body)
+
+
+def check_small_grid(lib):
+    """IOPX_GFX_OPS_MAX_BLOCKS = 2 and vectors of 2 * (2 * 256 * 2) + 3 = 2051 elements: the two-element form takes a third trip round its
+    grid-stride loop that ends in half a pair, the one-element form a fifth trip of 3.  A domain has 2^m points, so the domain-shaped entries
+    (the head route's division by Z_S among them) run 2^12 points under a cap of 3 blocks: 1536 per trip of the two-element form (the third
+    trip has 1024), 768 per trip of the other (the sixth has 256).  Every entry, at both placements, launches once under the name of its form
+    and returns what it returns under the default grid, with the output apart and, for the elementwise entries, over the first input (a loop that
+    visited a position twice would then work on its own output); lincomb and fz equal the oracle's results under the cap too."""
+    n, m = 2 * (2 * 256 * 2) + 3, 12
+    N = 1 << m
+    basis, shift = codeword_domain(m)
+    div = ("k64_div_by_vanishing", [G.seeded("placed div", N)], N, lambda p, o: lib.div_by_vanishing(p[0], basis, shift, 4, G.elem(0x55), o, words=1))
+    paired = [(e, True) for e in pair_form_entries(lib, n, m) + [div]]
+    for cap, count, entries in ((2, n, paired + [(e, False) for e in one_form_entries(lib, n)]), (3, N, paired)):
+        ran = 0
+        for (label, inputs, out_count, call), two_forms in entries:
+            if out_count != count:
+                continue
+            ran += 1
+            want, _ = run_placed(lib, inputs, out_count, call, [0] * (len(inputs) + 1))
+            with options(lib, IOPX_GFX_OPS_MAX_BLOCKS=cap):
+                for off in OFFSETS:
+                    got, prof = run_placed(lib, inputs, out_count, call, [off] * (len(inputs) + 1))
+                    assert launches(prof, label) == ((0, 1) if off and two_forms else (1, 0)), (label, cap, off, launches(prof, label))
+                    assert np.array_equal(got, want), (label, cap, off)
+                    if two_forms:       # the output over the first input: a stride of fewer than V elements per lane would process a position twice
+                        got, _ = run_placed(lib, inputs, out_count, call, [off] * (len(inputs) + 1), alias=0)
+                        assert np.array_equal(got, want), (label, cap, off, "aliased")
+        assert ran == (7 if cap == 2 else 5), (cap, ran)      # add, lincomb, affine lincomb, lincheck, pow_table, spmv, division | rowcheck, fz, two sumchecks, div
+    with options(lib, IOPX_GFX_OPS_MAX_BLOCKS=2):
+        vecs, coef = [G.seeded("grid lincomb %d" % k, n) for k in range(2)], G.seeded("grid coef", 2)
+        got = on_device(lib, vecs, n, lambda p, o: lib.lincomb_dev(p, coef, n, o, words=1))
+        assert np.array_equal(got, xor_all([scaled(v, c) for v, c in zip(vecs, coef)]))
+    with options(lib, IOPX_GFX_OPS_MAX_BLOCKS=3):
+        fw, f1v = G.seeded("grid fz w", N), G.seeded("grid fz v", N)
+        got = on_device(lib, [fw, f1v], N, lambda p, o: lib.fz_dev(p[0], p[1], basis, shift, basis[:3], G.elem(5), o, words=1))
+        assert np.array_equal(got, oracle.fz_additive(fw, f1v, basis, shift, basis[:3], G.elem(5)))
 
 
 def check_domain_table_turnover(lib):

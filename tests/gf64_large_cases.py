@@ -1,4 +1,4 @@
-"""Cases past the launch caps of the GF(2^64) arm: the entries of libiop_amd/csrc/gf64_ops.hip at the smallest sizes where their grid-stride loops
+"""Cases past the launch caps of the GF(2^64) arm: the protocol-layer entries (libiop_amd/csrc/gfx_ops.h over gf64) at the smallest sizes where their grid-stride loops
 take a second trip (16384 workgroups of 256 lanes: 2^22 elements with one element per lane, 2^23 with two), and the LDE of
 libiop_amd/csrc/gf64.hip with more cosets than one staging group holds.  Run by tests/test_gpu_gf64_large.py on the MI355X; every function
 takes the Library under test, so the emulation can run them by hand (1 - 90 s each).  tests/test_gf64_large_emu.py checks the host-side
@@ -122,16 +122,17 @@ def assert_sumcheck_nonzero(got, f, h, basis, shift, sb, sshift, mu):
 
 # ---- device placements ----
 def both_placements(lib, inputs, out_count, call, label=None):
-    """C.on_device with the library's profile around each call: the entry launched its kernel once at either placement"""
+    """C.on_device with the library's profile around each call: the entry launched its kernel once at either placement, under the name of the
+    placement's form (`label` on the 16-byte boundary, `label` + "_w64" 8 bytes past it)"""
     if label is None:
         return C.on_device(lib, inputs, out_count, call)
     launches = []
     def counted(p, o):
         lib.profile_begin()
         call(p, o)
-        launches.append(lib.profile_report().get(label, (0,))[0])
+        launches.append(C.launches(lib.profile_report(), label))
     got = C.on_device(lib, inputs, out_count, counted)
-    assert launches == [1, 1], (label, launches)
+    assert launches == [(1, 0), (0, 1)], (label, launches)
     return got
 
 
@@ -143,7 +144,7 @@ def one_placement(lib, inputs, out_count, call, init=None):
         return dev.get(out, out_count)
 
 
-# ---- 1. the entries of gf64_ops.hip past their caps ----
+# ---- 1. the entries of gfx_ops.h over gf64 past their caps ----
 def check_add(lib, n=CAP_ODD):
     a, b = G.seeded("large add a", n), G.seeded("large add b", n)
     got = both_placements(lib, [a, b], n, lambda p, o: lib.field_add_dev(p[0], p[1], o, n, words=1), "k64_add")

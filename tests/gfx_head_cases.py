@@ -19,7 +19,6 @@ WORDS = B.WORDS
 NAME = B.NAME
 STEM = B.STEM
 OPTION = "IOPX_GFX_HEAD_EVAL"
-GRID_CAP = {1: "IOPX_GF64_OPS_MAX_BLOCKS", 2: "IOPX_GFX_OPS_MAX_BLOCKS", 4: "IOPX_GFX_OPS_MAX_BLOCKS"}
 DIV_SHAPES = ((0, 0), (1, 0), (1, 1), (5, 0), (5, 4), (5, 5), (9, 4), (11, 4))
 REEXTEND_SHAPES = ((3, 1), (5, 5), (9, 5), (9, 9), (13, 9))
 REEXTEND_BATCHES = ((3, 1), (1, 1), (2, 3))
@@ -105,12 +104,12 @@ def check_div_trust(lib):
 
 
 def check_div_grid_cap(lib, W):
-    """the field's grid cap at 2 blocks and 2^11 points: four trips of the one-element loop (two of gf64's pair loop), same outputs"""
+    """the grid cap (IOPX_GFX_OPS_MAX_BLOCKS) at 2 blocks and 2^11 points: four trips of the one-element loop (two of gf64's pair loop), same outputs"""
     m, sub_dim = 11, 4
     basis, shift, sub_shift = div_domains(m, sub_dim, W, "seeded")
     v = seeded("div cap", 1 << m, W)
     Z = vanishing_over(oracle.all_subset_sums(basis, shift), oracle.all_subset_sums(basis[:sub_dim], sub_shift))
-    with C.options(lib, **{GRID_CAP[W]: 2}):
+    with C.options(lib, IOPX_GFX_OPS_MAX_BLOCKS=2):
         for off in (0, 8):
             got, rows = run_div(lib, W, v, basis, shift, sub_dim, sub_shift, off, off)
             assert np.array_equal(oracle.gf_mul(got, Z), v), (NAME[W], off)

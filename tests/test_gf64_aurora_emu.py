@@ -63,6 +63,10 @@ def test_output_over_an_input():
     C.check_aliased_outputs(emu())
 
 
+def test_small_grid():
+    C.check_small_grid(emu())
+
+
 def test_domain_table_turnover():
     C.check_domain_table_turnover(emu())
 

@@ -1,4 +1,4 @@
-"""The memory contract of the GF(2^64) protocol-layer entries (libiop_amd/csrc/gf64_ops.hip) and of one native gf64 Aurora proof, with the
+"""The memory contract of the GF(2^64) protocol-layer entries (libiop_amd/csrc/gfx_ops.h, instantiated by gf64_ops.hip) and of one native gf64 Aurora proof, with the
 harness of tests/memory_contract_cases.py: every input in a 4096-byte frame of random non-zero bytes, every output in a frame pre-filled
 with random bytes, the library under its memory-check mode (IOPX_MEM_CHECK: guards around every block it allocates, poisoned payloads), two
 poison bytes, payload offsets 0 and 8 modulo 16 — the entries take two elements per lane at the first offset and one at the second.  After

@@ -93,6 +93,10 @@ def test_output_over_an_input(lib):
     C.check_aliased_outputs(lib)
 
 
+def test_small_grid(lib):
+    C.check_small_grid(lib)
+
+
 def test_domain_table_turnover(lib):
     C.check_domain_table_turnover(lib)
 

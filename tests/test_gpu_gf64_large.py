@@ -1,4 +1,4 @@
-"""The GF(2^64) arm past its launch caps on the MI355X (tests/gf64_large_cases.py): every entry of libiop_amd/csrc/gf64_ops.hip at the smallest
+"""The GF(2^64) arm past its launch caps on the MI355X (tests/gf64_large_cases.py): every protocol-layer entry (libiop_amd/csrc/gfx_ops.h over gf64) at the smallest
 size where its grid-stride loop takes a second trip (2^23 + 3 elements, 2^22 + 3 rows, m = 24), whole-vector against a host-side reference
 that tests/test_gf64_large_emu.py holds to the oracle at m = 12; and the LDE of libiop_amd/csrc/gf64.hip over two staging groups (2^13
 coefficients, 4101 cosets of an m = 26 domain).  The wall time of each test is the host-side reference's: the kernels take milliseconds."""

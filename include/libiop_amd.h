@@ -293,8 +293,9 @@ int iopx_gf64_inverse_host(const uint64_t *x, uint64_t *out);
  * (r1cs_rs_iop.tcc:181-222), sumcheck_g_oracle (sumcheck.tcc:58-119; a zero domain element inverts to zero, utils.tcc:79-97) and
  * polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371).  Codeword domains of dimension above 40 are refused.
  * iopx_gf64_mul_dev and iopx_gf64_inv_dev above are the products and inverses.  Aurora over gf64 runs through these from the Python
- * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); Fractal and a distributed prover
- * are not built over gf64 (the fused re-extensions: libiop_amd_batch.h; head evaluation, behind the option IOPX_GFX_HEAD_EVAL: libiop_amd_head.h). */
+ * prover (libiop_amd.domains.GF64AuroraOps) and from the native one (IOPX_FIELD_GF64 below); a distributed prover is not built over gf64
+ * (the fused re-extensions: libiop_amd_batch.h; head evaluation, behind the option IOPX_GFX_HEAD_EVAL: libiop_amd_head.h; Fractal, behind the option
+ * IOPX_GFX_FRACTAL: libiop_amd_fractal.h). */
 int iopx_gf64_add_dev(const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t count);
 int iopx_gf64_pow_table_dev(uint64_t *d_out, size_t count, const uint64_t *base, const uint64_t *init);
 int iopx_lincomb_gf64_dev(const void *const *d_oracles, size_t num_oracles, const uint64_t *coefficients, size_t n, uint64_t *d_out);
@@ -398,6 +399,13 @@ int iopx_gf256_inverse_host(const uint64_t *x, uint64_t *out);
  * entries of those names in this file at one, two and four words per element, declared once for the three fields in libiop_amd_head.h (beside this
  * file).  With them the native Aurora prover takes the head route over these fields when the option IOPX_GFX_HEAD_EVAL is non-zero (default 0). */
 #include "libiop_amd_head.h"
+
+/* ---- GF(2^64), GF(2^128), GF(2^256): what the Fractal prover needs ---------------------------------- */
+/* iopx_{gf64,gf128,gf256}_div_dev, iopx_domain_offsets_*_dev, iopx_vanishing_evals_*_dev, iopx_rational_combine_*_dev and
+ * iopx_rational_sumcheck_constraint_*_dev: the gf192 entries of those names in this file at one, two and four words per element, declared once for
+ * the three fields in libiop_amd_fractal.h (beside this file).  With them iopx_fractal_index / iopx_fractal_prove run over IOPX_FIELD_GF64 when the
+ * option IOPX_GFX_FRACTAL is non-zero (default 0: refused, as over gf128 and gf256 whatever the option says). */
+#include "libiop_amd_fractal.h"
 
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
 /* merkle_tree::construct_with_leaves_serialized_by_cosets + compute_inner_nodes:
@@ -676,7 +684,7 @@ int iopx_pow_solve_poseidon_bn128(const iopx_poseidon_params *params, const uint
  * algorithmic_bytes = elements swept x 24 x (read + write) summed over the launches, 0 for kernels that do not report it). */
 /* Options: named integers that select a prover schedule or a tile geometry (the names are listed in DESIGN.md).  A name's value is what
  * iopx_set_option gave it, else the environment variable of that name (read once per process, at the name's first lookup), else the built-in
- * default.  Schedule options (IOPX_HEAD_EVAL, IOPX_GFX_HEAD_EVAL, IOPX_MERKLE_STREAM, IOPX_DEFER_ROOTS) are looked up per proof; tile geometries are latched by
+ * default.  Schedule options (IOPX_HEAD_EVAL, IOPX_GFX_HEAD_EVAL, IOPX_GFX_FRACTAL, IOPX_MERKLE_STREAM, IOPX_DEFER_ROOTS) are looked up per proof; tile geometries are latched by
  * their component at its first use. */
 int iopx_set_option(const char *name, int value);
 int iopx_clear_option(const char *name);
@@ -758,8 +766,9 @@ int iopx_fp3_modulus(uint64_t *out);
 #define IOPX_FIELD_ALT_BN128_FR 2   /* Aurora instances (BLAKE2b or Poseidon: iopx_aurora_prove_hashed) and the FRI-only SNARK; no Fractal, no distributed prover */
 /* libff::gf64 (3 stays unknown): Aurora instances and the FRI-only SNARK on one GPU with BLAKE2b, in the reference's schedule unless the option IOPX_GFX_HEAD_EVAL is non-zero (default 0:
  * no head evaluation, whatever IOPX_HEAD_EVAL says; non-zero: the head route where IOPX_HEAD_EVAL allows it, same bytes; libiop_amd_head.h.  Re-extensions through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf64: a communicator (the _dist forms),
- * iopx_fractal_index / iopx_fractal_prove, a Poseidon hash, and a codeword domain of more than 2^IOPX_GF64_MAX_DOMAIN_DIM points — the bound of the gf64
- * transform entries — which is checked from the parameters before any device work. */
+ * iopx_fractal_index / iopx_fractal_prove unless the option IOPX_GFX_FRACTAL is non-zero (default 0; non-zero: the Fractal indexer and prover on one GPU
+ * with BLAKE2b, the oracle's bytes; libiop_amd_fractal.h), a Poseidon hash, and a codeword domain of more than 2^IOPX_GF64_MAX_DOMAIN_DIM points — the
+ * bound of the gf64 transform entries — which is checked from the parameters before any device work. */
 #define IOPX_FIELD_GF64 4
 #define IOPX_GF64_MAX_DOMAIN_DIM 40
 /* libff::gf128: Aurora instances from CSR matrices (iopx_aurora_instance_create; iopx_aurora_prove, iopx_aurora_prove_hashed with IOPX_HASH_BLAKE2B,

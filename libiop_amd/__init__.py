@@ -102,6 +102,13 @@ BATCH_SYMBOLS = [pattern % field for field in ("gf64", "gf128", "gf256")
 HEAD_SYMBOLS = [pattern % field for field in ("gf64", "gf128", "gf256")
                 for pattern in ("iopx_div_by_vanishing_%s_dev", "iopx_%s_vanishing_host", "iopx_add_reextend2_%s_batch_dev")]
 
+# the declarations of include/libiop_amd_fractal.h (which libiop_amd.h includes): what the Fractal prover needs over gf64, gf128 and gf256 beyond Aurora's
+# entries (the batch division, point - x and c - Z_S(x) over a domain, the rational combination, the rational sumcheck's constraint oracle), one
+# parameterised text for the three fields
+FRACTAL_SYMBOLS = [pattern % field for field in ("gf64", "gf128", "gf256")
+                   for pattern in ("iopx_%s_div_dev", "iopx_domain_offsets_%s_dev", "iopx_vanishing_evals_%s_dev", "iopx_rational_combine_%s_dev",
+                                   "iopx_rational_sumcheck_constraint_%s_dev")]
+
 
 class NoDeviceError(RuntimeError):
     pass
@@ -343,6 +350,10 @@ class Library:
         c.iopx_div_by_vanishing_gf192_dev.argtypes = [_vp, _u64p, _sz, _u64p, _sz, _u64p, _vp]
         c.iopx_add_reextend2_gf192_batch_dev.argtypes = [_vp, _sz, _u64p, _vp, _sz, _u64p, _u64p, _sz, _sz, _u64p, _sz, _sz, ctypes.POINTER(_vp)]
         for name in ("div_by_vanishing_%s_dev", "%s_vanishing_host", "add_reextend2_%s_batch_dev"):
+            for field in ("gf64", "gf128", "gf256"):
+                getattr(c, "iopx_" + name % field).argtypes = list(getattr(c, "iopx_" + name % "gf192").argtypes)
+        # what the Fractal prover needs: the prototypes of the gf192 entries, for the three fields of libiop_amd_fractal.h
+        for name in ("%s_div_dev", "domain_offsets_%s_dev", "vanishing_evals_%s_dev", "rational_combine_%s_dev", "rational_sumcheck_constraint_%s_dev"):
             for field in ("gf64", "gf128", "gf256"):
                 getattr(c, "iopx_" + name % field).argtypes = list(getattr(c, "iopx_" + name % "gf192").argtypes)
 
@@ -1392,15 +1403,18 @@ class Library:
         fn = self.c.iopx_lincomb_affine_gf64_dev if words == 1 else self.c.iopx_lincomb_affine_fp3_dev if prime_field else self.c.iopx_lincomb_affine_gf128_dev if words == 2 else self.c.iopx_lincomb_affine_gf256_dev if words == 4 else self.c.iopx_lincomb_affine_gf192_dev
         self._check(fn(ptrs, len(d_oracles), co.ctypes.data_as(_u64p), c0.ctypes.data_as(_u64p), int(n), _vp(d_out)))
 
-    def field_div_dev(self, d_num, d_den, d_out, count, prime_field=False):
+    def field_div_dev(self, d_num, d_den, d_out, count, prime_field=False, words=3):
         """d_out = d_num / d_den elementwise by batch inversion (d_num None: inverses); zero denominators give zero."""
-        fn = self.c.iopx_fp3_div_dev if prime_field else self.c.iopx_gf192_div_dev
+        fn = self.c.iopx_fp3_div_dev if prime_field else (self.c.iopx_gf64_div_dev if words == 1 else self.c.iopx_gf128_div_dev if words == 2
+              else self.c.iopx_gf256_div_dev if words == 4 else self.c.iopx_gf192_div_dev)
         self._check(fn(_vp(d_num) if d_num is not None else None, _vp(d_den), _vp(d_out), int(count)))
 
-    def domain_offsets_dev(self, basis, shift, point, d_out):
+    def domain_offsets_dev(self, basis, shift, point, d_out, words=3):
         """d_out[j] = point - x_j over the affine subspace (basis, shift)."""
-        basis, shift, point = _as_u64(basis).reshape(-1, 3), _as_u64(shift), _as_u64(point)
-        self._check(self.c.iopx_domain_offsets_gf192_dev(basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
+        basis, shift, point = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, words), _as_u64(shift, words), _as_u64(point, words)
+        fn = (self.c.iopx_domain_offsets_gf64_dev if words == 1 else self.c.iopx_domain_offsets_gf128_dev if words == 2
+              else self.c.iopx_domain_offsets_gf256_dev if words == 4 else self.c.iopx_domain_offsets_gf192_dev)
+        self._check(fn(basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p),
                                                          point.ctypes.data_as(_u64p), _vp(d_out)))
 
     def domain_offsets_multiplicative_dev(self, log_n, gen, shift, point, d_out):
@@ -1408,11 +1422,13 @@ class Library:
         self._check(self.c.iopx_domain_offsets_fp3_dev(int(log_n), gen.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p), point.ctypes.data_as(_u64p),
                                                        _vp(d_out)))
 
-    def vanishing_evals_dev(self, basis, shift, vanishing_basis, vanishing_shift, constant, d_out):
+    def vanishing_evals_dev(self, basis, shift, vanishing_basis, vanishing_shift, constant, d_out, words=3):
         """d_out[j] = constant - Z_S(x_j), S = span(vanishing_basis) + vanishing_shift, x over the subspace (basis, shift)."""
-        basis, vb = _as_u64(basis).reshape(-1, 3), _as_u64(vanishing_basis).reshape(-1, 3)
-        shift, vs, c0 = _as_u64(shift), _as_u64(vanishing_shift), _as_u64(constant)
-        self._check(self.c.iopx_vanishing_evals_gf192_dev(basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), vb.ctypes.data_as(_u64p),
+        basis, vb = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, words), np.ascontiguousarray(vanishing_basis, dtype=np.uint64).reshape(-1, words)
+        shift, vs, c0 = _as_u64(shift, words), _as_u64(vanishing_shift, words), _as_u64(constant, words)
+        fn = (self.c.iopx_vanishing_evals_gf64_dev if words == 1 else self.c.iopx_vanishing_evals_gf128_dev if words == 2
+              else self.c.iopx_vanishing_evals_gf256_dev if words == 4 else self.c.iopx_vanishing_evals_gf192_dev)
+        self._check(fn(basis.ctypes.data_as(_u64p), basis.shape[0], shift.ctypes.data_as(_u64p), vb.ctypes.data_as(_u64p),
                                                           vb.shape[0], vs.ctypes.data_as(_u64p), c0.ctypes.data_as(_u64p), _vp(d_out)))
 
     def vanishing_evals_multiplicative_dev(self, log_n, gen, shift, vanishing_log_order, vanishing_shift, constant, d_out):
@@ -1420,18 +1436,22 @@ class Library:
         self._check(self.c.iopx_vanishing_evals_fp3_dev(int(log_n), gen.ctypes.data_as(_u64p), shift.ctypes.data_as(_u64p), int(vanishing_log_order),
                                                         vs.ctypes.data_as(_u64p), c0.ctypes.data_as(_u64p), _vp(d_out)))
 
-    def rational_combine_dev(self, d_numerators, d_denominators, coefficients, n, d_numerator_out, d_denominator_out, prime_field=False):
+    def rational_combine_dev(self, d_numerators, d_denominators, coefficients, n, d_numerator_out, d_denominator_out, prime_field=False, words=3):
         """combined_numerator / combined_denominator::evaluated_contents for up to 4 rationals."""
-        co = _as_u64(coefficients)
+        co = _as_u64(coefficients, words)
         if co.shape[0] != len(d_numerators) or len(d_numerators) != len(d_denominators):
             raise ValueError("Expected same number of random coefficients as oracles.")
         pn, pd = (_vp * len(d_numerators))(*d_numerators), (_vp * len(d_denominators))(*d_denominators)
-        fn = self.c.iopx_rational_combine_fp3_dev if prime_field else self.c.iopx_rational_combine_gf192_dev
+        fn = self.c.iopx_rational_combine_fp3_dev if prime_field else (self.c.iopx_rational_combine_gf64_dev if words == 1 else self.c.iopx_rational_combine_gf128_dev if words == 2
+              else self.c.iopx_rational_combine_gf256_dev if words == 4 else self.c.iopx_rational_combine_gf192_dev)
         self._check(fn(pn, pd, len(d_numerators), co.ctypes.data_as(_u64p), int(n), _vp(d_numerator_out), _vp(d_denominator_out)))
 
-    def rational_sumcheck_constraint_dev(self, d_p, d_N, d_D, d_xinv, basis, shift, summation_dim, summation_shift, claimed_sum, d_out):
-        basis, shift, ss, mu = _as_u64(basis).reshape(-1, 3), _as_u64(shift), _as_u64(summation_shift), _as_u64(claimed_sum)
-        self._check(self.c.iopx_rational_sumcheck_constraint_gf192_dev(_vp(d_p), _vp(d_N), _vp(d_D), _vp(d_xinv), basis.ctypes.data_as(_u64p), basis.shape[0],
+    def rational_sumcheck_constraint_dev(self, d_p, d_N, d_D, d_xinv, basis, shift, summation_dim, summation_shift, claimed_sum, d_out, words=3):
+        basis = np.ascontiguousarray(basis, dtype=np.uint64).reshape(-1, words)
+        shift, ss, mu = _as_u64(shift, words), _as_u64(summation_shift, words), _as_u64(claimed_sum, words)
+        fn = (self.c.iopx_rational_sumcheck_constraint_gf64_dev if words == 1 else self.c.iopx_rational_sumcheck_constraint_gf128_dev if words == 2
+              else self.c.iopx_rational_sumcheck_constraint_gf256_dev if words == 4 else self.c.iopx_rational_sumcheck_constraint_gf192_dev)
+        self._check(fn(_vp(d_p), _vp(d_N), _vp(d_D), _vp(d_xinv), basis.ctypes.data_as(_u64p), basis.shape[0],
                                                                        shift.ctypes.data_as(_u64p), int(summation_dim), ss.ctypes.data_as(_u64p),
                                                                        mu.ctypes.data_as(_u64p), _vp(d_out)))
 

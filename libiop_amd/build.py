@@ -27,7 +27,7 @@ def _headers():
     (prover_capi.hip compiles those into the library)."""
     hs = [os.path.join(dp, f) for dp, _, fs in os.walk(CSRC) for f in fs if not f.endswith(".hip")]
     hs += [os.path.join(CPP, f) for f in os.listdir(CPP)]
-    hs += [os.path.join(_HERE, "..", "include", h) for h in ("libiop_amd.h", "libiop_amd_gfx.h", "libiop_amd_batch.h", "libiop_amd_head.h")]
+    hs += [os.path.join(_HERE, "..", "include", h) for h in ("libiop_amd.h", "libiop_amd_gfx.h", "libiop_amd_batch.h", "libiop_amd_head.h", "libiop_amd_fractal.h")]
     return hs
 
 

@@ -57,26 +57,26 @@ inline constexpr vector_ops gf192 = {
     iopx_gf192_add_dev, iopx_gf192_mul_dev, iopx_gf192_inv_dev, iopx_gf192_div_dev, iopx_gf192_pow_table_dev,
     iopx_lincomb_gf192_dev, iopx_lincomb_affine_gf192_dev, iopx_lincheck_gf192_dev, iopx_spmv_gf192_dev, iopx_rational_combine_gf192_dev,
 };
-// libff::gf64: the Aurora prover's entries (csrc/gfx_ops.h through gf64_ops.hip); no batch division and no rational combination (Fractal is not built over it)
+// libff::gf64: the Aurora and Fractal provers' entries (csrc/gfx_ops.h through gf64_ops.hip; the batch division and the rational combination: include/libiop_amd_fractal.h)
 inline constexpr vector_ops gf64 = {
     "gf64", 64, false,
     iopx_gf64_host_mul, iopx_gf64_inverse_host,
-    iopx_gf64_add_dev, iopx_gf64_mul_dev, iopx_gf64_inv_dev, nullptr, iopx_gf64_pow_table_dev,
-    iopx_lincomb_gf64_dev, iopx_lincomb_affine_gf64_dev, iopx_lincheck_gf64_dev, iopx_spmv_gf64_dev, nullptr,
+    iopx_gf64_add_dev, iopx_gf64_mul_dev, iopx_gf64_inv_dev, iopx_gf64_div_dev, iopx_gf64_pow_table_dev,
+    iopx_lincomb_gf64_dev, iopx_lincomb_affine_gf64_dev, iopx_lincheck_gf64_dev, iopx_spmv_gf64_dev, iopx_rational_combine_gf64_dev,
 };
-// libff::gf128: the vector helpers of csrc/gf128.hip and the Aurora prover's entries (csrc/gf128_ops.hip); as gf64, nothing that only Fractal calls
+// libff::gf128: the vector helpers of csrc/gf128.hip and the Aurora prover's entries (csrc/gf128_ops.hip), as gf64
 inline constexpr vector_ops gf128 = {
     "gf128", 128, false,
     iopx_gf128_host_mul, iopx_gf128_inverse_host,
-    iopx_gf128_add_dev, iopx_gf128_mul_dev, iopx_gf128_inv_dev, nullptr, iopx_gf128_pow_table_dev,
-    iopx_lincomb_gf128_dev, iopx_lincomb_affine_gf128_dev, iopx_lincheck_gf128_dev, iopx_spmv_gf128_dev, nullptr,
+    iopx_gf128_add_dev, iopx_gf128_mul_dev, iopx_gf128_inv_dev, iopx_gf128_div_dev, iopx_gf128_pow_table_dev,
+    iopx_lincomb_gf128_dev, iopx_lincomb_affine_gf128_dev, iopx_lincheck_gf128_dev, iopx_spmv_gf128_dev, iopx_rational_combine_gf128_dev,
 };
 // libff::gf256: the vector helpers of csrc/gf256.hip and the Aurora prover's entries (csrc/gf256_ops.hip); as gf128
 inline constexpr vector_ops gf256 = {
     "gf256", 256, false,
     iopx_gf256_host_mul, iopx_gf256_inverse_host,
-    iopx_gf256_add_dev, iopx_gf256_mul_dev, iopx_gf256_inv_dev, nullptr, iopx_gf256_pow_table_dev,
-    iopx_lincomb_gf256_dev, iopx_lincomb_affine_gf256_dev, iopx_lincheck_gf256_dev, iopx_spmv_gf256_dev, nullptr,
+    iopx_gf256_add_dev, iopx_gf256_mul_dev, iopx_gf256_inv_dev, iopx_gf256_div_dev, iopx_gf256_pow_table_dev,
+    iopx_lincomb_gf256_dev, iopx_lincomb_affine_gf256_dev, iopx_lincheck_gf256_dev, iopx_spmv_gf256_dev, iopx_rational_combine_gf256_dev,
 };
 inline constexpr subspace_ops gf192_subspace = {
     iopx_add_fft_gf192_dev, iopx_add_lde_gf192_dev, iopx_add_ifft_gf192_dev,
@@ -93,8 +93,8 @@ inline constexpr subspace_ops gf64_subspace = {
     iopx_add_fft_gf64_dev, iopx_add_lde_gf64_dev, iopx_add_ifft_gf64_dev,
     iopx_fri_fold_add_gf64_dev, iopx_fri_domains_gf64, iopx_ldt_combine_gf64_dev,
     iopx_rowcheck_gf64_dev, iopx_fz_gf64_dev, iopx_sumcheck_g_gf64_dev,
-    iopx_poly_div_vanishing_gf64_dev, nullptr,
-    nullptr, nullptr,
+    iopx_poly_div_vanishing_gf64_dev, iopx_domain_offsets_gf64_dev,
+    iopx_vanishing_evals_gf64_dev, iopx_rational_sumcheck_constraint_gf64_dev,
     iopx_add_ifft_gf64_batch_dev, iopx_add_lde_gf64_batch_dev,
     iopx_add_reextend_gf64_batch_dev, iopx_add_reextend_lde_gf64_batch_dev,
     iopx_div_by_vanishing_gf64_dev, iopx_add_reextend2_gf64_batch_dev,
@@ -104,8 +104,8 @@ inline constexpr subspace_ops gf128_subspace = {
     iopx_add_fft_gf128_dev, iopx_add_lde_gf128_dev, iopx_add_ifft_gf128_dev,
     iopx_fri_fold_add_gf128_dev, iopx_fri_domains_gf128, iopx_ldt_combine_gf128_dev,
     iopx_rowcheck_gf128_dev, iopx_fz_gf128_dev, iopx_sumcheck_g_gf128_dev,
-    iopx_poly_div_vanishing_gf128_dev, nullptr,
-    nullptr, nullptr,
+    iopx_poly_div_vanishing_gf128_dev, iopx_domain_offsets_gf128_dev,
+    iopx_vanishing_evals_gf128_dev, iopx_rational_sumcheck_constraint_gf128_dev,
     iopx_add_ifft_gf128_batch_dev, iopx_add_lde_gf128_batch_dev,
     iopx_add_reextend_gf128_batch_dev, iopx_add_reextend_lde_gf128_batch_dev,
     iopx_div_by_vanishing_gf128_dev, iopx_add_reextend2_gf128_batch_dev,
@@ -115,8 +115,8 @@ inline constexpr subspace_ops gf256_subspace = {
     iopx_add_fft_gf256_dev, iopx_add_lde_gf256_dev, iopx_add_ifft_gf256_dev,
     iopx_fri_fold_add_gf256_dev, iopx_fri_domains_gf256, iopx_ldt_combine_gf256_dev,
     iopx_rowcheck_gf256_dev, iopx_fz_gf256_dev, iopx_sumcheck_g_gf256_dev,
-    iopx_poly_div_vanishing_gf256_dev, nullptr,
-    nullptr, nullptr,
+    iopx_poly_div_vanishing_gf256_dev, iopx_domain_offsets_gf256_dev,
+    iopx_vanishing_evals_gf256_dev, iopx_rational_sumcheck_constraint_gf256_dev,
     iopx_add_ifft_gf256_batch_dev, iopx_add_lde_gf256_batch_dev,
     iopx_add_reextend_gf256_batch_dev, iopx_add_reextend_lde_gf256_batch_dev,
     iopx_div_by_vanishing_gf256_dev, iopx_add_reextend2_gf256_batch_dev,

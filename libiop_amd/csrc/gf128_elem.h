@@ -34,6 +34,9 @@ struct Elem128 {
     static __device__ __forceinline__ mem mul(const mem &a, const mem &b) { return pack(g128_mul(unpack(a), unpack(b))); }
     static __device__ __forceinline__ mem inv(const mem &a) { return pack(g128_inv(unpack(a))); }
 
+    static constexpr uint64_t MODULUS_LOW = 0x87;               // x^128 + x^7 + x^2 + x + 1 without its leading term
+    static constexpr bool DIV_EUCLID = true;                    // kx_div inverts a workgroup's root by the binary Euclid: measured faster
+
     // the host side
     typedef hgf128 host;
     static const char *stem() { return "k128_"; }

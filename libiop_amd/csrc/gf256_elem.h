@@ -48,6 +48,9 @@ struct Elem256 {
     static __device__ __forceinline__ mem mul(const mem &a, const mem &b) { return pack(g256_mul(unpack(a), unpack(b))); }
     static __device__ __forceinline__ mem inv(const mem &a) { return pack(g256_inv(unpack(a))); }
 
+    static constexpr uint64_t MODULUS_LOW = 0x425;               // x^256 + x^10 + x^5 + x^2 + 1 without its leading term
+    static constexpr bool DIV_EUCLID = true;                    // kx_div inverts a workgroup's root by the binary Euclid: measured faster
+
     // the host side
     typedef hgf256 host;
     static const char *stem() { return "k256_"; }

@@ -22,6 +22,9 @@ struct Elem64 {
     static __device__ __forceinline__ mem mul(mem a, mem b) { return g64_word(g64_mul(g64_from(a), g64_from(b))); }
     static __device__ __forceinline__ mem inv(mem a) { return g64_word(g64_inv(g64_from(a))); }
 
+    static constexpr uint64_t MODULUS_LOW = 0x1B;               // x^64 + x^4 + x^3 + x + 1 without its leading term
+    static constexpr bool DIV_EUCLID = true;                    // kx_div inverts a workgroup's root by the binary Euclid: measured faster
+
     // the host side
     typedef hgf64 host;
     static const char *stem() { return "k64_"; }

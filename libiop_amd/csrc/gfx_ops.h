@@ -13,6 +13,8 @@
 //   x_sumcheck_g_dev                               sumcheck_g_oracle::evaluated_contents (sumcheck.tcc:58-119)
 //   x_poly_div_vanishing_dev                       polynomial_over_vanishing_polynomial(...).first (vanishing_polynomial.tcc:314-371)
 //   x_div_by_vanishing_dev, x_vanishing_host       the head route's pointwise division by Z_S and the host's Z_S(x) (include/libiop_amd_head.h)
+//   x_div_dev, x_domain_offsets_dev, x_vanishing_evals_dev, x_rational_combine_dev, x_rational_sumcheck_constraint_dev
+//                                                  the holographic prover's steps, the twins of fractal_ops.hip (include/libiop_amd_fractal.h)
 //
 // Every kernel reads each input once and writes the output once, in a grid-stride loop.  An element travels as F::mem through F::load<A16> /
 // F::store<A16>: the A16 instantiation (16-byte accesses) runs when every device pointer that it reads or writes 16 bytes at a time is 16-byte
@@ -22,7 +24,7 @@
 // such an element and the plain name.  Constants of a launch (coefficients, the squares of a base, the terms of a division pass) travel in
 // the kernel's argument block: no upload.  The domain-shaped values Z_I(x_j), Z_H(x_j), x_j, x_j^|H| are subset sums of an (m + 1)-entry
 // table over the bits of j (linearized_polynomial.tcc:83-108); position j + 1 of a pair differs from position j by the table's entry for
-// bit 0.  No LDS.  The grid is capped by the option IOPX_GFX_OPS_MAX_BLOCKS (default 16384, looked up per launch; a test helper: a small cap
+// bit 0.  No LDS but the product tree of the batch division (kx_div).  The grid is capped by the option IOPX_GFX_OPS_MAX_BLOCKS (default 16384, looked up per launch; a test helper: a small cap
 // sends every grid-stride loop round again at a few thousand elements).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,19 +56,21 @@ template<class F, bool A16> constexpr int ops_lane = A16 && F::W == 1 ? 2 : 1;
 // the others) when `a16`, K<F, false> otherwise, under the matching profile name: the field's stem + the kernel's name (+ "_w64"), built once
 // per launch site and field.  Where the two would be the same code (a one-word element, one element per lane) there is one instantiation
 // and one name, without "_w64".
-#define IOPX_OPS_LAUNCH(a16, name, bytes, K, lane, work, ...)                                                          \
+#define IOPX_OPS_LAUNCH(a16, name, bytes, K, lane, work, ...) IOPX_OPS_LAUNCH_ON(a16, name, bytes, K, lane, work, ops_grid_x, 0, __VA_ARGS__)
+// ... with the grid as GRID(slots of `lane` elements) and `lds` bytes of dynamic LDS
+#define IOPX_OPS_LAUNCH_ON(a16, name, bytes, K, lane, work, GRID, lds, ...)                                            \
     do {                                                                                                               \
         constexpr size_t lane_ = (lane);                                                                               \
         constexpr bool forms_ = F::W > 1 || lane_ > 1;                                                                 \
         const bool a16_ = forms_ && (a16);                                                                             \
         static const std::string names_[2] = { std::string(F::stem()) + name, std::string(F::stem()) + name + "_w64" }; \
         ProfScope ps_(names_[forms_ && !a16_ ? 1 : 0].c_str(), bytes);                                                 \
-        const dim3 grid_(ops_grid_x(a16_ ? ((work) + lane_ - 1) / lane_ : (work)));                                    \
+        const dim3 grid_(GRID(a16_ ? ((work) + lane_ - 1) / lane_ : (work)));                                          \
         if constexpr (forms_) {                                                                                        \
-            if (a16_) hipLaunchKernelGGL((K<F, true>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                    \
-            else hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                        \
+            if (a16_) hipLaunchKernelGGL((K<F, true>), grid_, dim3(256), lds, stream(), __VA_ARGS__);                  \
+            else hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), lds, stream(), __VA_ARGS__);                      \
         } else {                                                                                                       \
-            hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), 0, stream(), __VA_ARGS__);                             \
+            hipLaunchKernelGGL((K<F, false>), grid_, dim3(256), lds, stream(), __VA_ARGS__);                           \
         }                                                                                                              \
     } while (0)
 
@@ -368,6 +372,255 @@ __global__ void __launch_bounds__(256) kx_lincheck(LincheckParamsX<F> p)
         comb = L::mul(comb, L::load(p.p1, j, p.n));
         comb = L::add(comb, L::mul(L::load(p.fz, j, p.n), L::load(p.p2, j, p.n)));
         L::store(p.out, j, p.n, comb);
+    }
+}
+
+// ---- the holographic (Fractal) prover's steps: the twins of fractal_ops.hip ------------------------------------------------------
+template<class F>
+__device__ __forceinline__ bool ops_is_zero(const typename F::mem &v)
+{
+    if constexpr (F::W == 1) return v == 0;
+    else {
+        uint64_t any = 0;
+#pragma unroll
+        for (int i = 0; i < F::W; ++i) any |= v.w[i];
+        return any == 0;
+    }
+}
+
+// the V elements of a lane's value, one by one (LaneX<F, A16, V>::val is the element itself at V = 1)
+template<class F, bool A16, int V>
+__device__ __forceinline__ void lane_split(const typename LaneX<F, A16, V>::val &x, typename F::mem (&e)[V])
+{
+    if constexpr (V == 1) e[0] = x;
+    else {
+#pragma unroll
+        for (int i = 0; i < V; ++i) e[i] = x.e[i];
+    }
+}
+template<class F, bool A16, int V>
+__device__ __forceinline__ typename LaneX<F, A16, V>::val lane_join(const typename F::mem (&e)[V])
+{
+    if constexpr (V == 1) return e[0];
+    else {
+        typename LaneX<F, A16, V>::val x;
+#pragma unroll
+        for (int i = 0; i < V; ++i) x.e[i] = e[i];
+        return x;
+    }
+}
+
+// out[j] = num[j] / den[j] (num null: 1 / den[j]; a zero denominator yields zero, utils.tcc:79-97) by Montgomery's trick, as k_div_gf192: a logical
+// lane walks the slots lane, lane + T, ... of the launch (a slot: the V consecutive elements of one access), parks its running products in the
+// OUTPUT on the way up and consumes them on the way down; the 256 lanes of a workgroup combine their totals in an LDS tree (511 nodes), so a
+// workgroup pays for ONE field inversion (lane 0's serial work).  A zero denominator, and the absent position at the end of an odd n, is stepped
+// over as a one.  Written over logical lanes, so that any block size runs the same arithmetic.
+template<class F>
+struct DivParamsX {
+    const uint64_t *num;        // nullable
+    const uint64_t *den;
+    uint64_t *out;              // distinct from num and den
+    size_t n;
+};
+
+static constexpr unsigned DIVX_LANES = 256, DIVX_TREE_NODES = 2 * DIVX_LANES - 1, DIVX_SLOTS_PER_LANE = 16, DIVX_MAX_BLOCKS = 2048;
+__device__ __forceinline__ unsigned divx_level_base(int l) { return 2 * DIVX_LANES - ((2 * DIVX_LANES) >> l); }
+
+// a^-1 for a != 0 by the binary extended Euclidean algorithm on polynomials over GF(2), as gf_inv_euclid of fractal_ops.hip: g a = u and h a = v
+// modulo the field's polynomial f = x^(64 W) + F::MODULUS_LOW, and the one of higher degree absorbs a shifted copy of the other until u = 1; at most
+// 2 * 64 W shift-and-XOR steps on W + 1 words, for the ONE lane that inverts a workgroup's root.  Every index below is a constant once the loops are
+// unrolled, so the four values stay in registers (no scratch memory: the register report of DESIGN.md §5.18).
+template<int N>
+__device__ __forceinline__ int poly_degree(const uint64_t (&x)[N])
+{
+    int d = -1;
+#pragma unroll
+    for (int i = 0; i < N; ++i) if (x[i]) d = 64 * i + 63 - __builtin_clzll(x[i]);
+    return d;
+}
+template<int N>
+__device__ __forceinline__ void poly_xor_shifted(uint64_t (&x)[N], const uint64_t (&y)[N], int j)
+{
+    const int bs = j & 63, ws = j >> 6;
+    uint64_t t[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) t[i] = bs ? (y[i] << bs) | (i ? y[i - 1] >> (64 - bs) : 0) : y[i];
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        if (ws == c) {
+#pragma unroll
+            for (int i = 0; i + c < N; ++i) x[i + c] ^= t[i];
+        }
+    }
+}
+template<class F>
+__device__ inline typename F::mem ops_inv_euclid(const typename F::mem &a)
+{
+    constexpr int W = F::W, N = W + 1;
+    uint64_t u[N], v[N], g[N], h[N];
+    memcpy(u, &a, 8 * W);                   // F::mem is W words
+    u[W] = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) { v[i] = 0; g[i] = 0; h[i] = 0; }
+    v[0] = F::MODULUS_LOW; v[W] = 1; g[0] = 1;
+    int du = poly_degree<N>(u), dv = 64 * W;
+    while (du > 0) {
+        int j = du - dv;
+        if (j < 0) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) { uint64_t t = u[i]; u[i] = v[i]; v[i] = t; t = g[i]; g[i] = h[i]; h[i] = t; }
+            const int d = du; du = dv; dv = d;
+            j = -j;
+        }
+        poly_xor_shifted<N>(u, v, j);
+        poly_xor_shifted<N>(g, h, j);
+        du = poly_degree<N>(u);
+    }
+    typename F::mem r;
+    memcpy(&r, g, 8 * W);
+    return r;
+}
+
+// EUCLID: the root is inverted by ops_inv_euclid, otherwise by the field's Fermat power (F::inv)
+template<class F, bool A16, bool EUCLID>
+__device__ __forceinline__ void div_body(const DivParamsX<F> &p)
+{
+    constexpr int V = ops_lane<F, A16>;
+    typedef LaneX<F, A16> L;
+    typedef typename F::mem mem;
+    extern __shared__ __attribute__((aligned(16))) uint64_t iopx_smem[];
+    mem *tree = reinterpret_cast<mem *>(iopx_smem);
+    const size_t T = (size_t)gridDim.x * DIVX_LANES;
+    const size_t slots = (p.n + V - 1) / V;
+    const mem one = F::one();
+    const unsigned tid = threadIdx.x, nt = blockDim.x;      // read once, as the other LDS kernels do
+    for (unsigned lane = tid; lane < DIVX_LANES; lane += nt) {
+        mem run = one;
+        for (size_t s = (size_t)blockIdx.x * DIVX_LANES + lane; s < slots; s += T) {
+            mem d[V];
+            lane_split<F, A16, V>(L::load(p.den, V * s, p.n), d);
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                if (!ops_is_zero<F>(d[e])) run = F::mul(run, d[e]);
+                d[e] = run;
+            }
+            L::store(p.out, V * s, p.n, lane_join<F, A16, V>(d));
+        }
+        tree[lane] = run;
+    }
+    __syncthreads();
+    for (int l = 1; (DIVX_LANES >> l) >= 1; ++l) {
+        const unsigned cnt = DIVX_LANES >> l, base = divx_level_base(l), below = divx_level_base(l - 1);
+        for (unsigned i = tid; i < cnt; i += nt) tree[base + i] = F::mul(tree[below + 2 * i], tree[below + 2 * i + 1]);
+        __syncthreads();
+    }
+    if (tid == 0) tree[DIVX_TREE_NODES - 1] = EUCLID ? ops_inv_euclid<F>(tree[DIVX_TREE_NODES - 1]) : F::inv(tree[DIVX_TREE_NODES - 1]);   // never zero: a product of non-zero elements
+    __syncthreads();
+    for (int l = 8; l >= 1; --l) {
+        const unsigned cnt = DIVX_LANES >> l, base = divx_level_base(l), below = divx_level_base(l - 1);
+        for (unsigned i = tid; i < cnt; i += nt) {
+            const mem inv = tree[base + i], left = tree[below + 2 * i], right = tree[below + 2 * i + 1];
+            tree[below + 2 * i] = F::mul(inv, right);
+            tree[below + 2 * i + 1] = F::mul(inv, left);
+        }
+        __syncthreads();
+    }
+    for (unsigned lane = tid; lane < DIVX_LANES; lane += nt) {
+        const size_t first = (size_t)blockIdx.x * DIVX_LANES + lane;
+        const size_t count = first < slots ? (slots - first + T - 1) / T : 0;
+        mem inv = tree[lane];
+        for (size_t i = count; i-- > 0; ) {
+            const size_t s = first + i * T;
+            mem d[V], before[V], q[V];
+            lane_split<F, A16, V>(L::load(p.den, V * s, p.n), d);
+            // the running product in front of each element: the one parked by the previous element of this slot, or by the last of the previous slot
+            lane_split<F, A16, V>(L::load(p.out, V * s, p.n), before);
+#pragma unroll
+            for (int e = V - 1; e > 0; --e) before[e] = before[e - 1];
+            before[0] = i ? F::template load<A16>(p.out, V * (s - T) + (V - 1)) : one;
+            typename L::val nm = L::splat(one);
+            if (p.num) nm = L::load(p.num, V * s, p.n);
+#pragma unroll
+            for (int e = V - 1; e >= 0; --e) {
+                const bool zero = ops_is_zero<F>(d[e]);
+                q[e] = zero ? F::zero() : F::mul(before[e], inv);                                // 1 / d
+                if (!zero) inv = F::mul(inv, d[e]);
+            }
+            typename L::val r = lane_join<F, A16, V>(q);
+            if (p.num) r = L::mul(r, nm);
+            L::store(p.out, V * s, p.n, r);
+        }
+    }
+}
+
+template<class F, bool A16> __global__ void __launch_bounds__(256) kx_div(DivParamsX<F> p) { div_body<F, A16, false>(p); }
+template<class F, bool A16> __global__ void __launch_bounds__(256) kx_div_euclid(DivParamsX<F> p) { div_body<F, A16, true>(p); }
+
+// out[j] = tab[0] + sum_{bit k of j} tab[1 + k]: point - x over a domain (domain_offsets), c - Z_S(x) (vanishing_evals)
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_subset_sums(uint64_t *out, const uint64_t *tab, int m, size_t n)
+{
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, n) L::store(out, j, n, L::sums(tab, m, j));
+}
+
+// N = sum_i c_i N_i prod_{k != i} D_k, D = prod_k D_k (rational_linear_combination.tcc:13-108)
+#define RATIONALX_MAX 4
+template<class F>
+struct RationalParamsX {
+    const uint64_t *N[RATIONALX_MAX], *D[RATIONALX_MAX];
+    typename F::mem c[RATIONALX_MAX];
+    uint64_t *outN, *outD;
+    int num;
+    size_t n;
+};
+
+// One rational after the other: with (N, D) the combination of the first i, the next one gives (N D_i + c_i N_i D, D D_i).  Three products per further
+// rational (13 at four, against 19 for the sum term by term), and only N, D and the rational at hand are live whatever the number of rationals: no
+// array indexed up to a bound of the launch (it would live in scratch memory), no unrolled copies of the body per count.
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_rational_combine(RationalParamsX<F> p)
+{
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, p.n) {
+        typename L::val numer = L::mul(L::load(p.N[0], j, p.n), L::splat(p.c[0])), denom = L::load(p.D[0], j, p.n);
+#pragma unroll 1
+        for (int i = 1; i < p.num; ++i) {
+            const typename L::val d = L::load(p.D[i], j, p.n);
+            const typename L::val term = L::mul(L::mul(L::load(p.N[i], j, p.n), L::splat(p.c[i])), denom);
+            numer = L::add(L::mul(numer, d), term);
+            denom = L::mul(denom, d);
+        }
+        L::store(p.outN, j, p.n, numer);
+        L::store(p.outD, j, p.n, denom);
+    }
+}
+
+// q(x) = (D(x) (p(x) + eps^-1 mu x^(|K| - 1)) - N(x)) / Z_K(x) (rational_sumcheck.tcc:58-112); x^(|K| - 1) = x^|K| / x with x^|K| a subset sum and
+// 1 / x supplied by the caller; Z_K is constant on the cosets of K, the blocks position >> k of the codeword domain: one entry of a table each
+template<class F>
+struct ConstraintParamsX {
+    const uint64_t *p, *N, *D, *xinv;
+    const uint64_t *ktab;       // (m + 1)-entry subset-sum table of x^|K|
+    const uint64_t *zinv;       // 2^(m - k) entries
+    typename F::mem c;          // eps^-1 mu
+    uint64_t *out;
+    int m, k;
+    size_t n;
+};
+
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_sumcheck_constraint(ConstraintParamsX<F> a)
+{
+    typedef LaneX<F, A16> L;
+    OPSX_LOOP_V((ops_lane<F, A16>), j, a.n) {
+        const typename L::operand pp = L::fetch(a.p, j, a.n), nn = L::fetch(a.N, j, a.n), dd = L::fetch(a.D, j, a.n), xi = L::fetch(a.xinv, j, a.n);
+        const typename L::cosets z = L::coset(a.zinv, j, a.k, a.n);
+        typename L::val s = L::mul(L::mul(L::sums(a.ktab, a.m, j), L::splat(a.c)), L::get(xi, j, a.n));
+        s = L::add(s, L::get(pp, j, a.n));
+        // characteristic 2: D s - N = D s + N
+        const typename L::val t = L::add(L::mul(L::get(dd, j, a.n), s), L::get(nn, j, a.n));
+        L::store(a.out, j, a.n, L::mul(t, L::entry(z)));
     }
 }
 
@@ -752,6 +1005,150 @@ static int x_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *s
     return IOPX_OK;
 }
 
+// ---- the holographic prover's entries: the arguments, refusals and messages of the gf192 entries of fractal_ops.hip ----------------------------
+// 16 slots per lane while that fills the GPU (the shared inversion is one lane's serial work per workgroup), 2048 workgroups at most
+static int div_grid_x(size_t slots)
+{
+    size_t cap = (size_t)opt_range("IOPX_GFX_OPS_MAX_BLOCKS", 16384, 1, 16384);
+    if (cap > DIVX_MAX_BLOCKS) cap = DIVX_MAX_BLOCKS;
+    size_t g = (slots + DIVX_LANES * DIVX_SLOTS_PER_LANE - 1) / (DIVX_LANES * DIVX_SLOTS_PER_LANE);
+    if (g > cap) g = cap;
+    return (int)(g ? g : 1);
+}
+
+template<class F>
+static int x_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t n)
+{
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (n == 0) return IOPX_OK;
+    if (!d_den || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (d_out == d_den || d_out == d_num) return fail(IOPX_ERR_INVALID_ARGUMENT, "the quotient buffer holds the running products: it cannot alias an input");
+    DivParamsX<F> p;
+    p.num = d_num; p.den = d_den; p.out = d_out; p.n = n;
+    // den read twice, out written twice and read once (, num read once).  The root's inversion: the field's measured choice (F::DIV_EUCLID, DESIGN.md
+    // §5.18), or what the option IOPX_GFX_DIV_INVERSION asks for (1: the Fermat power, 2: Euclid; a measuring and test helper, looked up per launch)
+    const int inversion = opt_range("IOPX_GFX_DIV_INVERSION", 0, 0, 2);
+    const bool a16 = ops_al16(d_den) && ops_al16(d_out) && (!d_num || ops_al16(d_num));
+    const size_t bytes = n * 8 * F::W * (d_num ? 6 : 5), lds = (size_t)DIVX_TREE_NODES * 8 * F::W + 8;
+    if (inversion ? inversion == 2 : F::DIV_EUCLID) IOPX_OPS_LAUNCH_ON(a16, "div", bytes, kx_div_euclid, (ops_lane<F, true>), n, div_grid_x, lds, p);
+    else IOPX_OPS_LAUNCH_ON(a16, "div", bytes, kx_div, (ops_lane<F, true>), n, div_grid_x, lds, p);
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// d_out[j] = tab[0] + the subset sum of tab[1..m] over the bits of j; tab: the (m + 1) entries of a launch, uploaded (a domain of dimension 40
+// has 41: too many for the argument block at four words beside nothing else, and a table costs one small copy)
+template<class F, bool OFFSETS>
+static int subset_sums_x(const std::vector<uint64_t> &tab, size_t m, uint64_t *d_out)
+{
+    int rc;
+    TmpBuf dt;
+    if ((rc = dt.alloc(tab.size() * 8)) != IOPX_OK) return rc;
+    if ((rc = upload(dt.p, tab.data(), tab.size() * 8)) != IOPX_OK) return rc;
+    const size_t n = (size_t)1 << m;
+    // one kernel under the name of its caller (a launch site builds its profile names once)
+    if (OFFSETS) IOPX_OPS_LAUNCH(ops_al16(d_out) && ops_table_al16<F>(dt.p), "domain_offsets", n * 8 * F::W, kx_subset_sums, (ops_lane<F, true>), n, d_out, (const uint64_t *)dt.u64(), (int)m, n);
+    else IOPX_OPS_LAUNCH(ops_al16(d_out) && ops_table_al16<F>(dt.p), "vanishing_evals", n * 8 * F::W, kx_subset_sums, (ops_lane<F, true>), n, d_out, (const uint64_t *)dt.u64(), (int)m, n);
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+// d_out[j] = point - x_j over span(basis[0..m)) + shift
+template<class F>
+static int x_domain_offsets_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)
+{
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if ((m > 0 && !basis) || !shift || !point || !d_out) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
+    std::vector<uint64_t> tab(F::W * (m + 1));
+    for (int w = 0; w < F::W; ++w) tab[w] = shift[w] ^ point[w];               // point - x = point + shift + sum of basis vectors
+    if (m) memcpy(&tab[F::W], basis, 8 * F::W * m);
+    return subset_sums_x<F, true>(tab, m, d_out);
+}
+
+// d_out[j] = constant - Z_S(x_j) over span(basis[0..m)) + shift, S = span(vanishing_basis) + vanishing_shift
+template<class F>
+static int x_vanishing_evals_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *vanishing_basis, size_t vanishing_dim,
+                                 const uint64_t *vanishing_shift, const uint64_t *constant, uint64_t *d_out)
+{
+    typedef typename F::host H;
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if ((m > 0 && !basis) || !shift || (vanishing_dim > 0 && !vanishing_basis) || !vanishing_shift || !constant || !d_out)
+        return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (m > 40 || vanishing_dim > 63) return fail(IOPX_ERR_INVALID_ARGUMENT, "domain dimension too large");
+    const std::vector<H> vb = host_elems_x<F>(vanishing_basis, vanishing_dim);
+    const SubspacePolyX<H> lin(vb.data(), vanishing_dim);
+    std::vector<uint64_t> tab;
+    push_x<F>(tab, H(constant) + lin.eval(H(shift)) + lin.eval(H(vanishing_shift)));
+    for (size_t k = 0; k < m; ++k) push_x<F>(tab, lin.eval(H(basis + F::W * k)));
+    return subset_sums_x<F, false>(tab, m, d_out);
+}
+
+template<class F>
+static int x_rational_combine_dev(const void *const *d_N, const void *const *d_D, size_t num, const uint64_t *coeffs, size_t n, uint64_t *d_outN,
+                                  uint64_t *d_outD)
+{
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!d_N || !d_D || !coeffs || !d_outN || !d_outD) return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (num == 0 || num > RATIONALX_MAX) return fail(IOPX_ERR_INVALID_ARGUMENT, "Expected same number of evaluations as in registration.");
+    RationalParamsX<F> p;
+    memset(&p, 0, sizeof(p));
+    bool a16 = ops_al16(d_outN) && ops_al16(d_outD);
+    for (size_t i = 0; i < num; ++i) {
+        if (!d_N[i] || !d_D[i]) return fail(IOPX_ERR_INVALID_ARGUMENT, "null oracle");
+        p.N[i] = (const uint64_t *)d_N[i]; p.D[i] = (const uint64_t *)d_D[i];
+        memcpy(&p.c[i], coeffs + F::W * i, 8 * F::W);
+        a16 = a16 && ops_al16(d_N[i]) && ops_al16(d_D[i]);
+    }
+    p.outN = d_outN; p.outD = d_outD; p.num = (int)num; p.n = n;
+    if (n == 0) return IOPX_OK;
+    IOPX_OPS_LAUNCH(a16, "rational_combine", n * 8 * F::W * (2 * num + 2), kx_rational_combine, (ops_lane<F, true>), n, p);
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
+template<class F>
+static int x_rational_sumcheck_constraint_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, const uint64_t *d_xinv, const uint64_t *basis,
+                                              size_t m, const uint64_t *shift, size_t summation_dim, const uint64_t *summation_shift,
+                                              const uint64_t *claimed_sum, uint64_t *d_out)
+{
+    typedef typename F::host H;
+    int rc = ensure_device();
+    if (rc != IOPX_OK) return rc;
+    if (!d_p || !d_N || !d_D || !d_xinv || !d_out || (m > 0 && !basis) || !shift || !summation_shift || !claimed_sum)
+        return fail(IOPX_ERR_INVALID_ARGUMENT, "null argument");
+    if (summation_dim > m || m > 40) return fail(IOPX_ERR_INVALID_ARGUMENT, "the summation domain must be spanned by a prefix of the codeword domain's basis");
+    const size_t k = summation_dim;
+    const std::vector<H> kb = host_elems_x<F>(basis, k);
+    const SubspacePolyX<H> lin(kb.data(), k);
+    if (lin.coeff[0].is_zero()) return fail(IOPX_ERR_INVALID_ARGUMENT, "the summation domain's basis is linearly dependent");
+    const H c = lin.coeff[0].inverse() * H(claimed_sum);                                   // eps^-1 mu (rational_sumcheck.tcc:52-56)
+    // 1 / Z_K per coset of K, and the subset-sum table of x^|K| over the codeword domain: functions of the two domains only, kept on the device
+    TmpBuf dz, dk;
+    if ((rc = vanishing_inverse_table_x<F>(basis, m, shift, k, summation_shift, dz, 5, "the codeword domain intersects the summation domain")) != IOPX_OK) return rc;
+    rc = cached_domain_table(table_key_x<F>(basis, m, shift, nullptr, k, summation_shift, 6), [&](std::vector<uint64_t> &tab) -> int {
+        for (size_t i = 0; i <= m; ++i) {
+            H v(i == 0 ? shift : basis + F::W * (i - 1));
+            for (size_t s = 0; s < k; ++s) v = v.squared();                                // v^|K|
+            push_x<F>(tab, v);
+        }
+        return IOPX_OK;
+    }, dk);
+    if (rc != IOPX_OK) return rc;
+    ConstraintParamsX<F> a;
+    memset(&a, 0, sizeof(a));
+    a.p = d_p; a.N = d_N; a.D = d_D; a.xinv = d_xinv; a.ktab = dk.u64(); a.zinv = dz.u64(); a.c = mem_of_x<F>(c); a.out = d_out;
+    a.m = (int)m; a.k = (int)k; a.n = (size_t)1 << m;
+    IOPX_OPS_LAUNCH(ops_al16(d_p) && ops_al16(d_N) && ops_al16(d_D) && ops_al16(d_xinv) && ops_al16(d_out) && ops_table_al16<F>(dk.p) && ops_table_al16<F>(dz.p),
+                    "rational_sumcheck_constraint", a.n * 8 * F::W * 5, kx_sumcheck_constraint, (ops_lane<F, true>), a.n, a);
+    IOPX_HIP(hipGetLastError());
+    return IOPX_OK;
+}
+
 } // namespace iopx
 
 // the C entries of one field: iopx_*_<field>_dev over the bodies above
@@ -814,5 +1211,29 @@ static int x_vanishing_host(const uint64_t *basis, size_t dim, const uint64_t *s
                                       uint64_t *linear_coefficient_out)                                                                                         \
     {                                                                                                                                                           \
         return iopx::x_vanishing_host<F>(basis, dim, shift, x, value_out, linear_coefficient_out);                                                              \
+    }                                                                                                                                                           \
+    int iopx_##FIELD##_div_dev(const uint64_t *d_num, const uint64_t *d_den, uint64_t *d_out, size_t count)                                                     \
+    {                                                                                                                                                           \
+        return iopx::x_div_dev<F>(d_num, d_den, d_out, count);                                                                                                  \
+    }                                                                                                                                                           \
+    int iopx_domain_offsets_##FIELD##_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *point, uint64_t *d_out)                       \
+    {                                                                                                                                                           \
+        return iopx::x_domain_offsets_dev<F>(basis, m, shift, point, d_out);                                                                                    \
+    }                                                                                                                                                           \
+    int iopx_vanishing_evals_##FIELD##_dev(const uint64_t *basis, size_t m, const uint64_t *shift, const uint64_t *vanishing_basis, size_t vanishing_dim,       \
+                                           const uint64_t *vanishing_shift, const uint64_t *constant, uint64_t *d_out)                                          \
+    {                                                                                                                                                           \
+        return iopx::x_vanishing_evals_dev<F>(basis, m, shift, vanishing_basis, vanishing_dim, vanishing_shift, constant, d_out);                               \
+    }                                                                                                                                                           \
+    int iopx_rational_combine_##FIELD##_dev(const void *const *d_numerators, const void *const *d_denominators, size_t num_rationals,                           \
+                                            const uint64_t *coefficients, size_t n, uint64_t *d_numerator_out, uint64_t *d_denominator_out)                     \
+    {                                                                                                                                                           \
+        return iopx::x_rational_combine_dev<F>(d_numerators, d_denominators, num_rationals, coefficients, n, d_numerator_out, d_denominator_out);               \
+    }                                                                                                                                                           \
+    int iopx_rational_sumcheck_constraint_##FIELD##_dev(const uint64_t *d_p, const uint64_t *d_N, const uint64_t *d_D, const uint64_t *d_xinv,                  \
+                                                        const uint64_t *basis, size_t m, const uint64_t *shift, size_t summation_dim,                           \
+                                                        const uint64_t *summation_shift, const uint64_t *claimed_sum, uint64_t *d_out)                          \
+    {                                                                                                                                                           \
+        return iopx::x_rational_sumcheck_constraint_dev<F>(d_p, d_N, d_D, d_xinv, basis, m, shift, summation_dim, summation_shift, claimed_sum, d_out);         \
     }                                                                                                                                                           \
     }

@@ -197,7 +197,6 @@ class GF64:
     """libff::gf64 (x^64 + x^4 + x^3 + x + 1, one word), additive arm.  Host scalars are (1,) uint64 arrays; the handful of host-side
     products run on Python integers."""
     name, additive, elem_bytes, words, soundness_bits = "gf64", True, 8, 1, 64
-    # nothing that only Fractal calls; lincomb_affine is there because its entry shares the kernel of lincomb
     entries = {
         "FFT": ("additive_FFT_gf64_dev", {}),
         "IFFT": ("additive_IFFT_gf64_dev", {}),
@@ -219,6 +218,12 @@ class GF64:
         "pow_table": ("pow_table_dev", {"words": 1}),
         "spmv": ("spmv_dev", {"words": 1}),
         "poly_div_vanishing": ("poly_div_vanishing_dev", {"words": 1}),
+        # what Fractal calls beyond Aurora: the entries of include/libiop_amd_fractal.h
+        "div": ("field_div_dev", {"words": 1}),
+        "domain_offsets": ("domain_offsets_dev", {"words": 1}),
+        "vanishing_evals": ("vanishing_evals_dev", {"words": 1}),
+        "rational_combine": ("rational_combine_dev", {"words": 1}),
+        "rational_sumcheck_constraint": ("rational_sumcheck_constraint_dev", {"words": 1}),
     }
 
     @staticmethod
@@ -346,6 +351,12 @@ class GF128(GF64):
         "pow_table": ("pow_table_dev", {"words": 2}),
         "spmv": ("spmv_dev", {"words": 2}),
         "poly_div_vanishing": ("poly_div_vanishing_dev", {"words": 2}),
+        # what Fractal calls beyond Aurora: the entries of include/libiop_amd_fractal.h
+        "div": ("field_div_dev", {"words": 2}),
+        "domain_offsets": ("domain_offsets_dev", {"words": 2}),
+        "vanishing_evals": ("vanishing_evals_dev", {"words": 2}),
+        "rational_combine": ("rational_combine_dev", {"words": 2}),
+        "rational_sumcheck_constraint": ("rational_sumcheck_constraint_dev", {"words": 2}),
     }
     _MASK = (1 << 64) - 1
 
@@ -446,6 +457,12 @@ class GF256(GF128):
         "pow_table": ("pow_table_dev", {"words": 4}),
         "spmv": ("spmv_dev", {"words": 4}),
         "poly_div_vanishing": ("poly_div_vanishing_dev", {"words": 4}),
+        # what Fractal calls beyond Aurora: the entries of include/libiop_amd_fractal.h
+        "div": ("field_div_dev", {"words": 4}),
+        "domain_offsets": ("domain_offsets_dev", {"words": 4}),
+        "vanishing_evals": ("vanishing_evals_dev", {"words": 4}),
+        "rational_combine": ("rational_combine_dev", {"words": 4}),
+        "rational_sumcheck_constraint": ("rational_sumcheck_constraint_dev", {"words": 4}),
     }
 
     @staticmethod
@@ -1010,6 +1027,11 @@ class GF64AuroraOps(GF64DeviceOps):
     calls (div, domain_offsets, domain_elements, vanishing_evals, lagrange_evals, rational_*) keep raising."""
 
 
+class GF64FractalOps(GF64AuroraOps):
+    """GF64AuroraOps plus what the Fractal prover (libiop_amd/fractal.py) calls: the iopx_*_gf64_dev entries of include/libiop_amd_fractal.h.  Constructed
+    by name — GF64AuroraOps and DeviceOps(...) over GF64 keep refusing what they refused before."""
+
+
 class GF128AuroraOps(GF128DeviceOps):
     """GF128DeviceOps plus what the Aurora prover calls: the iopx_*_gf128_dev entries of libiop_amd/csrc/gf128_ops.hip.  Constructed by name —
     DeviceOps(...) over GF128 keeps returning GF128DeviceOps.  The operators only Fractal calls keep raising."""
@@ -1044,6 +1066,8 @@ def _allow_only(cls, allowed, why):
 _GF64_WHY = "gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK and, through GF64AuroraOps, Aurora are the provers over this field)"
 _allow_only(GF64DeviceOps, _GF64_FRI, _GF64_WHY)
 _allow_only(GF64AuroraOps, _GF64_AURORA, _GF64_WHY)
+_allow_only(GF64FractalOps, _GF64_AURORA | {"div", "domain_offsets", "domain_elements", "vanishing_evals", "lagrange_evals", "rational_combine",
+                                            "rational_sumcheck_constraint"}, _GF64_WHY)
 _allow_only(GF128DeviceOps, _GF64_FRI, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(GF256DeviceOps, _GF64_FRI, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(GF128AuroraOps, _GF64_AURORA, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK and, through GF128AuroraOps, Aurora are the provers over this field)")

@@ -176,7 +176,7 @@ class SingleBoundaryConstraint(VirtualOracle):
         f, ops = self.ops.field, self.ops
         if f.element_in_domain(self.L, self.eval_point):
             raise NotImplementedError("the evaluation point lies in the codeword domain")
-        numerator = ops.lincomb_affine(constituents, f.neg(f.one()).reshape(1, 3), self.oracle_evaluation, constituents[0].shape[0])   # claimed - f
+        numerator = ops.lincomb_affine(constituents, f.neg(f.one()).reshape(1, -1), self.oracle_evaluation, constituents[0].shape[0])   # claimed - f
         return ops.div(numerator, ops.domain_offsets(self.L, self.eval_point))                                                      # / (point - x)
 
 
@@ -355,7 +355,7 @@ class HolographicMultiLincheck:
             combined_rational_over_K = self.rational_linear_combination[r].evaluated_contents(numerators, denominators)
             self.sumcheck_K[r].calculate_and_submit_proof(combined_rational_over_K)
             M_at_alpha_beta = self.sumcheck_K[r].get_claimed_sum()
-            IOP.submit_prover_message(self.M_at_alpha_beta[r], M_at_alpha_beta.reshape(1, 3))
+            IOP.submit_prover_message(self.M_at_alpha_beta[r], M_at_alpha_beta.reshape(1, -1))
             self.t_boundary_constraint[r].set_evaluation_point_and_eval(beta, M_at_alpha_beta)
             self.sumcheck_H[r].calculate_and_submit_proof()
 
@@ -381,15 +381,15 @@ def matrix_index_over_K(ops, M, K, H, input_variable_dim):
     row_times_col = ops.mul(row_evals, col_evals)
     if H.additive:                                            # (DZ_H) is the constant linear coefficient
         scale = f.inv(f.vanishing_derivative(H, f.zero(), ops.lib), ops.lib)
-        val_evals = ops.lincomb([M.d_coeff[:nnz]], scale.reshape(1, 3), nnz)
+        val_evals = ops.lincomb([M.d_coeff[:nnz]], scale.reshape(1, -1), nnz)
     else:                                                     # (DZ_H)(c) = |H| c^(|H| - 1) = |H| shift^|H| / c on the coset
         scale = f.inv(f.from_int(H.size * pow(H.shift_int, H.size, f.P)))
-        val_evals = ops.lincomb([ops.mul(M.d_coeff[:nnz], col_evals)], scale.reshape(1, 3), nnz)
+        val_evals = ops.lincomb([ops.mul(M.d_coeff[:nnz], col_evals)], scale.reshape(1, -1), nnz)
     pad = K.size - nnz
     h0 = H_elements[:1]
     k0 = ops.domain_elements(K)[:1]
-    padded = lambda t, fill: t if pad == 0 else torch.cat([t, fill.expand(pad, 3)])
-    zero = ops.upload(f.zero().reshape(1, 3))
+    padded = lambda t, fill: t if pad == 0 else torch.cat([t, fill.expand(pad, fill.shape[-1])])
+    zero = ops.upload(f.zero().reshape(1, -1))
     rows, cols = padded(row_evals, h0), padded(col_evals, h0)
     vals, rcs = padded(val_evals, zero), padded(row_times_col, ops.mul(k0, k0))
     return [cols.contiguous(), rows.contiguous(), vals.contiguous(), rcs.contiguous()]                   # "We are dealing with the transpose"

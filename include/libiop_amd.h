@@ -404,7 +404,8 @@ int iopx_gf256_inverse_host(const uint64_t *x, uint64_t *out);
 /* iopx_{gf64,gf128,gf256}_div_dev, iopx_domain_offsets_*_dev, iopx_vanishing_evals_*_dev, iopx_rational_combine_*_dev and
  * iopx_rational_sumcheck_constraint_*_dev: the gf192 entries of those names in this file at one, two and four words per element, declared once for
  * the three fields in libiop_amd_fractal.h (beside this file).  With them iopx_fractal_index / iopx_fractal_prove run over IOPX_FIELD_GF64 when the
- * option IOPX_GFX_FRACTAL is non-zero (default 0: refused, as over gf128 and gf256 whatever the option says). */
+ * option IOPX_GFX_FRACTAL is non-zero, and over IOPX_FIELD_GF128 and IOPX_FIELD_GF256 when the option IOPX_GFX_FRACTAL_WIDE is non-zero (both default 0:
+ * refused; neither option speaks for the other's fields). */
 #include "libiop_amd_fractal.h"
 
 /* ---- BCS Merkle tree, BLAKE2b ------------------------------------------------------------------- */
@@ -684,7 +685,7 @@ int iopx_pow_solve_poseidon_bn128(const iopx_poseidon_params *params, const uint
  * algorithmic_bytes = elements swept x 24 x (read + write) summed over the launches, 0 for kernels that do not report it). */
 /* Options: named integers that select a prover schedule or a tile geometry (the names are listed in DESIGN.md).  A name's value is what
  * iopx_set_option gave it, else the environment variable of that name (read once per process, at the name's first lookup), else the built-in
- * default.  Schedule options (IOPX_HEAD_EVAL, IOPX_GFX_HEAD_EVAL, IOPX_GFX_FRACTAL, IOPX_MERKLE_STREAM, IOPX_DEFER_ROOTS) are looked up per proof; tile geometries are latched by
+ * default.  Schedule options (IOPX_HEAD_EVAL, IOPX_GFX_HEAD_EVAL, IOPX_GFX_FRACTAL, IOPX_GFX_FRACTAL_WIDE, IOPX_MERKLE_STREAM, IOPX_DEFER_ROOTS) are looked up per proof; tile geometries are latched by
  * their component at its first use. */
 int iopx_set_option(const char *name, int value);
 int iopx_clear_option(const char *name);
@@ -774,7 +775,8 @@ int iopx_fp3_modulus(uint64_t *out);
 /* libff::gf128: Aurora instances from CSR matrices (iopx_aurora_instance_create; iopx_aurora_prove, iopx_aurora_prove_hashed with IOPX_HASH_BLAKE2B,
  * iopx_aurora_instance_warm) and the FRI-only SNARK on one GPU, 2 words per element, in the reference's schedule (head evaluation only under the option
  * IOPX_GFX_HEAD_EVAL, default 0: libiop_amd_head.h; re-extensions through libiop_amd_batch.h's fused entries).  Refused with IOPX_ERR_INVALID_ARGUMENT and a message that names gf128: a communicator, a Poseidon hash, iopx_fractal_index /
- * iopx_fractal_prove, a codeword domain of more than 2^IOPX_GFX_MAX_DOMAIN_DIM points (checked from the parameters before any device work), and
+ * iopx_fractal_prove unless the option IOPX_GFX_FRACTAL_WIDE is non-zero (default 0, looked up per call, whatever IOPX_GFX_FRACTAL holds; non-zero: the Fractal
+ * indexer and prover on one GPU with BLAKE2b, the bytes of tests/gfx_fractal_model.py; libiop_amd_fractal.h), a codeword domain of more than 2^IOPX_GFX_MAX_DOMAIN_DIM points (checked from the parameters before any device work), and
  * iopx_aurora_example_instance_create (the synthetic instance is not generated over this field: build it as CSR matrices plus an assignment). */
 #define IOPX_FIELD_GF128 5
 #define IOPX_GFX_MAX_DOMAIN_DIM 40

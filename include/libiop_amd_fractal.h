@@ -19,7 +19,12 @@
  * reports the other form under the kernel's name + "_w64").
  *
  * With them iopx_fractal_index, iopx_fractal_prove and iopx_aurora_instance_warm(..., protocol 1) run over IOPX_FIELD_GF64 (one GPU, BLAKE2b) when the
- * option IOPX_GFX_FRACTAL is non-zero (default 0: refused as before).  Over gf128 and gf256 they stay refused: no independent expected bytes exist.  The
+ * option IOPX_GFX_FRACTAL is non-zero (default 0: refused as before), and over IOPX_FIELD_GF128 and IOPX_FIELD_GF256 when the option
+ * IOPX_GFX_FRACTAL_WIDE is non-zero (default 0, looked up per call: refused in the words of before, whatever IOPX_GFX_FRACTAL holds; gf64 is governed by
+ * IOPX_GFX_FRACTAL alone).  A communicator, an unsupported security parameter, a codeword domain above the transforms' cap (before any device work) and a
+ * proof without an index keep their refusals with either option set.  iopx_rational_combine_FIELD_dev has two forms over an element of several words,
+ * one rational after the other with inlined products and a lean one through a single product site (same arguments, refusals, profile row, declared
+ * bytes and output bytes); the option IOPX_GFX_RATIONAL_FORM picks one per launch (0: the field's measured choice, 1: inlined, 2: lean).  The
  * Python binding lists these names in libiop_amd.FRACTAL_SYMBOLS, beside EXPORTED_SYMBOLS, GFX_OPS_SYMBOLS, BATCH_SYMBOLS and HEAD_SYMBOLS. */
 #ifndef LIBIOP_AMD_FRACTAL_H
 #define LIBIOP_AMD_FRACTAL_H

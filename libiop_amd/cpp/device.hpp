@@ -52,9 +52,13 @@ struct field_host {
     static FieldT neg(const FieldT &a) { return sub(zero(), a); }
     static FieldT inverse(const FieldT &a) { uint64_t w[WORDS]; check(entry(&P::host_inverse, "inverse")(detail::words(&a), w)); return from_words(w); }
     // Over gf64, gf128 and gf256 only the head route and the Fractal prover ask for Z_S on the host, and they sit behind IOPX_GFX_HEAD_EVAL and
-    // IOPX_GFX_FRACTAL: with both options unset the two subspace forms below are refused as before either existed (nothing observable changes); with
-    // one set they go through the field's vanishing_host slot
-    static bool subspace_host_forms() { return WORDS == 3 || iopx_get_option("IOPX_GFX_HEAD_EVAL", 0) != 0 || iopx_get_option("IOPX_GFX_FRACTAL", 0) != 0; }
+    // IOPX_GFX_FRACTAL / IOPX_GFX_FRACTAL_WIDE: with the three options unset the two subspace forms below are refused as before any of them existed
+    // (nothing observable changes); with one set they go through the field's vanishing_host slot
+    static bool subspace_host_forms()
+    {
+        return WORDS == 3 || iopx_get_option("IOPX_GFX_HEAD_EVAL", 0) != 0 || iopx_get_option("IOPX_GFX_FRACTAL", 0) != 0 ||
+               iopx_get_option("IOPX_GFX_FRACTAL_WIDE", 0) != 0;
+    }
     // Z_S(x) for the domain S (vanishing_polynomial::evaluation_at_point): the linearized polynomial of the subspace through the
     // library's host helper / x^|S| - shift^|S| (vanishing_polynomial.tcc:14-25)
     static FieldT vanishing_eval(const field_subset<FieldT> &S, const FieldT &x)

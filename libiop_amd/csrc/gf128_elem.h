@@ -36,6 +36,7 @@ struct Elem128 {
 
     static constexpr uint64_t MODULUS_LOW = 0x87;               // x^128 + x^7 + x^2 + x + 1 without its leading term
     static constexpr bool DIV_EUCLID = true;                    // kx_div inverts a workgroup's root by the binary Euclid: measured faster
+    static constexpr bool RATIONAL_LEAN = false;                // kx_rational_combine keeps its inlined products: the lean form measured slower
 
     // the host side
     typedef hgf128 host;

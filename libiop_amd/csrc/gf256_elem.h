@@ -50,6 +50,7 @@ struct Elem256 {
 
     static constexpr uint64_t MODULUS_LOW = 0x425;               // x^256 + x^10 + x^5 + x^2 + 1 without its leading term
     static constexpr bool DIV_EUCLID = true;                    // kx_div inverts a workgroup's root by the binary Euclid: measured faster
+    static constexpr bool RATIONAL_LEAN = true;                 // kx_rational_combine_lean is the rational combination's form: measured faster
 
     // the host side
     typedef hgf256 host;

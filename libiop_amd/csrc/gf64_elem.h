@@ -24,6 +24,7 @@ struct Elem64 {
 
     static constexpr uint64_t MODULUS_LOW = 0x1B;               // x^64 + x^4 + x^3 + x + 1 without its leading term
     static constexpr bool DIV_EUCLID = true;                    // kx_div inverts a workgroup's root by the binary Euclid: measured faster
+    static constexpr bool RATIONAL_LEAN = false;                // kx_rational_combine keeps its inlined products: one form over a one-word element
 
     // the host side
     typedef hgf64 host;

@@ -596,6 +596,51 @@ __global__ void __launch_bounds__(256) kx_rational_combine(RationalParamsX<F> p)
     }
 }
 
+// The lean form of the same recurrence for an element of several words (one element per lane): the products of a lane run one after the other
+// through ONE product site, a rolled loop whose trip picks its operands by the phase it is in, and every value stays in F::reg form from its load
+// (one unpack) to the two stores (one pack each).  Per further rational i the phases are
+//   0: t = N_i c_i (and D_i is loaded)    1: t = t D    2: N = N D_i + t    3: D = D D_i
+// and the first rational takes phase 0 alone (N = N_0 c_0): 1 + 4 (num - 1) products, the count of the form above.  Live across the site: N, D,
+// t, D_i and the two operands, whatever the number of rationals; the phase and the rational's index are uniform over the launch (scalar
+// registers, scalar branches).  Field arithmetic is exact, so the outputs are the bytes of the form above.  Which form a field takes by default
+// is F::RATIONAL_LEAN, a measurement; the option IOPX_GFX_RATIONAL_FORM overrides it per launch.
+template<class F, bool A16>
+__global__ void __launch_bounds__(256) kx_rational_combine_lean(RationalParamsX<F> p)
+{
+    typedef typename F::reg R;
+    OPSX_LOOP(j, p.n) {
+        R numer = F::unpack(F::zero()), t = numer, d = numer;
+        R denom = F::unpack(F::template load<A16>(p.D[0], j));
+        int i = 0, phase = 0;
+#pragma unroll 1
+        while (i < p.num) {
+            R a, b;
+            if (phase == 0) {
+                a = F::unpack(F::template load<A16>(p.N[i], j));
+                b = F::unpack(p.c[i]);
+                if (i) d = F::unpack(F::template load<A16>(p.D[i], j));
+            } else if (phase == 1) {
+                a = t; b = denom;
+            } else {
+                a = phase == 2 ? numer : denom; b = d;
+            }
+            const R r = F::rmul(a, b);
+            if (phase == 0) {
+                if (i == 0) { numer = r; i = 1; }
+                else { t = r; phase = 1; }
+            } else if (phase == 1) {
+                t = r; phase = 2;
+            } else if (phase == 2) {
+                numer = F::unpack(F::add(F::pack(r), F::pack(t))); phase = 3;
+            } else {
+                denom = r; phase = 0; ++i;
+            }
+        }
+        F::template store<A16>(p.outN, j, F::pack(numer));
+        F::template store<A16>(p.outD, j, F::pack(denom));
+    }
+}
+
 // q(x) = (D(x) (p(x) + eps^-1 mu x^(|K| - 1)) - N(x)) / Z_K(x) (rational_sumcheck.tcc:58-112); x^(|K| - 1) = x^|K| / x with x^|K| a subset sum and
 // 1 / x supplied by the caller; Z_K is constant on the cosets of K, the blocks position >> k of the codeword domain: one entry of a table each
 template<class F>
@@ -1106,7 +1151,16 @@ static int x_rational_combine_dev(const void *const *d_N, const void *const *d_D
     }
     p.outN = d_outN; p.outD = d_outD; p.num = (int)num; p.n = n;
     if (n == 0) return IOPX_OK;
-    IOPX_OPS_LAUNCH(a16, "rational_combine", n * 8 * F::W * (2 * num + 2), kx_rational_combine, (ops_lane<F, true>), n, p);
+    // The form: the field's measured choice (F::RATIONAL_LEAN), or what the option IOPX_GFX_RATIONAL_FORM asks for (1: one rational
+    // after the other with inlined products, 2: the lean form; a measuring and test helper, looked up per launch).  The lean form exists for an
+    // element of several words; over a one-word element every value of the option gives the one form there is.
+    const int form = opt_range("IOPX_GFX_RATIONAL_FORM", 0, 0, 2);
+    bool lean = false;
+    if constexpr (F::W > 1) lean = form ? form == 2 : F::RATIONAL_LEAN;
+    if constexpr (F::W > 1) {
+        if (lean) IOPX_OPS_LAUNCH(a16, "rational_combine", n * 8 * F::W * (2 * num + 2), kx_rational_combine_lean, 1, n, p);
+    }
+    if (!lean) IOPX_OPS_LAUNCH(a16, "rational_combine", n * 8 * F::W * (2 * num + 2), kx_rational_combine, (ops_lane<F, true>), n, p);
     IOPX_HIP(hipGetLastError());
     return IOPX_OK;
 }

@@ -60,34 +60,36 @@ struct Instance : InstanceBase {
     static constexpr bool binary = field_kind<F>::type == affine_subspace_type;      // 32 bytes are alt_bn128 Fr or gf256: the kind tells them apart
     static constexpr bool bn128 = !binary && sizeof(F) == 32;     // alt_bn128 Fr: Aurora only, on one GPU
     static constexpr bool gf64 = binary && sizeof(F) == 8;        // gf64: Aurora, and Fractal behind IOPX_GFX_FRACTAL; on one GPU, BLAKE2b
-    static constexpr bool gf128 = binary && sizeof(F) == 16;      // gf128, gf256: as gf64
+    static constexpr bool gf128 = binary && sizeof(F) == 16;      // gf128, gf256: as gf64, with Fractal behind IOPX_GFX_FRACTAL_WIDE
     static constexpr bool gf256 = binary && sizeof(F) == 32;
     static constexpr bool gfx = gf128 || gf256;
     static const char *gfx_name() { return gf128 ? "gf128" : "gf256"; }
-    // gf64: Fractal behind the option IOPX_GFX_FRACTAL (default 0, looked up per call: unset, the refusal of before the prover was built), on one GPU; a
-    // codeword domain past the transforms' cap is refused before any device work
-    void gf64_fractal(const char *entry, iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) const
+    static const char *subspace_name() { return gf64 ? "gf64" : gfx_name(); }
+    // gf64, gf128, gf256: Fractal behind an option (default 0, looked up per call: unset, the refusal of before the prover was built) — IOPX_GFX_FRACTAL
+    // for gf64, IOPX_GFX_FRACTAL_WIDE for gf128 and gf256, neither speaking for the other — on one GPU; a codeword domain past the transforms' cap is
+    // refused before any device work
+    void subspace_fractal(const char *entry, iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) const
     {
-        if (iopx_get_option("IOPX_GFX_FRACTAL", 0) == 0) throw std::invalid_argument(std::string(entry) + ": there is no Fractal prover over gf64");
-        if (comm) throw std::invalid_argument("gf64 has no distributed prover: pass no communicator");
+        const std::string name = subspace_name();
+        if (iopx_get_option(gf64 ? "IOPX_GFX_FRACTAL" : "IOPX_GFX_FRACTAL_WIDE", 0) == 0) throw std::invalid_argument(std::string(entry) + ": there is no Fractal prover over " + name);
+        if (comm) throw std::invalid_argument(name + " has no distributed prover: pass no communicator");
         require_supported_security(security_parameter);
         const fractal_snark_parameters<F> params(cs, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
-        if (params.codeword_domain_dim_ > IOPX_GF64_MAX_DOMAIN_DIM)
-            throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": the gf64 transforms take domains of dimension up to " +
-                                        std::to_string(IOPX_GF64_MAX_DOMAIN_DIM));
+        const size_t cap = gf64 ? IOPX_GF64_MAX_DOMAIN_DIM : IOPX_GFX_MAX_DOMAIN_DIM;
+        if (params.codeword_domain_dim_ > cap)
+            throw std::invalid_argument("codeword domain dimension " + std::to_string(params.codeword_domain_dim_) + ": the " + name + " transforms take domains of dimension up to " +
+                                        std::to_string(cap));
     }
     std::vector<std::string> fractal_index(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
         if constexpr (bn128) throw std::invalid_argument("iopx_fractal_index: there is no Fractal prover over alt_bn128 Fr");
-        else if constexpr (gf64) return gf64_fractal("iopx_fractal_index", comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter), fractal_index_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
-        else if constexpr (gfx) throw std::invalid_argument(std::string("iopx_fractal_index: there is no Fractal prover over ") + gfx_name());
+        else if constexpr (gf64 || gfx) return subspace_fractal("iopx_fractal_index", comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter), fractal_index_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
         else return fractal_index_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
     }
     std::string fractal_prove(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter) override
     {
         if constexpr (bn128) throw std::invalid_argument("iopx_fractal_prove: there is no Fractal prover over alt_bn128 Fr");
-        else if constexpr (gf64) return gf64_fractal("iopx_fractal_prove", comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter), fractal_prove_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
-        else if constexpr (gfx) throw std::invalid_argument(std::string("iopx_fractal_prove: there is no Fractal prover over ") + gfx_name());
+        else if constexpr (gf64 || gfx) return subspace_fractal("iopx_fractal_prove", comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter), fractal_prove_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
         else return fractal_prove_(comm, security_parameter, RS_extra_dimensions, FRI_localization_parameter);
     }
     std::vector<std::string> fractal_index_(iopx_comm *comm, size_t security_parameter, size_t RS_extra_dimensions, size_t FRI_localization_parameter)

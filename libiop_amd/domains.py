@@ -1042,6 +1042,16 @@ class GF256AuroraOps(GF256DeviceOps):
     DeviceOps(...) over GF256 keeps returning GF256DeviceOps.  The operators only Fractal calls keep raising."""
 
 
+class GF128FractalOps(GF128AuroraOps):
+    """GF128AuroraOps plus what the Fractal prover (libiop_amd/fractal.py) calls: the iopx_*_gf128_dev entries of include/libiop_amd_fractal.h.
+    Constructed by name — GF128AuroraOps and DeviceOps(...) over GF128 keep refusing what they refused before."""
+
+
+class GF256FractalOps(GF256AuroraOps):
+    """GF256AuroraOps plus what the Fractal prover (libiop_amd/fractal.py) calls: the iopx_*_gf256_dev entries of include/libiop_amd_fractal.h.
+    Constructed by name — GF256AuroraOps and DeviceOps(...) over GF256 keep refusing what they refused before."""
+
+
 _OPERATORS = frozenset(name for name, f in vars(DeviceOps).items() if callable(f) and not name.startswith("__") and name != "_call")
 _GF64_FRI = frozenset({"local_size", "mark_codeword_domain", "mark_fri_domains", "query_responses", "empty", "upload", "download", "FFT", "IFFT",
                        "IFFT_of_known_degree", "fold", "solve_pow", "merkle_tree", "ldt_combine"})
@@ -1066,12 +1076,15 @@ def _allow_only(cls, allowed, why):
 _GF64_WHY = "gf64: DeviceOps.%s has no GF(2^64) entry (the FRI-only SNARK and, through GF64AuroraOps, Aurora are the provers over this field)"
 _allow_only(GF64DeviceOps, _GF64_FRI, _GF64_WHY)
 _allow_only(GF64AuroraOps, _GF64_AURORA, _GF64_WHY)
-_allow_only(GF64FractalOps, _GF64_AURORA | {"div", "domain_offsets", "domain_elements", "vanishing_evals", "lagrange_evals", "rational_combine",
-                                            "rational_sumcheck_constraint"}, _GF64_WHY)
+_GFX_FRACTAL = _GF64_AURORA | {"div", "domain_offsets", "domain_elements", "vanishing_evals", "lagrange_evals", "rational_combine",
+                               "rational_sumcheck_constraint"}
+_allow_only(GF64FractalOps, _GFX_FRACTAL, _GF64_WHY)
 _allow_only(GF128DeviceOps, _GF64_FRI, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(GF256DeviceOps, _GF64_FRI, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK is the prover over this field)")
 _allow_only(GF128AuroraOps, _GF64_AURORA, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK and, through GF128AuroraOps, Aurora are the provers over this field)")
 _allow_only(GF256AuroraOps, _GF64_AURORA, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK and, through GF256AuroraOps, Aurora are the provers over this field)")
+_allow_only(GF128FractalOps, _GFX_FRACTAL, "gf128: DeviceOps.%s has no GF(2^128) entry (the FRI-only SNARK and, through GF128AuroraOps and GF128FractalOps, Aurora and Fractal are the provers over this field)")
+_allow_only(GF256FractalOps, _GFX_FRACTAL, "gf256: DeviceOps.%s has no GF(2^256) entry (the FRI-only SNARK and, through GF256AuroraOps and GF256FractalOps, Aurora and Fractal are the provers over this field)")
 _allow_only(AltBn128DeviceOps, _OPERATORS - {"_coset_range"}, "DeviceOps.%s: coset ranges belong to the additive re-extension: no alt_bn128 Fr form")
 
 
